@@ -1,6 +1,6 @@
 """Benchmark of the PFN training hot path on MI355X (contract: see the task statement / DESIGN.md).
 
-    python bench.py [--config 2|4|5] --gpus N --steps K --warmup W
+    python bench.py [--config 2|4|5] --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no torchrun environment spawns the N ranks itself (same torch.distributed.run command line).
@@ -10,7 +10,12 @@ datasets from the prior (HIP sampler), forward through the PFN (HIP), loss (HIP 
 all-reduce of the flat gradient], clip + Adam (HIP).  The metric is synthetic datasets / second over all ranks (weak
 scaling: per-GPU batch fixed).  The default is configs[1] (the configuration the metric is quoted on).
 
-The JSON line also carries
+A plain run sets up, runs W untimed and K timed steps, writes the outputs of the last timed step when --dump-outputs is given
+(DIR/<name>.npy: `loss`, `parameters`, `grad_norm`, see timed_outputs) and prints the line: the contract keys, `config` and
+`step_roofline` (FLOP arithmetic on the timed window, no run of its own).  Every side measurement below runs only with --full
+(the --no-* flags then drop single ones of them).
+
+With --full the JSON line also carries
   roofline     : the step's dominant kernel (picked by launches x isolated duration): `frac` / `achieved` = algorithmic FLOPs (mask-aware,
                  SURVEY.md 8(d)) / its average launch duration INSIDE the running step -- HIP event pairs around the launches on their
                  launch stream (pfn_profile_*), two micro-batch streams + the sampler sharing the chip -- vs the dense bf16 MFMA peak;
@@ -26,7 +31,8 @@ The JSON line also carries
   val_bar_nll  : the loss of the benchmarked model on a fixed-seed validation draw (second half of BASELINE.json's metric);
   cpu_baseline : the reference's CPU path timed on the host cores on a bounded sample of the same workload from the same
                  weights and inputs (rank 0, N = 1 only): the torch nn.TransformerEncoder stack the reference instantiates
-                 (kind "torch-modules", the reported value) and the explicit-math port that is the parity checker.
+                 (kind "torch-modules", the reported value) and the explicit-math port that is the parity checker;
+  allreduce_ms : (N > 1) the two collectives of the gradient buffer timed alone, back to back, after the timed steps.
 """
 import argparse
 import contextlib
@@ -655,11 +661,13 @@ def read_profile():
 
 
 def run_config(config, device, rank, world, precision, batch=None, streams=None, steps=20, warmup=5, aggregate_k=1, fixed_sep=None, prefetch_group=None,
-               profile_steps=0, aggregate_streams=0, aggregate_stacked=False):
+               profile_steps=0, aggregate_streams=0, aggregate_stacked=False, capture_outputs=False, time_allreduce=False):
     """One benchmark run of a BASELINE.json configuration: builds criterion, model, optimizer and the prior's loader, runs `warmup` untimed and
     `steps` timed OPTIMIZER steps (each = `aggregate_k` batches of `batch` datasets per rank: forward + loss + backward per batch, gradients
     summed, then [all-reduce +] clip + Adam -- reference train.py:66-97) between barrier + synchronize on both sides, max over ranks.
-    profile_steps > 0: that many further steps with the library's in-step kernel timing on (not part of the timed window)."""
+    profile_steps > 0: that many further steps with the library's in-step kernel timing on (not part of the timed window).
+    capture_outputs: `outputs` = timed_outputs() of the last timed step, taken right after the timed window.
+    time_allreduce (N > 1): `allreduce_ms` = the two collectives timed alone after the timed window."""
     from transformerscandobayesianinference_amd import _hip, dp
     from transformerscandobayesianinference_amd.optim import FusedClipAdam
     from transformerscandobayesianinference_amd.streams import MicroBatchStreams
@@ -701,6 +709,7 @@ def run_config(config, device, rank, world, precision, batch=None, streams=None,
         reducer = dp.OverlappedGradientReducer(model)
 
     stacked = aggregate_stacked and aggregate_k > 1 and micro.can_stack(model)
+    last = {}      # the per-(position, dataset) losses of the latest batch (a reference to the step's own tensor: no work added)
 
     def step(batches):
         if stacked:      # the batches of the optimizer step as one launch set per micro-batch stream, every dataset with its own eval position (streams.py)
@@ -715,6 +724,7 @@ def run_config(config, device, rank, world, precision, batch=None, streams=None,
             if reducer is not None:
                 reducer.finish()
             opt.step(zero_grad=True)
+            last['losses'] = outs[-1]
             return outs[-1].mean()
         for k in range(aggregate_k):       # reference train.py:92-97: micro-batch gradients are summed, one optimizer step per aggregate_k batches
             sep = fixed_sep if fixed_sep is not None else sampler()
@@ -734,6 +744,7 @@ def run_config(config, device, rank, world, precision, batch=None, streams=None,
         if reducer is not None:
             reducer.finish()       # two collectives: the upper layers' half was enqueued behind their weight gradients, under the backward
         opt.step(zero_grad=True)
+        last['losses'] = losses
         return losses.mean()
 
     def barrier():
@@ -770,6 +781,8 @@ def run_config(config, device, rank, world, precision, batch=None, streams=None,
     timed_seps = list(seps)
     out = dict(config=config, w=w, model=model, batch=batch, streams=streams, steps=steps, warmup=warmup, aggregate_k=aggregate_k, group=group, seps=timed_seps,
                micro_groups=micro.groups(model, batch))
+    if capture_outputs:
+        out['outputs'] = timed_outputs(model, opt, last['losses'])
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         every = [torch.zeros_like(t) for _ in range(world)]
@@ -782,14 +795,15 @@ def run_config(config, device, rank, world, precision, batch=None, streams=None,
         grad = model.flat_parameters()[1]
         out['overlapped_in_steps'] = bool(reducer.overlapped_last_step)
         out['fallback_steps'] = reducer.fallbacks
-        barrier()
-        t1 = time.time()
-        for _ in range(5):
-            reducer.finish()           # not armed: both collectives back to back, nothing to hide behind = the exposed cost
-        torch.cuda.synchronize()
-        out['allreduce_ms'] = (time.time() - t1) / 5 * 1e3
+        if time_allreduce:
+            barrier()
+            t1 = time.time()
+            for _ in range(5):
+                reducer.finish()           # not armed: both collectives back to back, nothing to hide behind = the exposed cost
+            torch.cuda.synchronize()
+            out['allreduce_ms'] = (time.time() - t1) / 5 * 1e3
+            grad.zero_()
         out['reducer_layout'] = reducer.layout()
-        grad.zero_()
     out['elapsed'], out['local_elapsed'], out['final_loss'] = elapsed, local_elapsed, loss.item()
     if profile_steps > 0 and world == 1:
         # the same steps once more with an event pair around every launch of the step's kernel classes, ON their launch streams: how long each
@@ -845,6 +859,42 @@ def inference_cost(model, w, device, sep):
     out['batch'] = B
     out['inference_extra_weight_bytes'] = int(model._eval_shadow.numel()) if getattr(model, '_eval_shadow', None) is not None else 0
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_CAP = {'loss': 1 << 22, 'parameters': 1 << 23}      # elements per array: 16 + 32 MiB of float32 at most
+
+
+def dump_sample(t, cap, seed=0):
+    """`t` whole when it has at most `cap` elements; otherwise a fixed seeded sample of `cap` of its elements (flat indices drawn with
+    replacement by a CPU generator seeded with `seed`, sorted), the same positions on every run of the same shape."""
+    if t.numel() <= cap:
+        return t
+    idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(seed)).sort()[0]
+    return t.reshape(-1)[idx.to(t.device)]
+
+
+def timed_outputs(model, opt, losses):
+    """What a caller of the timed step receives from its last step, as host arrays:
+      loss       [T - sep, batch] float32: the per-(position, dataset) losses of the step's (last) batch on this rank;
+      parameters float32: the flat parameter buffer after the step's clip + Adam update (a fixed seeded sample when larger than DUMP_CAP);
+      grad_norm  [1] float64: the global gradient norm the update saw, before clipping."""
+    import numpy as np
+    flat = model.flat_parameters()[0]
+    return {'loss': dump_sample(losses.detach().float(), DUMP_CAP['loss']).cpu().numpy(),
+            'parameters': dump_sample(flat.detach().float(), DUMP_CAP['parameters']).cpu().numpy(),
+            'grad_norm': np.array([opt.last_grad_norm()], dtype=np.float64)}
+
+
+def write_outputs(directory, outputs):
+    """outputs {name: float32 / float64 array} -> directory/<name>.npy"""
+    import numpy as np
+    total = sum(a.nbytes for a in outputs.values())
+    assert total <= DUMP_LIMIT_BYTES, f'outputs of {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte dump limit'
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, f'{name}.npy'), a)
 
 
 def release(r):
@@ -947,14 +997,21 @@ def main():
     ap.add_argument('--precision', default='fp16', choices=['bf16', 'fp16', 'f32'],
                     help='operand format of the TIMED (training) path, recorded as `dtype`.  fp16 (round 6): the 16-bit format whose training forward holds the north star\'s 1e-3 on NLL and '
                          'posterior means (same MFMA rate and bytes as bf16; gradients under a device-side loss scale); the bf16 figures ride along as `also_bf16`')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true')
-    ap.add_argument('--no-kernel-breakdown', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip `other_configs` (short runs of configs 4 and 5) and `batch_sweep` (configs[1] at per-GPU batch 4 x 25, 8, 16, 32)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all): loss, parameters, grad_norm')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every side measurement: in-step and isolated kernel timings (roofline, kernels), parity against the f64 oracle, '
+                         'val_bar_nll, cpu_baseline, also_bf16, other_configs, batch_sweep, allreduce_ms (N > 1).  Off: the headline figure only')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip `cpu_baseline`')
+    ap.add_argument('--no-parity', action='store_true', help='with --full: skip the parity blocks, `val_bar_nll` and `cpu_baseline`')
+    ap.add_argument('--no-kernel-breakdown', action='store_true', help='with --full: skip the in-step profile steps and the kernel table (`roofline`, `kernels`)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip `also_bf16`, `other_configs` (short runs of configs 4 and 5) and `batch_sweep` (configs[1] at per-GPU batch 4 x 25, 8, 16, 32)')
     ap.add_argument('--fixed-sep', type=int, default=None, help='use one eval position instead of the sampler')
     ap.add_argument('--prefetch-group', type=int, default=None, help='steps of datasets per sampler call (default: the loader class\'s; the bench uses its gcd with --steps)')
     ap.add_argument('--tune', default='', help='experiments: comma-separated key=value pairs for pfn_set_tuning (include/pfn_hip.h); recorded in config')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)
 
@@ -973,9 +1030,12 @@ def main():
     t_start = time.time()
     r = run_config(args.config, device, rank, world, args.precision, batch=args.batch, streams=args.streams, steps=args.steps, warmup=args.warmup,
                    aggregate_k=args.aggregate_k, fixed_sep=args.fixed_sep, prefetch_group=args.prefetch_group, aggregate_streams=args.aggregate_streams, aggregate_stacked=args.aggregate_stacked,
-                   profile_steps=0 if (world > 1 or args.no_kernel_breakdown) else 5)
+                   profile_steps=5 if (args.full and world == 1 and not args.no_kernel_breakdown) else 0,
+                   capture_outputs=args.dump_outputs is not None and rank == 0, time_allreduce=args.full)
     if rank != 0:
         return
+    if args.dump_outputs is not None:
+        write_outputs(args.dump_outputs, r.pop('outputs'))
     model, batch, streams, seps = r['model'], r['batch'], r['streams'], r['seps']
     S, nf, E, F, L, O = w['bptt'], w['num_features'], w['emsize'], w['nhid'], w['nlayers'], w['num_bars']
     tp = throughput_fields(r, world)
@@ -1005,18 +1065,19 @@ def main():
     if world > 1:
         result['ranks_seen'] = r['ranks_seen']
         result['per_rank_ms_per_step'] = [e / args.steps * 1e3 for e in r['per_rank_elapsed']]      # spread = load imbalance / stragglers at the all-reduce
-        result['allreduce_ms'] = r['allreduce_ms']
+        if 'allreduce_ms' in r:
+            result['allreduce_ms'] = r['allreduce_ms']
         result['allreduce_bytes'] = model.flat_parameters()[1].numel() * 4
         result['allreduce_overlapped'] = dict(r['reducer_layout'], in_timed_steps=r['overlapped_in_steps'], fallback_steps=r['fallback_steps'],
                                               note='the gradient buffer is reduced as two collectives; `overlapped_bytes` (upper half of the layers + '
                                                    'decoder) start behind those layers\' weight gradients and run under the rest of the backward, '
-                                                   '`exposed_bytes` after it; allreduce_ms = both collectives timed alone, back to back (an upper bound on what a step '
+                                                   '`exposed_bytes` after it; allreduce_ms (--full) = both collectives timed alone, back to back (an upper bound on what a step '
                                                    'can lose to communication); fallback_steps = armed steps whose early collective could not be overlapped')
         result['collective_backend'] = torch.distributed.get_backend()
         result['devices_visible'] = torch.cuda.device_count()
         if os.environ.get('PFN_DP_SINGLE_DEVICE') == '1':
             result['ranks_share_device'] = True    # one-GPU test hook: NOT a scaling measurement
-    if world == 1 and not args.no_kernel_breakdown:
+    if args.full and world == 1 and not args.no_kernel_breakdown:
         # kernels are launched per micro-batch (column group of the batch, streams.py): time them at THAT shape
         groups = r['micro_groups']
         mean_sep = int(round(sum(seps) / len(seps)))
@@ -1081,7 +1142,7 @@ def main():
                                       '`achieved` / `avg_launch_us` = the same kernel class timed inside the step'}
         result['kernels'] = [{k: (round(v, 6) if isinstance(v, float) else v) for k, v in kk.items()} for kk in ks]
         result['in_step_kernel_us'] = {k: dict(avg_us=round(v['avg_us'], 2), launches=v['launches']) for k, v in in_step.items()}
-    if world == 1 and not args.no_parity:
+    if args.full and world == 1 and not args.no_parity:
         parity, inputs = parity_check(model, w, device, args.precision)
         timed = parity.pop('training_forward')
         timed['mean_ref_rms'] = parity['mean_ref_rms']      # the scale `mean_rel_l2` divides by (targets: y_test_rms)
@@ -1098,7 +1159,7 @@ def main():
         if not args.no_cpu_baseline:
             result['cpu_baseline'] = cpu_baseline(w, inputs)
     result['seconds_main_line'] = time.time() - t_start
-    if world == 1 and not args.no_extras and args.config == 2 and args.batch is None and args.aggregate_k == 1:
+    if args.full and world == 1 and not args.no_extras and args.config == 2 and args.batch is None and args.aggregate_k == 1:
         release(r)
         del model
         result['other_configs'] = {}

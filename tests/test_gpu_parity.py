@@ -1037,12 +1037,12 @@ def test_failed_cholesky_is_repaired_with_jitter():
 def test_bench_self_launches_the_ranks_on_one_device(ranks):
     """`python bench.py --gpus N` without a torchrun environment spawns the ranks itself; on a one-GPU box the PFN_DP_* hooks put
     every rank on device 0 over gloo (RCCL refuses two ranks per device) -- the line must say so, count every rank, carry the per-rank step times, the
-    all-reduce figures and the fallback count, and stay inside the 6 KB contract (N = 8: what the driver's scaling run launches)."""
+    all-reduce figures (`allreduce_ms`: --full) and the fallback count, and stay inside the 6 KB contract (N = 8: what the driver's scaling run launches)."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(PFN_DP_BACKEND='gloo', PFN_DP_SINGLE_DEVICE='1')
-    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(ranks), '--steps', '2', '--warmup', '1', '--batch', '4'],
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(ranks), '--steps', '2', '--warmup', '1', '--batch', '4', '--full'],
                          capture_output=True, text=True, env=env, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     text = [l for l in res.stdout.splitlines() if l.startswith('{')][-1]
@@ -1539,14 +1539,14 @@ def test_rccl_data_parallel_on_two_gpus(tmp_path):
 
 
 def test_bench_on_two_gpus_over_rccl():
-    """`python bench.py --gpus 2` end to end (the driver's scaling run launches exactly this): rank 0's JSON line says the collectives ran on RCCL,
+    """`python bench.py --gpus 2 --full` end to end (the driver's scaling run launches it without --full): rank 0's JSON line says the collectives ran on RCCL,
     both ranks were seen, the timed steps took the overlapped two-collective path, and carries the numbers that make an 8-GPU line diagnosable
     (allreduce_ms, exposed bytes, per-rank step times).  Skipped on a one-GPU box."""
     _two_gpus()
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if not k.startswith('PFN_DP_')}
-    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2'], capture_output=True, text=True,
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2', '--full'], capture_output=True, text=True,
                          env=env, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][-1])
@@ -1579,15 +1579,15 @@ def test_fast_gp_mix_get_model_samples_like_the_reference_call_sequence():
 
 
 def test_bench_line_contract():
-    """The driver parses the LAST stdout line of the DEFAULT command `python bench.py --gpus 1 --steps 20 --warmup 5` (round 4's 26 KB line lost its head in
-    the driver's 8 KB tail): the line is one compact JSON object of at most 6 KB carrying every key of the contract with the right type, the metric / workload
+    """The driver parses the LAST stdout line of `python bench.py --gpus 1 --steps 20 --warmup 5`, here with every side measurement on (--full; round 4's 26 KB
+    line lost its head in the driver's 8 KB tail): the line is one compact JSON object of at most 6 KB carrying every key of the contract with the right type, the metric / workload
     are BASELINE.json's, `roofline` and `cpu_baseline` carry their fields, one number each for configs[3], configs[4] and the batch sweep, and the timed
     window fits inside the command's own clock.  The full record goes to bench_detail.json."""
     import json, subprocess, sys, time
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT') and not k.startswith('PFN_DP_')}
     t0 = time.time()
-    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5'], capture_output=True, text=True, env=env, timeout=1200)
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5', '--full'], capture_output=True, text=True, env=env, timeout=1200)
     wall = time.time() - t0
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -1618,6 +1618,44 @@ def test_bench_line_contract():
     assert len(d['batch_sweep']) >= 4 and all(e['value'] > 0 for e in d['batch_sweep'])
     detail = json.load(open(os.path.join(root, d['detail'])))
     assert detail['value'] == pytest.approx(d['value'], rel=1e-4) and 'kernels' in detail and 'legs' in detail['cpu_baseline']
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline only: one line with the contract keys, `steps` = K, `ms_per_step` = the
+    timed window / K, and none of the side measurements of --full.  --dump-outputs writes what the last timed step computed (the losses of its batch,
+    the updated parameters, the gradient norm) as float32 / float64 .npy within 64 MB, and two runs of the same arguments draw the same inputs: under
+    the bit-reproducible schedule (PFN_BENCH_DETERMINISTIC=1) they write the same arrays."""
+    import json, subprocess, sys, time
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT') and not k.startswith('PFN_DP_')}
+    env['PFN_BENCH_DETERMINISTIC'] = '1'
+    runs = []
+    for i in range(2):
+        out = tmp_path / f'run{i}'
+        t0 = time.time()
+        res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(out)],
+                             capture_output=True, text=True, env=env, timeout=600)
+        wall = time.time() - t0
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        lines = [l for l in res.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d['n_gpus'] == 1 and d['steps'] == 3 and d['warmup'] == 1 and d['unit'] == 'datasets/s' and d['higher_is_better'] is True and d['dtype'] == 'fp16'
+        assert abs(d['value'] - d['config']['global_batch'] * 1e3 / d['ms_per_step']) < 1e-4 * d['value']
+        assert d['ms_per_step'] * d['steps'] * 1e-3 < d['seconds_total'] <= wall
+        assert not set(d) & {'roofline', 'cpu_baseline', 'parity_inference', 'parity_timed_path', 'val_bar_nll', 'also_bf16', 'other_configs', 'batch_sweep'}
+        files = {p.stem: np.load(p) for p in out.glob('*.npy')}
+        assert set(files) == {'loss', 'parameters', 'grad_norm'}
+        assert sum(p.stat().st_size for p in out.glob('*.npy')) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and a.size and np.isfinite(a).all() for a in files.values())
+        assert files['loss'].shape[1] == d['config']['per_gpu_batch'] and files['grad_norm'][0] > 0
+        assert abs(float(files['loss'].mean()) - d['config']['final_loss']) < 1e-4 * abs(d['config']['final_loss'])
+        runs.append((d, files))
+    (d0, a), (d1, b) = runs
+    assert d0['config']['mean_sep'] == d1['config']['mean_sep']
+    for k in a:
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-5, atol=1e-6, err_msg=k)
 
 
 _DP_TRAIN_SCRIPT = r"""

@@ -203,6 +203,25 @@ def test_bench_profile_classes_match_the_header():
     assert max(enum.values()) + 2 == slots and all(v % 2 == 0 for v in enum.values())     # slot + 1 = the top layer's launch on the test rows
 
 
+def test_bench_output_dump_stays_within_its_limit(tmp_path):
+    """bench.py --dump-outputs: an array up to its cap is written whole, a larger one as a fixed seeded sample of `cap` elements (the same positions on
+    every call), every file a float32 / float64 .npy, and the caps keep the whole dump within 64 MB.  --full and --dump-outputs are options of the command."""
+    import numpy as np
+    import bench
+    assert sum(bench.DUMP_CAP.values()) * 4 <= bench.DUMP_LIMIT_BYTES - 4096
+    small = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    assert bench.dump_sample(small, 12) is small
+    big = torch.randn(5000)
+    a, b = bench.dump_sample(big, 100), bench.dump_sample(big.clone(), 100)
+    assert a.shape == (100,) and torch.equal(a, b) and all((big == v).any() for v in a)
+    bench.write_outputs(str(tmp_path / 'out'), {'loss': small.numpy(), 'grad_norm': np.array([1.5])})
+    assert np.load(tmp_path / 'out' / 'loss.npy').dtype == np.float32 and np.load(tmp_path / 'out' / 'grad_norm.npy').dtype == np.float64
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / 'bad'), {'index': np.arange(3)})
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0 and '--full' in res.stdout and '--dump-outputs' in res.stdout
+
+
 def test_one_image_layout_of_the_key_block_pass_is_bank_conflict_free():
     """attention.hip BwdKvCfg::ONE: query q of a 32-query tile sits in LDS row perm(q) (the two 2-bit fields of the row index swapped) under the row
     padding RB + 16 bytes.  Under the LDS model of MI355X_MICROARCH.md (64 banks of 4 bytes; ds_read_b128 served in the 16-lane groups listed there,

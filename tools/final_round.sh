@@ -16,10 +16,10 @@ for cfg in 2 4 5; do
 done
 PFN_RECORD_BOUNDS=$O/parity_measured.json python -m pytest tests -m gpu -q 2>&1 | tail -15 > $O/pytest.log
 for cfg in 2 4 5; do
-  python bench.py --config $cfg > $O/bench_config$cfg.line 2> $O/bench_config$cfg.err
+  python bench.py --full --config $cfg > $O/bench_config$cfg.line 2> $O/bench_config$cfg.err
   cp bench_detail.json $O/bench_config$cfg.json
 done
-python bench.py --precision bf16 --no-extras > $O/bench_config2_bf16.line 2> $O/bench_config2_bf16.err
+python bench.py --full --precision bf16 --no-extras > $O/bench_config2_bf16.line 2> $O/bench_config2_bf16.err
 cp bench_detail.json $O/bench_config2_bf16.json
 cp profiles/r06_pmc_traffic_config*.json profiles/r06_in_step_kernels_config*.json $O/ 2>/dev/null
 tail -3 $O/pytest.log; for cfg in 2 4 5; do head -c 700 $O/bench_config$cfg.line; echo; done; head -c 400 $O/bench_config2_bf16.line; echo; head -30 $O/profile_summary_config2.txt

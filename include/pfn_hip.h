@@ -53,7 +53,7 @@ enum { PFN_PREC_BF16 = 0, /* bf16 MFMA operands, f32 accumulate / residual / sta
  * (encoders.py:8), NoPositionalEncoding (positional_encodings.py:12-18) and the default
  * decoder Linear-GELU-Linear (transformer.py:23). */
 typedef struct pfn_model_desc {
-  int32_t num_features; /* x-encoder input width (train.py:33) */
+  int32_t num_features; /* x-encoder input width (train.py:33); 1 .. 1022: the embedding stages 16 tokens x (num_features + 2) f32 in 64 KB of LDS -- wider is PFN_ERR_UNSUPPORTED */
   int32_t emsize;       /* ninp */
   int32_t nhead;
   int32_t nhid;         /* FFN width and decoder hidden width (transformer.py:17,23) */

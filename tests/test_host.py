@@ -124,6 +124,20 @@ def test_param_layout_matches_reference_state_dict_order():
     assert lib.pfn_param_count(ctypes.byref(bad)) < 0 and b'head dim' in lib.pfn_last_error_string()
 
 
+def test_encoder_width_limit_is_refused_when_the_model_is_built():
+    """The widest fused embedding (include/pfn_hip.h num_features) fails in the descriptor check and in the model's constructor, not in a backward."""
+    lib = _hip.lib()
+    ok = _hip.ModelDesc(_hip.MAX_FEATURES, 128, 4, 256, 1, 20, _hip.PREC_FP16, 1e-5)
+    assert lib.pfn_param_count(ctypes.byref(ok)) > 0
+    wide = _hip.ModelDesc(_hip.MAX_FEATURES + 1, 128, 4, 256, 1, 20, _hip.PREC_FP16, 1e-5)
+    assert lib.pfn_param_count(ctypes.byref(wide)) < 0 and b'num_features' in lib.pfn_last_error_string()
+    from transformerscandobayesianinference_amd import encoders
+    from transformerscandobayesianinference_amd.transformer import TransformerModel
+    TransformerModel(encoders.Linear(_hip.MAX_FEATURES, 128), 20, 128, 4, 256, 1, y_encoder=encoders.Linear(1, 128))
+    with pytest.raises(ValueError, match='features'):
+        TransformerModel(encoders.Linear(_hip.MAX_FEATURES + 1, 128), 20, 128, 4, 256, 1, y_encoder=encoders.Linear(1, 128))
+
+
 def test_top_layer_row_rule_and_flop_accounting():
     """The stack drops the top encoder layer's train rows (the reference returns output[single_eval_pos:], transformer.py:91) under a rule that is
     host logic -- pfn_top_layer_rows -- and bench.py's FLOP count follows it."""

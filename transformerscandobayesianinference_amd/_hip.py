@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libpfn_hip.so')
 ABI_VERSION = 8
 
+MAX_FEATURES = 1022      # pfn_model_desc.num_features (include/pfn_hip.h): wider encoders are refused when the model is built
 PREC_BF16 = 0
 PREC_F32 = 1
 PREC_FP16 = 2      # fp16 MFMA operands under a device-side loss scale (include/pfn_hip.h): the timed path that holds the north star's 1e-3

@@ -69,6 +69,7 @@ int check_desc(const pfn_model_desc* d) {
   if (d->precision != PFN_PREC_BF16 && d->precision != PFN_PREC_F32 && d->precision != PFN_PREC_FP16) return fail(PFN_ERR_ARGUMENT, "bad precision %d", d->precision);
   if (d->num_features < 1 || d->emsize < 8 || d->nhead < 1 || d->nhid < 8 || d->nlayers < 0 || d->n_out < 0)
     return fail(PFN_ERR_ARGUMENT, "bad model dimensions");   // n_out == 0: no decoder -- the stack returns the encoder's test rows
+  if (d->num_features > EMB_MAX_FEATURES) return fail(PFN_ERR_UNSUPPORTED, "num_features %d > %d unsupported (the embedding stages 16 tokens x (num_features + 2) f32 in 64 KB of LDS)", d->num_features, EMB_MAX_FEATURES);
   if (d->emsize % d->nhead) return fail(PFN_ERR_ARGUMENT, "emsize %d not divisible by nhead %d", d->emsize, d->nhead);
   if (d->emsize % 8 || d->nhid % 8) return fail(PFN_ERR_UNSUPPORTED, "emsize and nhid must be multiples of 8 (16-byte operand rows)");
   const int dh = d->emsize / d->nhead;
@@ -133,6 +134,7 @@ struct Ws {
   float* x0; char* x0_t;
   char* xaug_t;              // [M, emb_aug_width(nf)] operand precision: the embedding's augmented inputs (embed_fwd -> the backward's GEMM)
   float* embacc;             // [E, emb_aug_width(nf)] f32: that GEMM's result before it is scattered into the encoder gradients
+  float* xaug_amax;          // fp16 only: [emb_aug_width(nf)] max|.| of every column of xaug_t, from which its power-of-two scale derives (launch_embed_colmax)
   std::vector<LayerWs> layer;
   char *xt_t, *dpre, *dt;
   // backward scratch
@@ -195,6 +197,7 @@ Ws carve(const pfn_model_desc& d, int B, int S, char* base) {
   w.x0 = (float*)take(M * E * 4); w.x0_t = take(M * E * es);
   const int64_t aug = emb_aug_width(d.num_features) > 0 ? emb_aug_width(d.num_features) : 32;
   w.xaug_t = take(M * aug * es); w.embacc = (float*)take(E * aug * 4);
+  w.xaug_amax = (float*)take(aug * 4);      // (carved in every precision: the workspace size depends on the operand width only)
   w.layer.resize(d.nlayers);
   for (auto& l : w.layer) {
     l.qkv = take(M * 3 * E * es); l.ctx = take(M * E * es); l.lse = (float*)take((int64_t)B * d.nhead * S * 4);
@@ -420,6 +423,11 @@ static int stack_forward_impl(const pfn_model_desc* d, const float* params, cons
     e.out_f32 = w.x0; e.out_t = w.x0_t; e.S = S; e.B = B; e.nf = d->num_features; e.E = E; e.sep = sep; e.sep_of = sep_of;
     e.xaug_ld = emb_aug_width(d->num_features);
     e.xaug_t = e.xaug_ld > 0 ? w.xaug_t : nullptr;
+    e.xaug_amax = nullptr;
+    if (e.xaug_t && prec == PFN_PREC_FP16) {      // fp16: every column of the backward's operand at its own power of two (launch_embed_colmax)
+      PFN_TRY(launch_embed_colmax(e, w.xaug_amax, s));
+      e.xaug_amax = w.xaug_amax;
+    }
     PFN_TRY(launch_embed_fwd(e, prec, s));
   }
   const float* xin = w.x0;
@@ -893,7 +901,7 @@ static int stack_backward_impl(const pfn_model_desc* d, const float* params, con
     g.scale_amax = lsc;
     g.max_splits = det ? 1 : 128;      // a 512 x 32 result: measured 67 / 62 / 88 us with 64 / 128 / 256 splits (the partial sums are added atomically)
     PFN_TRY(launch_gemm_tn(g, prec, s));
-    PFN_TRY(launch_embed_grad_scatter(w.embacc, grads + L.enc_w, grads + L.yenc_w, grads + L.yenc_b, E, d->num_features, s));
+    PFN_TRY(launch_embed_grad_scatter(w.embacc, grads + L.enc_w, grads + L.yenc_w, grads + L.yenc_b, E, d->num_features, prec == PFN_PREC_FP16 ? w.xaug_amax : nullptr, s));
   } else {
     EmbedBwdArgs e;
     e.dsrc = w.gA; e.x = x; e.x_st = x_st; e.x_sb = x_sb; e.y = y; e.y_st = y_st; e.y_sb = y_sb;

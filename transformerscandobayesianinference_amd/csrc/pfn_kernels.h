@@ -262,8 +262,8 @@ int launch_transpose_cast(const float* src, void* dst_t, int rows, int cols, lon
 int launch_cast_rows(const float* src, long ld_src, void* dst_t, long ld_dst, long R, int C, int precision, hipStream_t s, const float* scale_amax = nullptr);
 // ---- loss scale of the fp16 backward (pfn_device.h loss_scale_up / loss_scale_down): `scale_amax` arguments below point at ONE device float holding
 // max|incoming gradient| (launch_absmax), from which every kernel derives the same power of two; nullptr = no scaling (bf16 / f32) ----
-int launch_absmax(const float* x, long n, float* amax, hipStream_t s);
-int set_loss_scale_target(int log2_target);      // PFN_TUNE_LOSS_SCALE_TARGET                                   // amax[0] = max |x[i]| (x 16-byte aligned)
+int launch_absmax(const float* x, long n, float* amax, hipStream_t s);      // amax[0] = max |x[i]| (x 4-byte aligned: a head in front of the first 16-byte boundary is read by scalar loads)
+int set_loss_scale_target(int log2_target);      // PFN_TUNE_LOSS_SCALE_TARGET
 int launch_scale_copy(const float* src, float* dst, long n, const float* scale_amax, hipStream_t s);    // dst = src * 2^k
 
 // x:[T,B,nf] (strides given in elements), y:[T,B]; out f32 + T in [B,S,E]
@@ -275,25 +275,40 @@ struct EmbedArgs {
   float* out_f32; void* out_t;
   void* xaug_t;   // optional [B*S, xaug_ld] T: the token's features, masked y, train flag, zero padding -- the B operand of the backward's GEMM
   int xaug_ld;    // columns of xaug_t: emb_aug_width(nf)
+  const float* xaug_amax;   // optional [xaug_ld]: max|.| of every column of xaug_t (launch_embed_colmax); column f is then stored times 2^-xaug_col_exp(f)
   int S, B, nf, E, sep;
   const int* sep_of;   // ragged batch: per-dataset eval positions [B] on the device (then `sep` is unused); nullptr = every dataset at `sep`
 };
+// the widest encoder: embed_fwd_kernel stages 16 tokens x (nf + 2) f32 in at most 64 KB of LDS (check_desc; include/pfn_hip.h num_features)
+constexpr int EMB_MAX_FEATURES = 1022;
 // columns of xaug_t / of the [E, aug] gradient accumulator: num_features + 2 rounded up to 32, 64 or 128 (the GEMM form of the embedding backward; 0 = wider
 // encoders keep the register kernel).  Round 6: 64 and 128 added -- BASELINE configs[3] has 60 features and spent 9 % of its kernel time in embed_bwd_wide_kernel
 __host__ __device__ inline int emb_aug_width(int nf) { return nf + 2 <= 32 ? 32 : nf + 2 <= 64 ? 64 : nf + 2 <= 128 ? 128 : 0; }
 int launch_embed_fwd(const EmbedArgs& a, int precision, hipStream_t s);
+// fp16 xaug_t: amax[f] = max|column f| over the batch for the features and the masked y (a.xaug_ld floats, zeroed here; the train flag column and the padding stay 0).
+// Each column is stored in xaug_t times a power of two that brings its maximum into [1, 2): feature scales far from 1 neither round to fp16 subnormals nor
+// saturate, and embed_grad_scatter multiplies the same power back out exactly.  The logits never see it (the forward reads x in f32)
+int launch_embed_colmax(const EmbedArgs& a, float* amax, hipStream_t s);
+__device__ inline int xaug_col_exp(const float* amax, int f) {
+  if (!amax) return 0;
+  const float m = amax[f];
+  if (!(m > 0.f) || !(m <= 3.402823466e38f)) return 0;     // (an all-zero column, or a NaN / inf in it: unscaled)
+  const int e = ilogbf(m);
+  return e < -126 ? -126 : e;
+}
 // backward: dsrc [B,S,E] f32 -> dwx, dbx, dwy, dby (accumulated, f32)
 struct EmbedBwdArgs {
   const float* dsrc; const float* x; long x_st, x_sb; const float* y; long y_st, y_sb;
   float* dwx; float* dbx; float* dwy; float* dby;
   int S, B, nf, E, sep;
   const int* sep_of;    // ragged batch: per-dataset eval positions [B] (nullptr = every dataset at `sep`)
-  int single_block;     // 1: one workgroup per column block walks every token (one writer per gradient element: PFN_SCHED_DETERMINISTIC)
+  int single_block;     // 1: every workgroup walks every token (one writer per gradient element: PFN_SCHED_DETERMINISTIC)
   const float* scale_amax;   // fp16 backward: dsrc carries the loss scale, the gradients leave without it (nullptr = none)
 };
 int launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s);
 // the GEMM form: acc[E, aug] = d(src)^T . xaug (launch_gemm_tn), aug = emb_aug_width(nf) -> dwx += acc[:, :nf], dwy += acc[:, nf], dby += acc[:, nf + 1]
-int launch_embed_grad_scatter(const float* acc, float* dwx, float* dwy, float* dby, int E, int nf, hipStream_t s);
+// (xaug_amax: the column scales of xaug_t, multiplied back out; nullptr = none)
+int launch_embed_grad_scatter(const float* acc, float* dwx, float* dwy, float* dby, int E, int nf, const float* xaug_amax, hipStream_t s);
 
 // src given in the reference layout [S,B,E] f32 (custom encoders): copy into [B,S,E] f32 + T
 int launch_sbe_to_bse(const float* src, float* out_f32, void* out_t, int S, int B, int E, int precision, hipStream_t s);

@@ -72,12 +72,19 @@ int launch_cast_rows(const float* src, long ld_src, void* dst, long ld_dst, long
 __global__ __launch_bounds__(256) void absmax_kernel(const float* x, long n, unsigned* amax_bits, float bias) {
   __shared__ float red[4];
   float m = 0.f;
-  const long n4 = n / 4;
+  // (a gradient that is a view into a larger buffer -- e.g. the second part of a torch.cat -- need not start on a 16-byte boundary: the elements in front of
+  // the first one are read one at a time, like the tail)
+  const long head = std::min<long>(n, ((16 - (long)(reinterpret_cast<uintptr_t>(x) & 15)) & 15) / 4);
+  const float* xv = x + head;
+  const long nv = n - head, n4 = nv / 4;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * i);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(xv + 4 * i);
     m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));      // (fmaxf drops a NaN operand: a NaN gradient stays a NaN downstream, the scale stays sane)
   }
-  if (blockIdx.x == 0) for (long i = n4 * 4 + threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(x[i]));
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < head) m = fmaxf(m, fabsf(x[threadIdx.x]));
+    for (long i = n4 * 4 + threadIdx.x; i < nv; i += 256) m = fmaxf(m, fabsf(xv[i]));
+  }
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
@@ -93,7 +100,7 @@ int set_loss_scale_target(int t) {
   return PFN_OK;
 }
 int launch_absmax(const float* x, long n, float* amax, hipStream_t s) {
-  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0) return PFN_ERR_ALIGNMENT;
+  if ((reinterpret_cast<uintptr_t>(x) & 3) != 0) return PFN_ERR_ALIGNMENT;
   if (hipMemsetAsync(amax, 0, sizeof(float), s) != hipSuccess) return PFN_ERR_LAUNCH;
   if (n <= 0) return PFN_OK;
   hipLaunchKernelGGL(absmax_kernel, dim3(grid_for(n / 4 + 1, 256 * 8, 1024)), dim3(256), 0, s, x, n, reinterpret_cast<unsigned*>(amax),
@@ -253,9 +260,11 @@ constexpr int EMB_TOK = 16;
 template <typename T> __global__ __launch_bounds__(256) void embed_fwd_kernel(EmbedArgs a) {
   operand_store_mode<T>();
   extern __shared__ float xs[];  // [EMB_TOK][nf + 1]  (last column: y or 0, plus flag in sign-free form)
+  __shared__ int xexp[128];      // the power of two of every xaug_t column (xaug_col_exp)
   const long ntok = (long)a.B * a.S;
   const long t0 = (long)blockIdx.x * EMB_TOK;
   const int nfp = a.nf + 2;
+  if (a.xaug_t && threadIdx.x < a.xaug_ld) xexp[threadIdx.x] = xaug_col_exp(a.xaug_amax, threadIdx.x);
   for (int i = threadIdx.x; i < EMB_TOK * nfp; i += 256) {
     const int tk = i / nfp, f = i % nfp;
     const long tok = t0 + tk;
@@ -276,7 +285,7 @@ template <typename T> __global__ __launch_bounds__(256) void embed_fwd_kernel(Em
     const int aug = a.xaug_ld;
     for (int i = threadIdx.x; i < EMB_TOK * aug; i += 256) {
       const int tk = i / aug, f = i % aug;
-      if (t0 + tk < ntok) xa[(t0 + tk) * aug + f] = (T)(f < nfp ? xs[tk * nfp + f] : 0.f);
+      if (t0 + tk < ntok) xa[(t0 + tk) * aug + f] = (T)(f < nfp ? ldexpf(xs[tk * nfp + f], -xexp[f]) : 0.f);
     }
   }
   for (int e = threadIdx.x; e < a.E; e += 256) {
@@ -302,7 +311,36 @@ template <typename T> __global__ __launch_bounds__(256) void embed_fwd_kernel(Em
     }
   }
 }
+__global__ __launch_bounds__(256) void embed_colmax_kernel(EmbedArgs a, unsigned* amax_bits) {
+  __shared__ unsigned cm[128];
+  if (threadIdx.x < 128) cm[threadIdx.x] = 0u;
+  __syncthreads();
+  const long ntok = (long)a.B * a.S;
+  const int nfy = a.nf + 1;      // the features and the masked y (the train flag is 0 / 1)
+  // (a stride that is a multiple of nfy: every thread stays on one column, keeps its maximum in a register and adds one LDS atomic)
+  const long i0 = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256 / nfy * nfy;
+  if (i0 < stride) {
+    const int f = (int)(i0 % nfy);
+    float m = 0.f;
+    for (long i = i0; i < ntok * nfy; i += stride) {
+      const long tok = i / nfy, b = tok / a.S, sidx = tok % a.S;
+      const int sep = a.sep_of ? a.sep_of[b] : a.sep;
+      m = fmaxf(m, fabsf(f < a.nf ? a.x[sidx * a.x_st + b * a.x_sb + f] : ((sidx < sep) ? a.y[sidx * a.y_st + b * a.y_sb] : 0.f)));
+    }
+    if (m > 0.f) atomicMax(cm + f, __builtin_bit_cast(unsigned, m));      // (non-negative floats order like their bit patterns)
+  }
+  __syncthreads();
+  if (threadIdx.x < nfy && cm[threadIdx.x]) atomicMax(amax_bits + threadIdx.x, cm[threadIdx.x]);
+}
+int launch_embed_colmax(const EmbedArgs& a, float* amax, hipStream_t s) {
+  if (a.xaug_ld <= 0 || a.xaug_ld > 128 || a.nf + 2 > a.xaug_ld) return PFN_ERR_UNSUPPORTED;
+  if (hipMemsetAsync(amax, 0, sizeof(float) * a.xaug_ld, s) != hipSuccess) return PFN_ERR_LAUNCH;
+  const long n = (long)a.B * a.S * (a.nf + 1);
+  hipLaunchKernelGGL(embed_colmax_kernel, dim3(grid_for(n, 256 * 16, 1024)), dim3(256), 0, s, a, reinterpret_cast<unsigned*>(amax));
+  return PFN_LAUNCH_OK();
+}
 int launch_embed_fwd(const EmbedArgs& a, int precision, hipStream_t s) {
+  if (a.nf < 1 || a.nf > EMB_MAX_FEATURES) return PFN_ERR_UNSUPPORTED;
   const long ntok = (long)a.B * a.S;
   const int grid = (int)((ntok + EMB_TOK - 1) / EMB_TOK);
   const size_t lds = EMB_TOK * (a.nf + 2) * sizeof(float);
@@ -380,60 +418,69 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbedBwdArgs a) {
     else if (f == NF8) unsafeAtomicAdd(a.dbx + ee, t);
   }
 }
-// wide encoders (nf + 2 > 32): features in chunks of 8, d(src) re-read per chunk
+// wide encoders (nf + 2 > 32): workgroup = 256 embedding columns x one group of 8 of the nf + 2 augmented inputs x one slice of the tokens; thread = column.
+// The slice's 8 inputs pass through LDS in tiles of 256 tokens (8 KB whatever nf is), d(src) is read once per group of 8.  single_block: one slice, every
+// token in order -- each gradient element then has one writer (PFN_SCHED_DETERMINISTIC)
+constexpr int EMBW_TOK = 256;
 __global__ __launch_bounds__(256) void embed_bwd_wide_kernel(EmbedBwdArgs a) {
-  extern __shared__ float xs[];
+  __shared__ float xs[EMBW_TOK * 8];
   const long ntok = (long)a.B * a.S;
-  const long t0 = (long)blockIdx.x * 128;
-  const int nf8 = (a.nf + 2 + 7) / 8 * 8;
-  for (int i = threadIdx.x; i < 128 * nf8; i += 256) {
-    const int tk = i / nf8, f = i % nf8;
-    const long tok = t0 + tk;
-    float v = 0.f;
-    if (tok < ntok) {
-      const long b = tok / a.S, sidx = tok % a.S;
-      const int sep = a.sep_of ? a.sep_of[b] : a.sep;
-      if (f < a.nf) v = a.x[sidx * a.x_st + b * a.x_sb + f];
-      else if (f == a.nf) v = (sidx < sep) ? a.y[sidx * a.y_st + b * a.y_sb] : 0.f;
-      else if (f == a.nf + 1) v = (sidx < sep) ? 1.f : 0.f;
+  const int f0 = blockIdx.y * 8;
+  const int e = blockIdx.z * 256 + threadIdx.x;
+  const long per = (ntok + gridDim.x - 1) / gridDim.x;
+  const long tbeg = (long)blockIdx.x * per, tend = std::min(ntok, tbeg + per);
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float db = 0.f;
+  for (long t0 = tbeg; t0 < tend; t0 += EMBW_TOK) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < EMBW_TOK * 8; i += 256) {
+      const int tk = i >> 3, f = f0 + (i & 7);
+      const long tok = t0 + tk;
+      float v = 0.f;
+      if (tok < tend) {
+        const long b = tok / a.S, sidx = tok % a.S;
+        const int sep = a.sep_of ? a.sep_of[b] : a.sep;
+        if (f < a.nf) v = a.x[sidx * a.x_st + b * a.x_sb + f];
+        else if (f == a.nf) v = (sidx < sep) ? a.y[sidx * a.y_st + b * a.y_sb] : 0.f;
+        else if (f == a.nf + 1) v = (sidx < sep) ? 1.f : 0.f;
+      }
+      xs[i] = v;
     }
-    xs[i] = v;
+    __syncthreads();
+    if (e >= a.E) continue;
+    const int ntk = (int)std::min<long>(EMBW_TOK, tend - t0);
+    for (int tk = 0; tk < ntk; ++tk) {
+      const float d = a.dsrc[(t0 + tk) * a.E + e];
+      db += d;
+      const f32x4 x0 = *reinterpret_cast<const f32x4*>(xs + tk * 8), x1 = *reinterpret_cast<const f32x4*>(xs + tk * 8 + 4);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) { acc[q] += d * x0[q]; acc[4 + q] += d * x1[q]; }
+    }
   }
-  __syncthreads();
-  const int ntk = (int)std::min<long>(128, ntok - t0);
+  if (e >= a.E) return;
   const float osc = loss_scale_down(a.scale_amax);
-  for (int e = threadIdx.x; e < a.E; e += 256) {
-    float db = 0.f;
-    for (int f0 = 0; f0 < nf8; f0 += 8) {
-      float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int tk = 0; tk < ntk; ++tk) {
-        const float d = a.dsrc[(t0 + tk) * a.E + e];
-        if (f0 == 0) db += d;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += d * xs[tk * nf8 + f0 + j];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int f = f0 + j;
-        if (f < a.nf) unsafeAtomicAdd(a.dwx + (long)e * a.nf + f, acc[j] * osc);
-        else if (f == a.nf) unsafeAtomicAdd(a.dwy + e, acc[j] * osc);
-        else if (f == a.nf + 1) unsafeAtomicAdd(a.dby + e, acc[j] * osc);
-      }
-    }
-    unsafeAtomicAdd(a.dbx + e, db * osc);
+  for (int j = 0; j < 8; ++j) {
+    const int f = f0 + j;
+    if (f < a.nf) unsafeAtomicAdd(a.dwx + (long)e * a.nf + f, acc[j] * osc);
+    else if (f == a.nf) unsafeAtomicAdd(a.dwy + e, acc[j] * osc);
+    else if (f == a.nf + 1) unsafeAtomicAdd(a.dby + e, acc[j] * osc);
   }
+  if (blockIdx.y == 0) unsafeAtomicAdd(a.dbx + e, db * osc);
 }
-__global__ __launch_bounds__(256) void embed_grad_scatter_kernel(const float* acc, float* dwx, float* dwy, float* dby, int E, int nf) {
+__global__ __launch_bounds__(256) void embed_grad_scatter_kernel(const float* acc, float* dwx, float* dwy, float* dby, int E, int nf, const float* xaug_amax) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= E * (nf + 2)) return;
   const int e = i / (nf + 2), f = i % (nf + 2);
-  const float v = acc[e * emb_aug_width(nf) + f];      // (already unscaled: the GEMM that filled acc took the loss scale out)
+  // (the GEMM that filled acc took the loss scale out; the column's own power of two comes out here -- exact, as it went in)
+  const float v = ldexpf(acc[e * emb_aug_width(nf) + f], xaug_col_exp(xaug_amax, f));
   if (f < nf) unsafeAtomicAdd(dwx + (long)e * nf + f, v);
   else if (f == nf) unsafeAtomicAdd(dwy + e, v);
   else unsafeAtomicAdd(dby + e, v);
 }
-int launch_embed_grad_scatter(const float* acc, float* dwx, float* dwy, float* dby, int E, int nf, hipStream_t s) {
-  hipLaunchKernelGGL(embed_grad_scatter_kernel, dim3((E * (nf + 2) + 255) / 256), dim3(256), 0, s, acc, dwx, dwy, dby, E, nf);
+int launch_embed_grad_scatter(const float* acc, float* dwx, float* dwy, float* dby, int E, int nf, const float* xaug_amax, hipStream_t s) {
+  if (emb_aug_width(nf) == 0) return PFN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(embed_grad_scatter_kernel, dim3((E * (nf + 2) + 255) / 256), dim3(256), 0, s, acc, dwx, dwy, dby, E, nf, xaug_amax);
   return PFN_LAUNCH_OK();
 }
 int launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s) {
@@ -455,11 +502,10 @@ int launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s) {
     }
     return PFN_LAUNCH_OK();
   }
-  if (a.single_block) return PFN_ERR_UNSUPPORTED;      // the wide-encoder kernel splits the tokens over workgroups (atomics): no deterministic form
-  const int grid = (int)((ntok + 127) / 128);
-  const size_t lds = 128 * (size_t)nf8 * sizeof(float);
-  if (lds > 64 * 1024) return PFN_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(embed_bwd_wide_kernel, dim3(grid), dim3(256), lds, s, a);
+  if (a.nf > EMB_MAX_FEATURES) return PFN_ERR_UNSUPPORTED;
+  const int groups = nf8 / 8, ez = (a.E + 255) / 256;
+  const long splits = a.single_block ? 1 : std::max<long>(1, std::min<long>((ntok + EMBW_TOK - 1) / EMBW_TOK, 1024 / (groups * ez)));
+  hipLaunchKernelGGL(embed_bwd_wide_kernel, dim3((unsigned)splits, groups, ez), dim3(256), 0, s, a);
   return PFN_LAUNCH_OK();
 }
 
@@ -479,7 +525,7 @@ template <typename T> __global__ __launch_bounds__(256) void sbe_to_bse_kernel(c
   }
 }
 int launch_sbe_to_bse(const float* src, float* o32, void* ot, int S, int B, int E, int precision, hipStream_t s) {
-  if (E % 4) return PFN_ERR_ALIGNMENT;
+  if (E % 4 || (reinterpret_cast<uintptr_t>(src) & 15)) return PFN_ERR_ALIGNMENT;      // (16-byte loads of src)
   const long n4 = (long)S * B * E / 4;
   PFN_DISPATCH_OP(precision, hipLaunchKernelGGL(sbe_to_bse_kernel<T>, dim3(grid_for(n4, 256)), dim3(256), 0, s, src, o32, (T*)ot, S, B, E));
   return PFN_LAUNCH_OK();
@@ -495,7 +541,7 @@ __global__ __launch_bounds__(256) void bse_to_sbe_kernel(const float* src, float
   }
 }
 int launch_bse_to_sbe(const float* src, float* dst, int S, int B, int E, hipStream_t s, const float* scale_amax) {
-  if (E % 4) return PFN_ERR_ALIGNMENT;
+  if (E % 4 || (reinterpret_cast<uintptr_t>(dst) & 15)) return PFN_ERR_ALIGNMENT;
   const long n4 = (long)S * B * E / 4;
   hipLaunchKernelGGL(bse_to_sbe_kernel, dim3(grid_for(n4, 256)), dim3(256), 0, s, src, dst, S, B, E, scale_amax);
   return PFN_LAUNCH_OK();

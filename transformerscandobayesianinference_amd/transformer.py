@@ -65,6 +65,8 @@ class _StackFunction(torch.autograd.Function):
         desc, shadow = model._operands(stream, inference)
         if src is not None:
             src = src.contiguous().float()
+            if src.data_ptr() % 16:      # (a contiguous view keeps its storage offset; the kernel loads src 16 bytes at a time)
+                src = src.clone()
             S, B = src.shape[0], src.shape[1]
             xs = ys = None
             x_ptr = y_ptr = 0
@@ -196,6 +198,8 @@ class TransformerModel(nn.Module):
         self._custom_decoder = decoder is not None
         self.decoder = decoder(ninp, nhid, n_out) if decoder is not None else nn.Sequential(nn.Linear(ninp, nhid), nn.GELU(), nn.Linear(nhid, n_out))
         self.input_ln = SeqBN(ninp) if input_normalization else None
+        if self._fused_embedding() and encoder.in_features > _hip.MAX_FEATURES:
+            raise ValueError(f'{encoder.in_features} features: the fused embedding takes at most {_hip.MAX_FEATURES} (include/pfn_hip.h num_features)')
         # `precision`: operand type of the TRAINING path ('fp16', the default and the benchmarked mode since round 6: fp16 MFMA operands under a device-side loss
         # scale, saturating stores, keys centred, pre-LayerNorm sums in fp16; 'bf16' = rounds 1-5's path, same rate; 'f32' = exact-f32 parity mode).
         # `eval_precision`: operand type of INFERENCE passes -- model.eval() under torch.no_grad(), i.e. everything that produces

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PFN_ABI_VERSION 8
+#define PFN_ABI_VERSION 9
 
 enum {
   PFN_OK = 0,
@@ -126,6 +126,8 @@ enum { PFN_TUNE_GEMM_NT_KERNEL = 0,
        PFN_TUNE_RESIDUAL16 = 16,        /* 0: new descriptors carry PFN_SCHED_F32_RESIDUAL; 1 (default): they do not */
        PFN_TUNE_FUSE_Q_PROJECTION = 12, /* 1: new descriptors carry PFN_SCHED_FUSE_Q_PROJECTION (default 0) */
        PFN_TUNE_KEY_CENTERING = 13,     /* 1: new descriptors carry PFN_SCHED_KEY_CENTERING, 0: PFN_SCHED_NO_KEY_CENTERING, -1 (default): neither (centred with fp16, not with bf16) */
+       PFN_TUNE_ATTN_CACHE_SPLITS = 17, /* > 0: at most that many key-range splits in the attention of pfn_stack_predict (1 = one pass over the keys, no merge); 0 (default): the
+                                         * grid-size rule (csrc/attention.hip attn_cache_splits).  tools/bench_predict.py prices the split with it */
        PFN_TUNE_TOP_LAYER_TEST_ROWS = 6 /* 1 (default): the top encoder layer runs everything behind its K / V projection on the test rows only -- the reference
                                     * returns output[single_eval_pos:] (transformer.py:91), so that layer's train rows feed nothing; 0: every layer on every row */ };
 int pfn_set_tuning(int key, int value);
@@ -234,6 +236,37 @@ int pfn_stack_backward_ragged(const pfn_model_desc* d, const float* params, cons
                               const float* dlogits, float* grads, void* stream,
                               int first_group_layers, pfn_host_callback on_first_group, void* user,
                               int use_dropout, uint64_t dropout_seed);
+
+/* ---- CONDITION ONCE, PREDICT MANY (ABI 9).  What a user does with a trained PFN: hold one training set fixed and ask for the posterior predictive at many test
+ * points (reference presentation/heatmap_bardistribution.py, tabular.py, mcmc_svi_transformer_on_bayesian.py eval_transformer, BarDistribution.ei).  Under the mask
+ * of generate_D_q_matrix (transformer.py:34-41) a train row attends to keys [0, sep) only and a test row to those plus itself, so the train rows' keys and values in
+ * every layer do not depend on any test row, and test rows do not depend on each other.  pfn_stack_condition runs the train rows once and keeps every layer's
+ * K | V in a CONTEXT buffer; pfn_stack_predict then runs any number of test rows against it, in as many calls and chunks as the caller likes:
+ *   pfn_stack_predict(context of (x_train, y_train), x_test)  ==  pfn_stack_forward(cat(x_train, x_test), cat(y_train, anything), sep)  row for row
+ * up to rounding order (no dropout: the inference pass).  Fused embedding only (x / y given; positional encodings and SeqBN tie a row's value to the sequence).
+ *   x, y (condition): [sep, B, F] / [sep, B] f32 with element strides (x_st, x_sb, 1) / (y_st, y_sb); sep >= 0.  x (predict): [n, B, F] with strides (x_st, x_sb, 1).
+ *   CONTEXT: pfn_context_bytes(d, B, sep) bytes, per layer [B, sep, 2E] K | V rows in operand precision (K centred when the descriptor centres keys,
+ *     PFN_SCHED_NO_KEY_CENTERING) followed, when it does, by the [B, E] f32 key shift of that layer; every block 256-byte aligned.  sep = 0: 0 bytes, context may
+ *     be NULL (each test row attends only to itself).  The context belongs to the descriptor, the parameters and the B, F, sep it was made with: a caller
+ *     that changes any of them conditions again.
+ *   workspace (condition): pfn_workspace_bytes(d, B, sep) -- the train rows' forward; free again when the call has run.
+ *   workspace (predict): pfn_predict_workspace_bytes(d, B, n): the test rows of one layer at a time -- independent of nlayers and sep.
+ *   logits (predict): [n * B, n_out] f32, row t * B + b (the forward's (t - sep) * B + b with t counted from the first test row); n_out == 0 (custom decoder):
+ *     [n * B, emsize] f32, the encoder's test rows.
+ * Wrong sizes, a NULL context with sep > 0, or a context smaller than pfn_context_bytes return PFN_ERR_ARGUMENT before anything is launched. */
+int64_t pfn_context_bytes(const pfn_model_desc* d, int B, int sep);
+int pfn_stack_condition(const pfn_model_desc* d, const float* params, const void* shadow,
+                        const float* x, int64_t x_st, int64_t x_sb,
+                        const float* y, int64_t y_st, int64_t y_sb,
+                        int B, int sep,
+                        void* workspace, int64_t workspace_bytes,
+                        void* context, int64_t context_bytes, void* stream);
+int64_t pfn_predict_workspace_bytes(const pfn_model_desc* d, int B, int n);
+int pfn_stack_predict(const pfn_model_desc* d, const float* params, const void* shadow,
+                      const void* context, int64_t context_bytes, int sep,
+                      const float* x, int64_t x_st, int64_t x_sb,
+                      int B, int n,
+                      void* workspace, int64_t workspace_bytes, float* logits, void* stream);
 
 /* ---- bar distribution: replaces BarDistribution / FullSupportBarDistribution.forward and .mean
  * (bar_distribution.py:19-38, 83-117).  logits [R, nbars] f32 (row stride ld), y [R], borders

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libpfn_hip.so')
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 MAX_FEATURES = 1022      # pfn_model_desc.num_features (include/pfn_hip.h): wider encoders are refused when the model is built
 PREC_BF16 = 0
@@ -70,6 +70,12 @@ SIGNATURES = {
     'pfn_stack_forward_ragged': (_I, [_D, _P, _P, _P, _L, _L, _P, _L, _L, _I, _I, _P, _P, _I, _I, _L, _P, _L, _P, _P, _I, _U64]),
     # (..., ws, ws_bytes, dlogits, grads, stream, first_group_layers, callback, user, use_dropout, seed)
     'pfn_stack_backward_ragged': (_I, [_D, _P, _P, _P, _L, _L, _P, _L, _L, _I, _I, _P, _P, _I, _I, _L, _P, _L, _P, _P, _P, _I, _P, _P, _I, _U64]),
+    'pfn_context_bytes': (_L, [_D, _I, _I]),
+    # (d, params, shadow, x, x_st, x_sb, y, y_st, y_sb, B, sep, ws, ws_bytes, context, context_bytes, stream)
+    'pfn_stack_condition': (_I, [_D, _P, _P, _P, _L, _L, _P, _L, _L, _I, _I, _P, _L, _P, _L, _P]),
+    'pfn_predict_workspace_bytes': (_L, [_D, _I, _I]),
+    # (d, params, shadow, context, context_bytes, sep, x, x_st, x_sb, B, n, ws, ws_bytes, logits, stream)
+    'pfn_stack_predict': (_I, [_D, _P, _P, _P, _L, _I, _P, _L, _L, _I, _I, _P, _L, _P, _P]),
     'pfn_bar_nll_forward': (_I, [_P, _L, _P, _P, _L, _I, _I, _P, _P, _P, _P]),
     'pfn_bar_nll_backward': (_I, [_P, _L, _P, _P, _P, _L, _I, _P, _P]),
     'pfn_bar_mean': (_I, [_P, _L, _P, _L, _I, _I, _P, _P]),

@@ -219,8 +219,12 @@ template <typename T> PFN_DEV Frag<T> acc_to_frag_m1(const f32x16& acc, int c, c
 // of W_q[h], B = the wave's 32 x rows), so a lane ends up with its own query's 128 values, 16 per accumulator tile in accumulator order; acc_to_frag_m1 turns them
 // into the very fragments the K.Q^T product wants.  W_q[h] ([D, E], 128 KB at emsize 512) goes through the K / V tile buffers (not yet in use) in chunks of 128
 // columns, double-buffered; the x rows come straight from global memory, 16 bytes per lane and k-step (whole 1-KiB rows over the prologue).
-template <typename T, int D, bool DROP = false, int DV = D, bool FUSEQ = false>
+// CACHE (AttnArgs::kv; launch_attn_fwd_cache): the queries are S = n test rows whose keys [0, sep) were cached by pfn_stack_condition.  The key tiles stream from the
+// context instead of qkv, every query is a test row (its own key / value from qkv is the initial state), and with gridDim.z > 1 the workgroup streams only its split
+// of the keys -- the self key in split 0 -- and leaves unnormalised (o, m, l) for attn_merge_kernel.
+template <typename T, int D, bool DROP = false, int DV = D, bool FUSEQ = false, bool CACHE = false>
 __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs a) {
+  static_assert(!CACHE || (!DROP && !FUSEQ), "predict against a cache: no dropout, Q from qkv");
   operand_store_mode<T>();
   using C = AttnCfg<T, D>;
   using CV = AttnCfg<T, DV>;      // the V / O side: CV::NDB column blocks, CV::CIMG bytes per tile image
@@ -253,7 +257,12 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
   const int qi = wg.blk * C::QBLK + wave * 32 + li;
   const bool qvalid = qi < a.S;
   const int qc = min(qi, a.S - 1);
-  const int sep = a.sep_of ? a.sep_of[b] : a.sep;      // (wave-uniform: b comes from the block index)
+  // keys streamed by this workgroup: [0, sep) of qkv, or (CACHE) `sep` keys of the context from k_lo on
+  const int k_lo = CACHE ? (int)blockIdx.z * a.split_keys : 0;
+  const int sep = CACHE ? min(a.sep - k_lo, a.split_keys) : a.sep_of ? a.sep_of[b] : a.sep;      // (wave-uniform: b comes from the block index)
+  const long kld = CACHE ? a.kv_ld : rs;
+  const T* Ksrc = CACHE ? reinterpret_cast<const T*>(a.kv) + b * a.kv_sb + k_lo * kld + hd * D : Kp;
+  const T* Vsrc = CACHE ? Ksrc + a.E + vcol0 : Vp;
   if (a.q_from_sep && (wg.blk + 1) * C::QBLK <= sep / 256 * 256) return;      // ragged batch, top layer: this dataset's queries start above the block (ahead of every barrier)
   const float scale_log2 = rsqrtf((float)D) * LOG2E;
   // DROP: dropout on the probabilities (pfn_device.h dropout_keep with i = query, j = key).  The normaliser (row sum, lse) is that of
@@ -314,8 +323,8 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
 
   // initial state: the self key for test rows, empty for train rows.  The self K / V rows are only fetched by waves
   // that hold a test row at all (wave-uniform branch): 7 of 8 waves at the north star skip 24 loads per lane.
-  const bool is_test = qc >= sep;
-  const bool wave_has_test = !(ABL & 8) && wg.blk * C::QBLK + wave * 32 + 31 >= sep;   // ABL 8: profiling without the self-key work
+  const bool is_test = CACHE || qc >= sep;
+  const bool wave_has_test = CACHE ? blockIdx.z == 0 : !(ABL & 8) && wg.blk * C::QBLK + wave * 32 + 31 >= sep;   // ABL 8: profiling without the self-key work
   float m = -1e30f, lsum = 0.f;
   f32x16 o[CV::NDB];
 #pragma unroll
@@ -344,13 +353,13 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
   TileStage<T, C::KVB, C::RB, C::NT> sk;
   TileStage<T, C::KVB, CV::RB, C::NT> sv;
   if (ntiles > 0) {
-    sk.issue(Kp, rs, sep, D);
-    sv.issue(Vp, rs, sep, DV);
+    sk.issue(Ksrc, kld, sep, D);
+    sv.issue(Vsrc, kld, sep, DV);
     sk.template commit_p<C::RS>(Kt(0));
     sv.template commit_p<CV::CS>(Vt(0));
     if (ntiles > 1) {   // tile 1 stays in flight across the barrier (see the loop)
-      sk.issue(Kp + (long)C::KVB * rs, rs, sep - C::KVB, D);
-      sv.issue(Vp + (long)C::KVB * rs, rs, sep - C::KVB, DV);
+      sk.issue(Ksrc + (long)C::KVB * kld, kld, sep - C::KVB, D);
+      sv.issue(Vsrc + (long)C::KVB * kld, kld, sep - C::KVB, DV);
     }
   }
   __syncthreads();
@@ -412,8 +421,8 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
     }
     if (!(ABL & 1) && t + 2 < ntiles) {
       const long k2 = k0 + 2 * C::KVB;
-      sk.issue(Kp + k2 * rs, rs, sep - (int)k2, D);
-      sv.issue(Vp + k2 * rs, rs, sep - (int)k2, DV);
+      sk.issue(Ksrc + k2 * kld, kld, sep - (int)k2, D);
+      sv.issue(Vsrc + k2 * kld, kld, sep - (int)k2, DV);
     }
     if (t == nfull) {   // ragged last tile: keys >= sep do not exist
 #pragma unroll
@@ -487,6 +496,21 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
   if (ntiles > 0) pv_prev(vb_prev);
 
   lsum += __shfl_xor(lsum, 32, 64);
+  if constexpr (CACHE) {
+    if (gridDim.z > 1) {      // one split of several: unnormalised output and (m, l) for attn_merge_kernel
+      const long prow = ((long)blockIdx.z * a.B + b) * a.S + qc;
+      float* out = a.part_o + prow * a.E + hd * D + vcol0;
+#pragma unroll
+      for (int db = 0; db < CV::NDB; ++db) {
+        float v[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[r] = o[db][r];
+        store_row_block<float>(out + db * 32, v, h, qvalid);
+      }
+      if (qvalid && h == 0 && vcol0 == 0) *reinterpret_cast<float2*>(a.part_ml + 2 * (prow * a.H + hd)) = make_float2(m, lsum);
+      return;
+    }
+  }
   const float inv = DROP ? 1.f / (lsum * (1.f - a.p_drop)) : 1.f / lsum;
   {
     T* out = reinterpret_cast<T*>(a.ctx) + ((long)b * a.S + qc) * a.E + hd * D + vcol0;
@@ -497,7 +521,34 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
       for (int r = 0; r < 16; ++r) v[r] = o[db][r] * inv;
       store_row_block<T>(out + db * 32, v, h, qvalid);
     }
-    if (qvalid && h == 0 && vcol0 == 0) a.lse[((long)b * a.H + hd) * a.S + qi] = (m + __builtin_amdgcn_logf(lsum)) * LN2;
+    if (!CACHE && qvalid && h == 0 && vcol0 == 0) a.lse[((long)b * a.H + hd) * a.S + qi] = (m + __builtin_amdgcn_logf(lsum)) * LN2;
+  }
+}
+
+// The splits of a predict pass (attn_fwd_kernel CACHE, gridDim.z > 1) merged: ctx = sum_z 2^(m_z - M) o_z / sum_z 2^(m_z - M) l_z with M = max_z m_z.
+// One thread per (test row, 4 columns); the split count is small (attn_cache_splits), the pass reads nsplit x B n E floats once.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_merge_kernel(AttnArgs a, int nsplit, int D) {
+  const long rows = (long)a.B * a.S, c4n = a.E / 4, total = rows * c4n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long row = i / c4n;
+    const int c = (int)(i - row * c4n) * 4, hd = c / D;
+    float mx = -INFINITY;
+    for (int z = 0; z < nsplit; ++z) mx = fmaxf(mx, a.part_ml[2 * ((z * rows + row) * a.H + hd)]);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float l = 0.f;
+    for (int z = 0; z < nsplit; ++z) {
+      const float2 ml = *reinterpret_cast<const float2*>(a.part_ml + 2 * ((z * rows + row) * a.H + hd));
+      const float w = fast_exp2(ml.x - mx);
+      l += w * ml.y;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(a.part_o + (z * rows + row) * a.E + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] += w * v[e];
+    }
+    const float inv = 1.f / l;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] *= inv;
+    store4<T>(reinterpret_cast<T*>(a.ctx) + row * a.E + c, acc);
   }
 }
 
@@ -762,7 +813,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
     dma(1, t0 + 1);
     stage_stats(1, (t0 + 1) * QB);
   }
-  constexpr int DS_STORES = DO_DK && !(KVABL & 1) ? (sizeof(T) == 2 ? 2 : 4) : 0;   // store instructions of one tile's dS^T per wave
+  constexpr int DST_TILE_WRITES = DO_DK && !(KVABL & 1) ? (sizeof(T) == 2 ? 2 : 4) : 0;   // store instructions of one tile's dS^T per wave
   bool stored = false;                // this wave's dS^T stores of the previous tile may still be in flight
 
   auto tile = [&](auto buf_c, int t) {
@@ -789,7 +840,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
     // with this wave's LDS reads done and its pieces of tile t+1 landed (vmcnt = the dS^T stores issued behind them: loads and stores retire in order)
     auto sync_tile = [&]() __attribute__((always_inline)) {
       if (ABL & 4) dma_wait_all();
-      else if (stored) wait_vm_barrier<DS_STORES>();
+      else if (stored) wait_vm_barrier<DST_TILE_WRITES>();
       else wait_vm_barrier<0>();
     };
     if (wave_live) {
@@ -928,7 +979,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
       stage_stats(NXT, (t + 2) * QB);
     }
     // keys >= sep of a block row the dQ pass reads (rows < ds_rows) leave as zeros: that pass does not mask rows
-    if constexpr (DS_STORES > 0) {
+    if constexpr (DST_TILE_WRITES > 0) {
       if (!wave_all_valid) {      // last key block only (wave-uniform)
         if (!kvalid) {
 #pragma unroll
@@ -1505,6 +1556,30 @@ template <typename T, int D, bool DROP> static int launch_fwd_k(const AttnArgs& 
 template <typename T, int D> static int launch_fwd_t(const AttnArgs& a, hipStream_t s) {
   return a.p_drop > 0.f ? launch_fwd_k<T, D, true>(a, s) : launch_fwd_k<T, D, false>(a, s);     // dropout: the variants with the mask arithmetic
 }
+static int g_attn_cache_split_cap = 0;      // PFN_TUNE_ATTN_CACHE_SPLITS
+void set_attn_cache_split_cap(int splits) { g_attn_cache_split_cap = std::max(splits, 0); }
+// predict against a K / V cache: the forward kernel's CACHE instantiation over gridDim.z = attn_cache_splits key ranges, merged by attn_merge_kernel when there are several
+template <typename T, int D> static int launch_fwd_cache_t(const AttnArgs& a_in, hipStream_t s) {
+  using C = AttnCfg<T, D>;
+  constexpr int DV = (sizeof(T) == 4 && D == 256) ? 128 : D;
+  constexpr size_t lds = 2 * C::RIMG + 4 * AttnCfg<T, DV>::CIMG;
+  AttnArgs a = a_in;
+  int nsplit = attn_cache_splits(a.B, a.S, a.E, a.H, a.sep, sizeof(T) == 4 ? PFN_PREC_F32 : PFN_PREC_BF16);
+  if (g_attn_cache_split_cap > 0) nsplit = std::min(nsplit, g_attn_cache_split_cap);
+  const int ntiles = (a.sep + C::KVB - 1) / C::KVB;
+  a.split_keys = nsplit > 1 ? (ntiles + nsplit - 1) / nsplit * C::KVB : std::max(a.sep, 1);
+  const int nz = nsplit > 1 ? (a.sep + a.split_keys - 1) / a.split_keys : 1;      // (whole tiles per split: the last ones may merge)
+  if (nz > 1 && (!a.part_o || !a.part_ml)) return PFN_ERR_ARGUMENT;
+  static LdsAllowance allowance;
+  allowance.ensure(attn_fwd_kernel<T, D, false, DV, false, true>, lds);
+  const dim3 grid(((a.S + C::QBLK - 1) / C::QBLK) * a.H * a.B, D / DV, nz);
+  hipLaunchKernelGGL((attn_fwd_kernel<T, D, false, DV, false, true>), grid, dim3(C::NT), lds, s, a);
+  if (nz > 1) {
+    const long work = (long)a.B * a.S * (a.E / 4);
+    hipLaunchKernelGGL(attn_merge_kernel<T>, dim3((unsigned)std::min<long>((work + 255) / 256, 4096)), dim3(256), 0, s, a, nz, D);
+  }
+  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+}
 template <typename T, int D, bool DROP> static int launch_bwd_k(const AttnArgs& a, hipStream_t s) {
   using C = AttnCfg<T, D>;
   const int parts = a.parts ? a.parts : ~0;
@@ -1659,6 +1734,28 @@ int launch_attn_fwd(const AttnArgs& a_in, int precision, hipStream_t s) {
   a.pingpong = g_attn_pingpong;
   a.q_begin = a.q_begin / 256 * 256;
   PFN_ATTN_DISPATCH(launch_fwd_t, return (launch_fwd_t<float, 256>(a, s)))
+}
+// Key-range splits of a predict pass: when the query blocks x heads x datasets (x V slices) of one pass over the keys fill less than the chip's 256 CUs, the keys are
+// split into ranges of whole tiles until the grid holds about 512 workgroups (one to two rounds); one split means no merge.
+int attn_cache_splits(int B, int n, int E, int H, int sep, int precision) {
+  if (B < 1 || n < 1 || H < 1 || E % H) return 1;
+  const int D = E / H;
+  const bool w16 = prec_is16(precision);
+  const int qblk = (w16 && D <= 128) ? 256 : 128, kvb = (w16 && D <= 128) ? 64 : 32, slices = (!w16 && D == 256) ? 2 : 1;
+  const long wgs = (long)((n + qblk - 1) / qblk) * H * B * slices;
+  if (wgs >= 256) return 1;
+  const long want = 512 / wgs;
+  if (sep < 0) return (int)std::max<long>(1, want);
+  const long ntiles = (sep + kvb - 1) / kvb;
+  return (int)std::max<long>(1, std::min(want, ntiles));
+}
+int launch_attn_fwd_cache(const AttnArgs& a_in, int precision, hipStream_t s) {
+  if (a_in.B <= 0 || a_in.S <= 0 || a_in.H <= 0 || a_in.E % a_in.H || a_in.sep < 0 || (a_in.sep > 0 && !a_in.kv)) return PFN_ERR_ARGUMENT;
+  if ((a_in.E * prec_esize(precision)) % 16 || (a_in.kv_ld * prec_esize(precision)) % 16) return PFN_ERR_ALIGNMENT;
+  AttnArgs a = a_in;
+  a.pingpong = g_attn_pingpong;
+  a.q_begin = 0; a.sep_of = nullptr; a.q_from_sep = 0; a.p_drop = 0.f; a.xq = nullptr;
+  PFN_ATTN_DISPATCH(launch_fwd_cache_t, return (launch_fwd_cache_t<float, 256>(a, s)))
 }
 void attn_bwd_ds_dims(int S, int sep, int* rows, int* ld) {
   *rows = (sep + 63) / 64 * 64;       // whole key tiles of the dQ pass

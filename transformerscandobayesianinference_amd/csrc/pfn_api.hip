@@ -228,6 +228,45 @@ Ws carve(const pfn_model_desc& d, int B, int S, char* base) {
   return w;
 }
 
+// ---- K / V context of pfn_stack_condition / pfn_stack_predict --------------------------------------
+// Per layer: [B, sep, 2E] K | V rows of the train rows in operand precision (K centred when the keys are), then, when the keys are centred, the [B, E] f32 key
+// shift that centred them -- the test rows' own keys must leave the q|k|v projection shifted by the same vector.  sep = 0: nothing (each test row sees itself).
+struct Context { int64_t kv_bytes, shift_bytes, layer_bytes, bytes; };
+static bool context_centred(const pfn_model_desc& d) { return key_centering(d) && d.emsize % 64 == 0; }      // (the forward centres under the same two conditions)
+Context context_layout(const pfn_model_desc& d, int B, int sep) {
+  Context c;
+  c.kv_bytes = align_up((int64_t)B * sep * 2 * d.emsize * esize(d.precision), 256);
+  c.shift_bytes = context_centred(d) ? align_up((int64_t)B * d.emsize * 4, 256) : 0;
+  c.layer_bytes = sep > 0 ? c.kv_bytes + c.shift_bytes : 0;
+  c.bytes = c.layer_bytes * d.nlayers;
+  return c;
+}
+// where stack_forward_impl leaves every layer's K | V (and key shift) when it runs as the condition pass
+struct KvSink { char* base; Context c; };
+
+// Workspace of a predict pass: the test rows of ONE layer at a time (nothing is kept for a backward), in two sets that alternate -- set 2 holds a layer's input
+// (and then its output: linear2 + LN2 reads set 1 only), set 1 what LN1 leaves.  The attention's split partials follow (attn_cache_splits).
+struct PredictWs {
+  float *x2, *y2, *mean2, *rstd2; char* x2_t;
+  float *x1, *y1, *mean1, *rstd1; char* x1_t;
+  char *qkv, *ctx, *h, *hpre;
+  float *part_o, *part_ml;
+  int64_t bytes;
+};
+PredictWs carve_predict(const pfn_model_desc& d, int B, int n, char* base) {
+  PredictWs w;
+  const int64_t M = (int64_t)B * n, E = d.emsize, F = d.nhid, es = esize(d.precision);
+  const int64_t nsplit = attn_cache_splits(B, n, d.emsize, d.nhead, -1, d.precision);
+  int64_t cur = 0;
+  auto take = [&](int64_t nbytes) { char* p = base ? base + cur : nullptr; cur = align_up(cur + nbytes, 256); return p; };
+  w.x2 = (float*)take(M * E * 4); w.y2 = (float*)take(M * E * 4); w.mean2 = (float*)take(M * 4); w.rstd2 = (float*)take(M * 4); w.x2_t = take(M * E * es);
+  w.x1 = (float*)take(M * E * 4); w.y1 = (float*)take(M * E * 4); w.mean1 = (float*)take(M * 4); w.rstd1 = (float*)take(M * 4); w.x1_t = take(M * E * es);
+  w.qkv = take(M * 3 * E * es); w.ctx = take(M * E * es); w.h = take(M * F * es); w.hpre = take(M * F * es);
+  w.part_o = (float*)take(nsplit > 1 ? nsplit * M * E * 4 : 0); w.part_ml = (float*)take(nsplit > 1 ? nsplit * M * d.nhead * 8 : 0);
+  w.bytes = cur;
+  return w;
+}
+
 GemmNT nt(const void* A, long lda, const void* B, long ldb, int M, int N, int K, int flags) {
   GemmNT g;
   memset(&g, 0, sizeof(g));
@@ -303,6 +342,7 @@ int pfn_set_tuning(int key, int value) {
     case PFN_TUNE_GEMM_LN_ROWS: set_gemm_ln_rows64(value); return PFN_OK;
     case PFN_TUNE_GP_PLANES: g_gp_planes = value != 0; return PFN_OK;
     case PFN_TUNE_FUSE_DELTA: g_fuse_delta = value != 0; return PFN_OK;
+    case PFN_TUNE_ATTN_CACHE_SPLITS: set_attn_cache_split_cap(value); return PFN_OK;
     case PFN_TUNE_FUSE_LN_WIDE: g_default_schedule = value ? (g_default_schedule | PFN_SCHED_FUSE_LN_WIDE) : (g_default_schedule & ~PFN_SCHED_FUSE_LN_WIDE); return PFN_OK;
     case PFN_TUNE_TOP_LAYER_TEST_ROWS: g_default_schedule = value ? (g_default_schedule & ~PFN_SCHED_TOP_LAYER_ALL_ROWS) : (g_default_schedule | PFN_SCHED_TOP_LAYER_ALL_ROWS); return PFN_OK;
     default: return fail(PFN_ERR_ARGUMENT, "unknown tuning key %d", key);
@@ -376,7 +416,7 @@ int pfn_prepare_params(const pfn_model_desc* d, const float* params, void* shado
 static int stack_forward_impl(const pfn_model_desc* d, const float* params, const void* shadow,
                               const float* x, int64_t x_st, int64_t x_sb, const float* y, int64_t y_st, int64_t y_sb,
                               const float* src_sbe, int B, int S, int sep, void* workspace, int64_t workspace_bytes,
-                              float* logits, void* stream, bool use_dropout, uint64_t dropout_seed, const Ragged* rg = nullptr);
+                              float* logits, void* stream, bool use_dropout, uint64_t dropout_seed, const Ragged* rg = nullptr, const KvSink* sink = nullptr);
 int pfn_stack_forward(const pfn_model_desc* d, const float* params, const void* shadow,
                       const float* x, int64_t x_st, int64_t x_sb, const float* y, int64_t y_st, int64_t y_sb,
                       const float* src_sbe, int B, int S, int sep, void* workspace, int64_t workspace_bytes,
@@ -392,7 +432,7 @@ int pfn_stack_forward_dropout(const pfn_model_desc* d, const float* params, cons
 static int stack_forward_impl(const pfn_model_desc* d, const float* params, const void* shadow,
                               const float* x, int64_t x_st, int64_t x_sb, const float* y, int64_t y_st, int64_t y_sb,
                               const float* src_sbe, int B, int S, int sep, void* workspace, int64_t workspace_bytes,
-                              float* logits, void* stream, bool use_dropout, uint64_t dropout_seed, const Ragged* rg) {
+                              float* logits, void* stream, bool use_dropout, uint64_t dropout_seed, const Ragged* rg, const KvSink* sink) {
   PFN_TRY(check_desc(d));
   const float pdrop = use_dropout ? d->dropout : 0.f;     // > 0: TransformerEncoderLayer's four dropout sites are live (training)
   auto dseed = [&](int layer, int site) { return dropout_site_seed(dropout_seed, layer, site); };
@@ -471,6 +511,14 @@ static int stack_forward_impl(const pfn_model_desc* d, const float* params, cons
         g.flags |= EPI_ROWSHIFT; g.rowshift = w.kshift; g.rs_ld = E; g.rs_S = S; g.rs_n0 = fuse_q ? 0 : E; g.rs_n1 = g.rs_n0 + E;
       }
       PFN_TRY(launch_gemm_nt(g, prec, s));
+    }
+    if (sink) {      // the condition pass (pfn_stack_condition): this layer's K | V columns and key shift into the context; the top layer ends here
+      char* kv = sink->base + l * sink->c.layer_bytes;
+      if (hipMemcpy2DAsync(kv, 2 * E * es, a.qkv + (int64_t)E * es, 3 * E * es, 2 * E * es, (size_t)M, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fail(PFN_ERR_LAUNCH, "context copy of layer %d", l);
+      if (sink->c.shift_bytes && hipMemcpyAsync(kv + sink->c.kv_bytes, w.kshift, (size_t)B * E * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fail(PFN_ERR_LAUNCH, "key shift copy of layer %d", l);
+      if (l == d->nlayers - 1) break;
     }
     {
       AttnArgs at; memset(&at, 0, sizeof(at));
@@ -612,6 +660,133 @@ int pfn_stack_forward_ragged(const pfn_model_desc* d, const float* params, const
   Ragged rg = {sep_of, row_off, test_rows, sep_min};
   return stack_forward_impl(d, params, shadow, x, x_st, x_sb, y, y_st, y_sb, nullptr, B, S, sep_max, workspace, workspace_bytes, logits, stream, use_dropout != 0, dropout_seed, &rg);
 }
+// ---- condition once, predict many (ABI 9) ----------------------------------------------------------------------------------------------------------------------------
+int64_t pfn_context_bytes(const pfn_model_desc* d, int B, int sep) {
+  if (check_desc(d) != PFN_OK || B < 1 || sep < 0) return -1;
+  return context_layout(*d, B, sep).bytes;
+}
+// The train rows' forward (stack_forward_impl at S = sep: no test rows, no decoder) with every layer's K | V handed to the context as it is projected
+int pfn_stack_condition(const pfn_model_desc* d, const float* params, const void* shadow,
+                        const float* x, int64_t x_st, int64_t x_sb, const float* y, int64_t y_st, int64_t y_sb,
+                        int B, int sep, void* workspace, int64_t workspace_bytes, void* context, int64_t context_bytes, void* stream) {
+  PFN_TRY(check_desc(d));
+  if (B < 1 || sep < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d sep=%d", B, sep);
+  const KvSink sink = {(char*)context, context_layout(*d, B, sep)};
+  if (sep > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context");
+  if (context_bytes < sink.c.bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)sink.c.bytes);
+  if (sep == 0 || d->nlayers == 0) return PFN_OK;
+  if (!x || !y) return fail(PFN_ERR_ARGUMENT, "need x and y");
+  return stack_forward_impl(d, params, shadow, x, x_st, x_sb, y, y_st, y_sb, nullptr, B, sep, sep, workspace, workspace_bytes, nullptr, stream, false, 0, nullptr, &sink);
+}
+int64_t pfn_predict_workspace_bytes(const pfn_model_desc* d, int B, int n) {
+  if (check_desc(d) != PFN_OK || B < 1 || n < 0) return -1;
+  return carve_predict(*d, B, n, nullptr).bytes;
+}
+// The test rows alone, layer by layer, each against its layer's cached keys: the forward's schedule (same kernels, same fusion rules) on B n rows
+int pfn_stack_predict(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep,
+                      const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes, float* logits, void* stream) {
+  PFN_TRY(check_desc(d));
+  if (B < 1 || n < 0 || sep < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d n=%d sep=%d", B, n, sep);
+  const Context c = context_layout(*d, B, sep);
+  if (sep > 0 && d->nlayers > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context with sep=%d", sep);
+  if (context_bytes < c.bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)c.bytes);
+  if (!params || !shadow || !workspace || (n > 0 && (!x || !logits))) return fail(PFN_ERR_ARGUMENT, "null pointer");
+  PredictWs w = carve_predict(*d, B, n, (char*)workspace);
+  if (workspace_bytes < w.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)w.bytes);
+  if (n == 0) return PFN_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int prec = d->precision, es = esize(prec);
+  const int E = d->emsize, F = d->nhid, H = d->nhead, O = d->n_out, M = B * n;
+  Layout L = make_layout(*d);
+  const char* sh = (const char*)shadow;
+  auto W = [&](int64_t off) { return (const void*)(sh + off * es); };
+  {  // the x embedding only: test rows carry no y
+    EmbedArgs e; memset(&e, 0, sizeof(e));
+    e.x = x; e.x_st = x_st; e.x_sb = x_sb; e.y = x; e.y_st = 0; e.y_sb = 0;      // (y is not read below sep = 0)
+    e.wx = params + L.enc_w; e.bx = params + L.enc_b; e.wy = params + L.yenc_w; e.by = params + L.yenc_b;
+    e.out_f32 = w.x2; e.out_t = w.x2_t; e.S = n; e.B = B; e.nf = d->num_features; e.E = E; e.sep = 0;
+    PFN_TRY(launch_embed_fwd(e, prec, s));
+  }
+  // the forward's fusion rules (stack_forward_impl) for the same descriptor and these rows
+  Ws probe_ws; probe_ws.x0 = w.x2; probe_ws.x0_t = w.x2_t;
+  const bool ln_ok = ln_gemm_probe(*d, probe_ws, params, sh, M);
+  const bool fuse_ln = prec_is16(prec) && ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE));
+  const bool y16 = residual16(*d) && ln_ok;
+  const bool y16u = residual16_separate_ln(*d, ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE)));
+  struct Resid { const float* plain; const void* y; const float* mean; const float* rstd; const float* gamma; const float* beta; };
+  Resid res = {w.x2, nullptr, nullptr, nullptr, nullptr, nullptr};
+  auto set_resid = [](GemmLN& g, const Resid& r) { g.resid = r.plain; g.ry = r.y; g.rmean = r.mean; g.rrstd = r.rstd; g.rgamma = r.gamma; g.rbeta = r.beta; };
+  for (int l = 0; l < d->nlayers; ++l) {
+    const LayerP& p = L.layer[l];
+    const bool last = l == d->nlayers - 1;
+    const char* kv = (const char*)context + l * c.layer_bytes;
+    {  // packed q/k/v projection; the self keys shifted by the vector that centred the cached ones
+      GemmNT g = nt(w.x2_t, E, W(p.w_in), E, M, 3 * E, E, EPI_BIAS | EPI_OUT_T);
+      g.bias = params + p.b_in; g.out_t = w.qkv; g.ld_out_t = 3 * E;
+      if (c.shift_bytes && sep > 0) {
+        g.flags |= EPI_ROWSHIFT; g.rowshift = (const float*)(kv + c.kv_bytes); g.rs_ld = E; g.rs_S = n; g.rs_n0 = E; g.rs_n1 = 2 * E;
+      }
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+    }
+    {
+      AttnArgs at; memset(&at, 0, sizeof(at));
+      at.qkv = w.qkv; at.ctx = w.ctx; at.B = B; at.S = n; at.E = E; at.H = H; at.sep = sep;
+      at.kv = kv; at.kv_ld = 2L * E; at.kv_sb = (long)sep * 2 * E; at.part_o = w.part_o; at.part_ml = w.part_ml;
+      PFN_TRY(launch_attn_fwd_cache(at, prec, s));
+    }
+    if (fuse_ln) {  // x1 = LN1(x + out_proj(ctx))
+      GemmLN g; memset(&g, 0, sizeof(g));
+      g.A = w.ctx; g.lda = E; g.B = W(p.w_o); g.ldb = E; g.M = M; g.N = E; g.K = E; g.bias = params + p.b_o;
+      set_resid(g, res);
+      g.gamma = params + p.g1; g.beta = params + p.be1; g.eps = d->ln_eps;
+      g.y = w.y1; g.mean = w.mean1; g.rstd = w.rstd1; g.x_t = w.x1_t; g.y16 = y16;
+      PFN_TRY(launch_gemm_ln(g, prec, s));
+      res = Resid{nullptr, w.y1, w.mean1, w.rstd1, params + p.g1, params + p.be1};
+    } else {
+      GemmNT g = nt(w.ctx, E, W(p.w_o), E, M, E, E, EPI_BIAS | EPI_RESID | EPI_OUT_F32);
+      g.bias = params + p.b_o; g.resid = w.x2; g.ld_resid = E; g.out_f32 = w.y1; g.ld_out_f32 = E;
+      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = w.x2_t; g.ld_aux = E; g.out_t = w.y1; g.ld_out_t = E; }
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+      PFN_TRY(launch_layernorm_fwd(w.y1, params + p.g1, params + p.be1, y16u ? nullptr : w.x1, w.x1_t, w.mean1, w.rstd1, M, E, d->ln_eps, prec, s, y16u));
+    }
+    {  // linear1 + GELU
+      GemmNT g = nt(w.x1_t, E, W(p.w1), E, M, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
+      g.bias = params + p.b1; g.out_t = w.h; g.ld_out_t = F; g.out2_t = w.hpre; g.ld_out2 = F;
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+    }
+    if (fuse_ln) {  // x2 = LN2(x1 + linear2(h)), over the layer input (read by out_proj only)
+      GemmLN g; memset(&g, 0, sizeof(g));
+      g.A = w.h; g.lda = F; g.B = W(p.w2); g.ldb = F; g.M = M; g.N = E; g.K = F; g.bias = params + p.b2;
+      set_resid(g, res);
+      g.gamma = params + p.g2; g.beta = params + p.be2; g.eps = d->ln_eps;
+      g.y = w.y2; g.mean = w.mean2; g.rstd = w.rstd2; g.x_t = w.x2_t; g.y16 = y16;
+      g.x_f32 = last ? w.x2 : nullptr;
+      PFN_TRY(launch_gemm_ln(g, prec, s));
+      res = Resid{nullptr, w.y2, w.mean2, w.rstd2, params + p.g2, params + p.be2};
+    } else {
+      GemmNT g = nt(w.h, F, W(p.w2), F, M, E, F, EPI_BIAS | EPI_RESID | EPI_OUT_F32);
+      g.bias = params + p.b2; g.resid = w.x1; g.ld_resid = E; g.out_f32 = w.y2; g.ld_out_f32 = E;
+      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = w.x1_t; g.ld_aux = E; g.out_t = w.y2; g.ld_out_t = E; }
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+      PFN_TRY(launch_layernorm_fwd(w.y2, params + p.g2, params + p.be2, (y16u && !last) ? nullptr : w.x2, w.x2_t, w.mean2, w.rstd2, M, E, d->ln_eps, prec, s, y16u));
+    }
+  }
+  // [B, n] token order -> the caller's rows t B + b; then the decoder on them (set 1 and the q|k|v buffer are free now)
+  if (O == 0) return launch_gather_test_rows(w.x2, logits, n, B, E, 0, PFN_PREC_F32, s);
+  PFN_TRY(launch_gather_test_rows(w.x2, w.x1_t, n, B, E, 0, prec, s));
+  {
+    GemmNT g = nt(w.x1_t, E, W(L.dec0_w), E, M, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
+    g.bias = params + L.dec0_b; g.out_t = w.h; g.ld_out_t = F; g.out2_t = w.hpre; g.ld_out2 = F;
+    PFN_TRY(launch_gemm_nt(g, prec, s));
+  }
+  {
+    GemmNT g = nt(w.h, F, W(L.dec2_w), F, M, O, F, EPI_BIAS | EPI_OUT_F32);
+    g.bias = params + L.dec2_b; g.out_f32 = logits; g.ld_out_f32 = O;
+    PFN_TRY(launch_gemm_nt(g, prec, s));
+  }
+  return PFN_OK;
+}
+
 int pfn_stack_backward_ragged(const pfn_model_desc* d, const float* params, const void* shadow,
                               const float* x, int64_t x_st, int64_t x_sb, const float* y, int64_t y_st, int64_t y_sb,
                               int B, int S, const int32_t* sep_of, const int64_t* row_off, int sep_min, int sep_max, int64_t test_rows,

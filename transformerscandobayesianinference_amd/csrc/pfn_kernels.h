@@ -213,12 +213,23 @@ struct AttnArgs {
   // every workgroup reads its own dataset's position.  nullptr = every dataset at `sep`.
   const int* sep_of;
   int q_from_sep;      // ragged batch with the top layer on the test rows: dataset b skips the queries below sep_of[b] / 256 * 256 (q_begin then = the smallest of them: the grids)
-  // backward
-  const void* dctx; void* dqkv; float* delta;  // delta: [B,H,S] f32 scratch
-  void* ds;   // dS^T scratch [B, H, ds_rows, ds_ld] T: written by the key-block pass, read by the query-block pass (attn_bwd_ds_bytes)
-  int ds_rows, ds_ld;  // filled by the launcher
-  int parts;  // backward launches to run, bit mask over ATTN_BWD_*; 0 = all (profiling entry point pfn_op_attention_bwd_parts)
-  int zero_delta;  // the query-block pass (the last reader's successor) leaves delta[b, head, its queries] = 0: the next layer's GEMM epilogue ADDS into it (EPI_ROWDOT)
+  // The backward's fields and those of a predict pass share their bytes: no kernel reads both, and every other kernel's argument block keeps its layout.
+  union {
+    struct {      // backward
+      const void* dctx; void* dqkv; float* delta;  // delta: [B,H,S] f32 scratch
+      void* ds;   // dS^T scratch [B, H, ds_rows, ds_ld] T: written by the key-block pass, read by the query-block pass (attn_bwd_ds_bytes)
+      int ds_rows, ds_ld;  // filled by the launcher
+      int parts;  // backward launches to run, bit mask over ATTN_BWD_*; 0 = all (profiling entry point pfn_op_attention_bwd_parts)
+      int zero_delta;  // the query-block pass (the last reader's successor) leaves delta[b, head, its queries] = 0: the next layer's GEMM epilogue ADDS into it (EPI_ROWDOT)
+    };
+    struct {      // PREDICT AGAINST A K / V CACHE (launch_attn_fwd_cache; pfn_stack_predict): qkv holds the S = n test rows [B, n, 3E] -- the queries and their own (self)
+                  // keys and values -- and `sep` keys per dataset come from the context: K of key j at kv + b * kv_sb + j * kv_ld, its V E elements behind it
+      const void* kv; long kv_ld, kv_sb;
+      float* part_o;      // more than one split: [nsplit, B, n, E] f32 unnormalised outputs ...
+      float* part_ml;     // ... and [nsplit, B, n, H] (running max in log2 units, row sum) pairs; attn_merge_kernel writes ctx from them
+      int split_keys;     // filled by the launcher: keys per split (whole tiles); split z = blockIdx.z streams keys [z * split_keys, min(sep, (z + 1) * split_keys))
+    };
+  };
   int pingpong;  // filled by the launcher (PFN_TUNE_ATTN_PINGPONG): bit 0 forward, bit 1 key-block pass
   // filled by the launcher: the backward's key-block / query-block pair may run for a GROUP of datasets at a time (PFN_TUNE_ATTN_BWD_GROUP) -- datasets [b0, b0 + bg) of the
   // B in this call; every group re-uses the front of the dS^T scratch, so what the key-block pass wrote is still in the 256 MB memory-side cache when the query-block pass reads it
@@ -239,6 +250,11 @@ struct AttnArgs {
   float p_drop;            // 0 = off (the kernels without the mask arithmetic run)
   unsigned drop_seed;      // site seed of this layer's attention (dropout_site_seed(call seed, layer, 0)); the kernels mix (dataset, head) in
 };
+// splits of the key range [0, sep) that launch_attn_fwd_cache runs for n test rows of B datasets (a function of the grid size: few query blocks -> more splits);
+// sep < 0: the largest count any sep can give (what a workspace must hold)
+int attn_cache_splits(int B, int n, int E, int H, int sep, int precision);
+int launch_attn_fwd_cache(const AttnArgs& a, int precision, hipStream_t stream);
+void set_attn_cache_split_cap(int splits);      // PFN_TUNE_ATTN_CACHE_SPLITS: 0 = the rule, k > 0 = at most k splits
 void set_attn_pingpong(int mask);
 void set_attn_bwd_group(int datasets);      // 0 = all datasets of a call in one launch pair
 enum : int { ATTN_BWD_DELTA = 1, ATTN_BWD_KV = 2, ATTN_BWD_DQ = 4 };

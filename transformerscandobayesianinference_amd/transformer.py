@@ -180,6 +180,19 @@ def ragged_layout(T, widths, single_eval_positions):
     return seps, per_dataset, offs
 
 
+class PredictContext:
+    """A conditioned training set (`TransformerModel.condition`): every layer's keys and values of the train rows in one device buffer
+    (include/pfn_hip.h pfn_context_bytes), with what they were made from -- the parameter version, the descriptor, B, F, sep and the device.
+    `TransformerModel.predict` refuses a context whose model has changed since."""
+
+    def __init__(self, buffer, param_version, desc_key, B, F, sep, device):
+        self.buffer, self.param_version, self.desc_key = buffer, param_version, desc_key
+        self.B, self.F, self.sep, self.device = B, F, sep, device
+
+    def __repr__(self):
+        return f'PredictContext(B={self.B}, F={self.F}, sep={self.sep}, {self.buffer.numel()} bytes on {self.device})'
+
+
 class TransformerModel(nn.Module):
     requires_gpu = True   # train() checks this before building anything (the host-plumbing tests substitute a CPU stand-in)
 
@@ -377,6 +390,7 @@ class TransformerModel(nn.Module):
         through raw pointers (FusedClipAdam), or code that assigns through `p.data` (which bumps no version counter)."""
         self._shadow_version = None
         self._eval_shadow_version = None
+        self._param_updates = getattr(self, '_param_updates', 0) + 1      # (what a PredictContext compares: writes through raw pointers bump no version)
 
     def _param_version(self):
         """Every Parameter is a view of the flat buffer with its OWN version counter (`p.data = flat[...]` detaches
@@ -467,6 +481,90 @@ class TransformerModel(nn.Module):
         # (torch.split: its backward is ONE concatenation of the per-batch gradients; slicing would zero-fill and add a full-size tensor per batch)
         parts = torch.split(logits, [w * (T - sep) for sep, w in zip(seps, widths)])
         return [p.view(w, T - sep, logits.shape[1]).transpose(0, 1) for p, sep, w in zip(parts, seps, widths)]      # dataset-major rows -> the reference's [T - sep, b, n_out]
+
+    # ---- condition once, predict many ----
+    _PREDICT_ROWS = 1 << 15      # rows (test rows x datasets) per pfn_stack_predict call: bounds its workspace, any n is chunked to it
+
+    def _check_predict_model(self):
+        if self.pos_encoder is not None and not isinstance(self.pos_encoder, NoPositionalEncoding):
+            raise NotImplementedError('condition / predict: a positional encoding makes a row\'s output depend on its index in the sequence, so cached train rows '
+                                      'cannot serve test rows at other positions')
+        if self.input_ln is not None:
+            raise NotImplementedError('condition / predict: SeqBN normalises over the whole sequence, so the train rows\' activations depend on the test rows')
+        if not self._fused_embedding():
+            raise NotImplementedError('condition / predict need the fused embedding (Linear x / y encoders, no positional encoding, no SeqBN)')
+
+    def _predict_operands(self, stream):
+        if not self._is_flat():
+            self._flatten(next(self.parameters()).device)
+        return self._operands(stream, self._eval_desc is not None)      # eval_precision when the model has one, else precision (as an inference forward)
+
+    def _predict_version(self):
+        return (self._param_version(), getattr(self, '_param_updates', 0))
+
+    @torch.no_grad()
+    def condition(self, src):
+        """Run the training set src = (x_train [sep, B, F], y_train [sep, B]) once and keep every layer's keys and values: the returned PredictContext
+        serves any number of `predict` calls (pfn_stack_condition)."""
+        self._check_predict_model()
+        x, y = src
+        _hip.require_gpu_tensor(x, 'x')
+        _hip.require_gpu_tensor(next(self.parameters()), 'model parameters')
+        sep, B, F = x.shape
+        y = y.to(x.device)
+        if x.dtype != torch.float32 or x.stride(-1) != 1:
+            x = x.float().contiguous()
+        if y.dtype != torch.float32:
+            y = y.float()
+        lib = _hip.lib()
+        stream = _hip.stream_ptr(x.device)
+        desc, shadow = self._predict_operands(stream)
+        nbytes = _hip.check(lib.pfn_context_bytes(ctypes.byref(desc), B, sep), 'pfn_context_bytes')
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        if sep > 0:
+            ws_bytes = _hip.check(lib.pfn_workspace_bytes(ctypes.byref(desc), B, sep), 'pfn_workspace_bytes')
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+            _hip.check(lib.pfn_stack_condition(ctypes.byref(desc), self._flat.data_ptr(), shadow.data_ptr(), x.data_ptr(), x.stride(0), x.stride(1),
+                                               y.data_ptr(), y.stride(0), y.stride(1), B, sep, ws.data_ptr(), ws_bytes, buf.data_ptr(), nbytes, stream),
+                       'pfn_stack_condition')
+        return PredictContext(buf, self._predict_version(), desc.key(), B, F, sep, x.device)
+
+    @torch.no_grad()
+    def predict(self, context, x_test):
+        """Posterior-predictive logits [n, B, n_out] of the test rows x_test [n, B, F] given the conditioned training set: what model.eval() under
+        torch.no_grad() returns for model((cat(x_train, x_test), cat(y_train, anything)), single_eval_pos=sep), computed from the cached keys and values
+        (pfn_stack_predict).  Rows are independent; any n, in chunks of the caller's choosing."""
+        self._check_predict_model()
+        _hip.require_gpu_tensor(x_test, 'x_test')
+        _hip.require_gpu_tensor(next(self.parameters()), 'model parameters')
+        n, B, F = x_test.shape
+        if (B, F) != (context.B, context.F):
+            raise ValueError(f'predict: x_test has B={B}, F={F}; the context was conditioned on B={context.B}, F={context.F}')
+        if x_test.device != context.device:
+            raise ValueError(f'predict: x_test is on {x_test.device}, the context on {context.device}')
+        lib = _hip.lib()
+        stream = _hip.stream_ptr(x_test.device)
+        if not self._is_flat() or self._predict_version() != context.param_version:
+            raise RuntimeError('predict: the model parameters changed after condition() (optimizer step, load_state_dict, mark_params_updated); condition again')
+        desc, shadow = self._predict_operands(stream)
+        if desc.key() != context.desc_key:
+            raise RuntimeError('predict: the model descriptor (precision / schedule) changed after condition(); condition again')
+        if x_test.dtype != torch.float32 or x_test.stride(-1) != 1:
+            x_test = x_test.float().contiguous()
+        width = desc.n_out or desc.emsize
+        out = torch.empty((n, B, width), dtype=torch.float32, device=x_test.device)
+        chunk = max(1, self._PREDICT_ROWS // B)
+        ws = None
+        for t0 in range(0, n, chunk):
+            m = min(chunk, n - t0)
+            ws_bytes = _hip.check(lib.pfn_predict_workspace_bytes(ctypes.byref(desc), B, m), 'pfn_predict_workspace_bytes')
+            if ws is None or ws.numel() < ws_bytes:
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x_test.device)
+            xc = x_test[t0:t0 + m]
+            _hip.check(lib.pfn_stack_predict(ctypes.byref(desc), self._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(), context.buffer.numel(),
+                                             context.sep, xc.data_ptr(), xc.stride(0), xc.stride(1), B, m, ws.data_ptr(), ws.numel(), out[t0:t0 + m].data_ptr(),
+                                             stream), 'pfn_stack_predict')
+        return self.decoder(out) if self._custom_decoder else out
 
     # ---- forward ----
     def forward(self, src, src_mask=None, single_eval_pos=None):

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PFN_ABI_VERSION 9
+#define PFN_ABI_VERSION 10
 
 enum {
   PFN_OK = 0,
@@ -268,6 +268,32 @@ int pfn_stack_predict(const pfn_model_desc* d, const float* params, const void* 
                       int B, int n,
                       void* workspace, int64_t workspace_bytes, float* logits, void* stream);
 
+/* ---- INPUT GRADIENTS (ABI 10): d(output)/d(x) for Bayesian optimisation (reference acquisition_functions.py; botorch's optimize_acqf climbs grad_x of the
+ * acquisition value) and for sensitivity analyses.
+ * Predict: pfn_stack_predict_saved is pfn_stack_predict (same arguments, same kernels and fusion decisions, bit-identical logits) on a workspace of
+ *   pfn_predict_grad_workspace_bytes(d, B, n) bytes that keeps every layer's test-row activations (q|k|v, ctx, lse, the pre-LayerNorm sums and their statistics,
+ *   the GELU derivatives, the layer outputs) plus the backward's scratch: linear in nlayers, independent of sep.  pfn_stack_predict_backward then turns
+ *   dlogits [n * B, n_out] (row t * B + b; [n * B, emsize] when n_out == 0) into dx = d(x_test) [n, B, F] f32 with element strides (dx_st, dx_sb, 1).  The train
+ *   rows behind the context are constants: no gradient reaches the context or any parameter, and no parameter gradient is written.  fp16 descriptors run the
+ *   chain under the training backward's loss scale (from max |dlogits|); dx leaves unscaled.  The workspace must be the one the saved predict call wrote, for
+ *   the same descriptor, parameters, context, sep, B and n.
+ * Full forward: pfn_stack_input_grads, after pfn_stack_backward / pfn_stack_backward_split on the same workspace (fused embedding, not ragged): dx [S, B, F] for
+ *   every row and, when dy is not NULL, dy [S, B] for the train rows -- rows t >= sep of dy are 0 (the reference reads y[:sep] only, transformer.py:73).
+ * Wrong sizes, NULL pointers, or a context smaller than pfn_context_bytes return PFN_ERR_ARGUMENT before anything is launched. */
+int64_t pfn_predict_grad_workspace_bytes(const pfn_model_desc* d, int B, int n);
+int pfn_stack_predict_saved(const pfn_model_desc* d, const float* params, const void* shadow,
+                            const void* context, int64_t context_bytes, int sep,
+                            const float* x, int64_t x_st, int64_t x_sb,
+                            int B, int n,
+                            void* workspace, int64_t workspace_bytes, float* logits, void* stream);
+int pfn_stack_predict_backward(const pfn_model_desc* d, const float* params, const void* shadow,
+                               const void* context, int64_t context_bytes, int sep, int B, int n,
+                               void* workspace, int64_t workspace_bytes, const float* dlogits,
+                               float* dx, int64_t dx_st, int64_t dx_sb, void* stream);
+int pfn_stack_input_grads(const pfn_model_desc* d, const float* params, int B, int S, int sep,
+                          const void* workspace, int64_t workspace_bytes,
+                          float* dx, int64_t dx_st, int64_t dx_sb, float* dy, int64_t dy_st, int64_t dy_sb, void* stream);
+
 /* ---- bar distribution: replaces BarDistribution / FullSupportBarDistribution.forward and .mean
  * (bar_distribution.py:19-38, 83-117).  logits [R, nbars] f32 (row stride ld), y [R], borders
  * [nbars+1] sorted.  nll [R].  lse [R] and bucket [R] are saved for the backward. */
@@ -279,6 +305,9 @@ int pfn_bar_nll_backward(const float* logits, int64_t ld, const float* lse, cons
                          const float* gout, int64_t R, int nbars, float* dlogits, void* stream);
 int pfn_bar_mean(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars,
                  int full_support, float* mean, void* stream);
+/* its gradient (ABI 10): dlogits[r, j] = gout[r] * p_j * (c_j - mean[r]), c_j the bucket means pfn_bar_mean uses, mean[r] what it returned; row stride ld */
+int pfn_bar_mean_backward(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                          const float* mean, const float* gout, float* dlogits, void* stream);
 
 /* ---- optimizer: replaces clip_grad_norm_(params, 1.) + Adam.step() + zero_grad()
  * (train.py:55,95-97).  One fused pass over the flat buffers; the clip coefficient is computed on

@@ -1,8 +1,10 @@
 """Condition once, predict many, timed at the configs[1] model shape (18 features, emsize 512, 4 heads, nhid 1024, 6 layers, 1000 bars), sep = 2000:
 one inference forward at sep + n rows, `condition` once, `predict` repeated -- for n in {1, 16, 256, 2048}, B in {1, 64}, exact-f32 inference and fp16.
 HIP events around the calls; one JSON line per (format, B, n) and a last line with the summary.
-    python tools/bench_predict.py [--quick] [--reps R] [--no-split]
---quick: B = 1, n in {1, 16} only (the rocprofv3 kernel-trace run); --no-split: PFN_TUNE_ATTN_CACHE_SPLITS = 1 (one pass over the keys, no merge)."""
+    python tools/bench_predict.py [--quick] [--reps R] [--no-split] [--grad]
+--quick: B = 1, n in {1, 16} only (the rocprofv3 kernel-trace run); --no-split: PFN_TUNE_ATTN_CACHE_SPLITS = 1 (one pass over the keys, no merge).
+--grad: the input gradient at B = 64, n = 256 instead: predict_saved + predict_backward (pfn_stack_predict_backward) against predict, and against the only
+alternative without them, a full forward + backward over sep + n rows with x requiring grad (which runs the training-precision kernels, fp16)."""
 import argparse
 import json
 import os
@@ -51,14 +53,55 @@ def splits(B, n, prec):
     return 1 if wgs >= 256 else max(1, min(512 // wgs, -(-SEP // kvb)))
 
 
+def grad_rows(reps):
+    B, n = 64, 256
+    rows = []
+    for fmt in ('fp16', 'f32'):
+        model = model_for(fmt)
+        g = torch.Generator().manual_seed(B)
+        x = torch.randn(SEP + n, B, F, generator=g).cuda()
+        y = torch.randn(SEP + n, B, generator=g).cuda()
+        R = torch.randn(n, B, NBARS, generator=g).cuda()
+        with torch.no_grad():
+            ctx = model.condition((x[:SEP], y[:SEP]))
+            pred_ms = timed(lambda: model.predict(ctx, x[SEP:]), reps)
+        xt = x[SEP:].clone().requires_grad_(True)
+        saved_ms = timed(lambda: model.predict(ctx, xt), reps)
+
+        def fwd_bwd():
+            out = model.predict(ctx, xt)
+            torch.autograd.grad(out, xt, R)
+        grad_ms = timed(fwd_bwd, reps)
+        xf = x.clone().requires_grad_(True)
+
+        def full():
+            out = model((xf, y), single_eval_pos=SEP)
+            torch.autograd.grad(out, xf, R)
+        full_ms = timed(full, max(2, reps // 2))
+        backward_ms = grad_ms - saved_ms
+        r = dict(format=fmt, B=B, n=n, sep=SEP, predict_ms=pred_ms, predict_saved_ms=saved_ms, predict_backward_ms=backward_ms,
+                 saved_plus_backward_ms=grad_ms, backward_over_predict=backward_ms / pred_ms, full_forward_backward_ms=full_ms,
+                 full_over_saved_plus_backward=full_ms / grad_ms)
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+        del ctx, model
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--quick', action='store_true')
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--no-split', action='store_true')
+    ap.add_argument('--grad', action='store_true')
     args = ap.parse_args()
     if args.no_split:
         _hip.check(_hip.lib().pfn_set_tuning(PFN_TUNE_ATTN_CACHE_SPLITS, 1), 'pfn_set_tuning')
+    if args.grad:
+        rows = grad_rows(args.reps)
+        print(json.dumps(dict(summary='bench_predict --grad', no_split=args.no_split, rows=len(rows), device=torch.cuda.get_device_name(0))), flush=True)
+        return
     ns = (1, 16) if args.quick else (1, 16, 256, 2048)
     Bs = (1,) if args.quick else (1, 64)
     fmts = ('f32', 'fp16')

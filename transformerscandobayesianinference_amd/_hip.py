@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libpfn_hip.so')
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 MAX_FEATURES = 1022      # pfn_model_desc.num_features (include/pfn_hip.h): wider encoders are refused when the model is built
 PREC_BF16 = 0
@@ -76,9 +76,18 @@ SIGNATURES = {
     'pfn_predict_workspace_bytes': (_L, [_D, _I, _I]),
     # (d, params, shadow, context, context_bytes, sep, x, x_st, x_sb, B, n, ws, ws_bytes, logits, stream)
     'pfn_stack_predict': (_I, [_D, _P, _P, _P, _L, _I, _P, _L, _L, _I, _I, _P, _L, _P, _P]),
+    'pfn_predict_grad_workspace_bytes': (_L, [_D, _I, _I]),
+    # (same arguments as pfn_stack_predict; the workspace of pfn_predict_grad_workspace_bytes)
+    'pfn_stack_predict_saved': (_I, [_D, _P, _P, _P, _L, _I, _P, _L, _L, _I, _I, _P, _L, _P, _P]),
+    # (d, params, shadow, context, context_bytes, sep, B, n, ws, ws_bytes, dlogits, dx, dx_st, dx_sb, stream)
+    'pfn_stack_predict_backward': (_I, [_D, _P, _P, _P, _L, _I, _I, _I, _P, _L, _P, _P, _L, _L, _P]),
+    # (d, params, B, S, sep, ws, ws_bytes, dx, dx_st, dx_sb, dy, dy_st, dy_sb, stream)
+    'pfn_stack_input_grads': (_I, [_D, _P, _I, _I, _I, _P, _L, _P, _L, _L, _P, _L, _L, _P]),
     'pfn_bar_nll_forward': (_I, [_P, _L, _P, _P, _L, _I, _I, _P, _P, _P, _P]),
     'pfn_bar_nll_backward': (_I, [_P, _L, _P, _P, _P, _L, _I, _P, _P]),
     'pfn_bar_mean': (_I, [_P, _L, _P, _L, _I, _I, _P, _P]),
+    # (logits, ld, borders, R, nbars, full_support, mean, gout, dlogits, stream)
+    'pfn_bar_mean_backward': (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _P, _P]),
     'pfn_clip_adam_step': (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P]),
     'pfn_gp_workspace_bytes': (_L, [_I, _I]),
     'pfn_gp_prior_sample': (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P, _P]),

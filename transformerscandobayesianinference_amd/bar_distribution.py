@@ -43,16 +43,36 @@ class _BarNLL(torch.autograd.Function):
         return dlogits, None, None, None
 
 
+class _BarMeanFunction(torch.autograd.Function):
+    """mean = softmax(logits) . bucket means (pfn_bar_mean); backward pfn_bar_mean_backward: d mean / d logit_j = p_j (c_j - mean)."""
+
+    @staticmethod
+    def forward(ctx, flat, borders, full_support):
+        out = torch.empty(flat.shape[0], device=flat.device, dtype=torch.float32)
+        _hip.check(_hip.lib().pfn_bar_mean(flat.data_ptr(), flat.shape[1], borders.data_ptr(),
+                                           flat.shape[0], flat.shape[1], int(full_support), out.data_ptr(),
+                                           _hip.stream_ptr(flat.device)), 'pfn_bar_mean')
+        ctx.save_for_backward(flat, borders, out)
+        ctx.full_support = full_support
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        flat, borders, mean = ctx.saved_tensors
+        gout = gout.contiguous().float()
+        dlogits = torch.empty_like(flat)
+        _hip.check(_hip.lib().pfn_bar_mean_backward(flat.data_ptr(), flat.shape[1], borders.data_ptr(), flat.shape[0], flat.shape[1],
+                                                    int(ctx.full_support), mean.data_ptr(), gout.data_ptr(), dlogits.data_ptr(),
+                                                    _hip.stream_ptr(flat.device)), 'pfn_bar_mean_backward')
+        return dlogits, None, None
+
+
 def _bar_mean(logits, borders, full_support):
     _hip.require_gpu_tensor(logits, 'logits')
     shape = logits.shape[:-1]
-    flat = logits.detach().reshape(-1, logits.shape[-1]).contiguous().float()
-    out = torch.empty(flat.shape[0], device=flat.device, dtype=torch.float32)
-    borders = borders.contiguous().float().to(flat.device)
-    _hip.check(_hip.lib().pfn_bar_mean(flat.data_ptr(), flat.shape[1], borders.data_ptr(),
-                                       flat.shape[0], flat.shape[1], int(full_support), out.data_ptr(),
-                                       _hip.stream_ptr(flat.device)), 'pfn_bar_mean')
-    return out.view(shape)
+    flat = logits.reshape(-1, logits.shape[-1]).contiguous().float()
+    borders = borders.detach().contiguous().float().to(flat.device)
+    return _BarMeanFunction.apply(flat, borders, full_support).view(shape)
 
 
 class BarDistribution(nn.Module):

@@ -521,7 +521,8 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
       for (int r = 0; r < 16; ++r) v[r] = o[db][r] * inv;
       store_row_block<T>(out + db * 32, v, h, qvalid);
     }
-    if (!CACHE && qvalid && h == 0 && vcol0 == 0) a.lse[((long)b * a.H + hd) * a.S + qi] = (m + __builtin_amdgcn_logf(lsum)) * LN2;
+    // (CACHE: only when the predict pass keeps its activations for a backward -- pfn_stack_predict_saved)
+    if ((!CACHE || a.lse) && qvalid && h == 0 && vcol0 == 0) a.lse[((long)b * a.H + hd) * a.S + qi] = (m + __builtin_amdgcn_logf(lsum)) * LN2;
   }
 }
 
@@ -549,6 +550,190 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(AttnArgs a, int nsplit,
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[e] *= inv;
     store4<T>(reinterpret_cast<T*>(a.ctx) + row * a.E + c, acc);
+    // the merged log-sum-exp (natural units, as the unsplit kernel writes it) when a backward will read it
+    if (a.lse && c % D == 0) a.lse[((row / a.S) * a.H + hd) * a.S + row % a.S] = (mx + __builtin_amdgcn_logf(l)) * LN2;
+  }
+}
+
+// =============================================================================================
+// predict backward against a K / V cache (pfn_stack_predict_backward): d(q | k | v) of the test rows, the cached keys and values being constants
+// =============================================================================================
+// The forward's CACHE layout (lane <-> query, S^T = K Q^T) with the saved log-sum-exp in place of the online softmax.  Per key tile of KVB keys and wave:
+//   S^T  = K Q^T     (accumulator pre-loaded with -lse2 / c:  P = exp2(c S'))
+//   dP^T = V dO^T    (pre-loaded with -delta:                 dS = P dP')
+//   dQ^T += K^T dS^T (K from a column image of the same tile; dS^T leaves the accumulator as the forward's P does for P.V)
+// The training query-block pass with P recomputed instead of read: no dS^T is stored, and dQ stays in registers over the key sweep.  delta = rowsum(dO o O) is
+// formed in the prologue from the lane's own rows.  The self key is the initial state: dQ^T starts at ds_self k_self, and split 0 writes
+// dk_self = ds_self q / sqrt(D) and dv_self = p_self dO.  (Centred keys change nothing: the shift is one vector per dataset and sum_j dS_j = 0.)
+// One split: dQ / sqrt(D) goes straight to dqkv.  Several (gridDim.z): f32 partials [nsplit, B, n, E], summed in split order by attn_bwd_cache_merge_kernel.
+// DQ < D (exact f32 at head dim 256, as the forward's V slices): the dQ columns in gridDim.y slices, each of which forms the whole S and dP.
+template <typename T, int D> struct BwdCacheCfg {
+  static constexpr int DQ = (sizeof(T) == 4 && D == 256) ? 128 : D;
+  static constexpr int KVB = 32;                       // keys per tile: one 32 x 32 accumulator each for S and dP
+  static constexpr int NKK = D / 16, NDQ = DQ / 32, NPF = KVB / 16;
+  static constexpr int RB = D * (int)sizeof(T), QB = DQ * (int)sizeof(T);
+  static constexpr int RS = PadStride<RB>::ROW, CSQ = PadStride<QB>::COL;
+  static constexpr int KROW = KVB * RS, KCOL = KVB * CSQ;
+  static constexpr size_t LDS = 2 * KROW + KCOL;       // K and V row images, the K column image (the dQ slice's columns)
+  // the next tile's loads in flight under this tile's products -- except in exact f32 at head dim 256, where the staging registers (80) would spill
+  static constexpr bool PREFETCH = !(sizeof(T) == 4 && D == 256);
+};
+
+template <typename T, int D>
+__global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_cache_kernel(AttnCacheBwdArgs a) {
+  operand_store_mode<T>();
+  using C = AttnCfg<T, D>;
+  using G = BwdCacheCfg<T, D>;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  LdsPtr smem = lds_cast(smem_raw);
+  LdsPtr Krow = smem, Vrow = smem + G::KROW, Kcol = smem + 2 * G::KROW;
+  const AttnBlock wg = attn_block((a.S + C::QBLK - 1) / C::QBLK, a.H);
+  const int b = wg.b, hd = wg.hd;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, li = lane & 31;
+  const int qcol0 = G::DQ == D ? 0 : (int)blockIdx.y * G::DQ;
+  const long rs = 3L * a.E;
+  const int qi = wg.blk * C::QBLK + wave * 32 + li;
+  const bool qvalid = qi < a.S;
+  const long row = (long)b * a.S + min(qi, a.S - 1);
+  const T* qrow = reinterpret_cast<const T*>(a.qkv) + row * rs + hd * D;
+  const T* orow = reinterpret_cast<const T*>(a.ctx) + row * a.E + hd * D;
+  const T* dorow = reinterpret_cast<const T*>(a.dctx) + row * a.E + hd * D;
+  const int z = blockIdx.z, k_lo = z * a.split_keys;
+  const int nkeys = max(0, min(a.sep - k_lo, a.split_keys));
+  const long kld = a.kv_ld;
+  const T* Ksrc = reinterpret_cast<const T*>(a.kv) + b * a.kv_sb + k_lo * kld + hd * D;
+  const T* Vsrc = Ksrc + a.E;
+  const float scale = rsqrtf((float)D), c2 = scale * LOG2E;
+
+  Frag<T> qf[G::NKK], df[G::NKK];
+  float dpart = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < G::NKK; ++kk) {
+    qf[kk] = load_frag_global<T>(qrow + kk * 16 + 8 * h);
+    df[kk] = load_frag_global<T>(dorow + kk * 16 + 8 * h);
+    dpart += dot8(df[kk], load_frag_global<T>(orow + kk * 16 + 8 * h));
+  }
+  const float delta = dpart + __shfl_xor(dpart, 32, 64);
+  const float lse2 = a.lse[((long)b * a.H + hd) * a.S + (row - (long)b * a.S)] * LOG2E;
+
+  f32x16 o[G::NDQ];      // dQ^T (rows = the slice's columns, lane = query), unscaled
+#pragma unroll
+  for (int db = 0; db < G::NDQ; ++db)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+  if (z == 0) {      // the self key: its probability and score gradient from the lane's own rows
+    const T* krow = qrow + a.E;
+    const T* vrow = qrow + 2 * a.E;
+    float sp = 0.f, dpp = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < G::NKK; ++kk) {
+      sp += dot8(qf[kk], load_frag_global<T>(krow + kk * 16 + 8 * h));
+      dpp += dot8(df[kk], load_frag_global<T>(vrow + kk * 16 + 8 * h));
+    }
+    sp += __shfl_xor(sp, 32, 64);
+    dpp += __shfl_xor(dpp, 32, 64);
+    const float p = fast_exp2(__builtin_fmaf(sp, c2, -lse2)), ds = p * (dpp - delta);
+#pragma unroll
+    for (int db = 0; db < G::NDQ; ++db)
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const f32x4 kv4 = load4<T>(krow + qcol0 + db * 32 + 8 * rg + 4 * h);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[db][4 * rg + e] = ds * kv4[e];
+      }
+    if (qvalid && blockIdx.y == 0) {
+      T* dst = reinterpret_cast<T*>(a.dqkv) + row * rs + hd * D;
+#pragma unroll
+      for (int kk = 0; kk < G::NKK; ++kk) {
+        float vk[8], vv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { vk[e] = scale * ds * frag_get(qf[kk], e); vv[e] = p * frag_get(df[kk], e); }
+        store_frag_global<T>(dst + a.E + kk * 16 + 8 * h, vk);
+        store_frag_global<T>(dst + 2 * a.E + kk * 16 + 8 * h, vv);
+      }
+    }
+  }
+
+  // key tiles through one LDS set, staged in registers one tile ahead where the budget allows (BwdCacheCfg::PREFETCH)
+  const int ntiles = (nkeys + G::KVB - 1) / G::KVB;
+  TileStage<T, G::KVB, G::RB, C::NT> sk, sv;
+  TileStage<T, G::KVB, G::QB, C::NT> skc;      // (DQ < D only: the slice's K columns)
+  auto issue = [&](int t) __attribute__((always_inline)) {
+    const long k0 = (long)t * G::KVB;
+    sk.issue(Ksrc + k0 * kld, kld, nkeys - (int)k0, D);
+    sv.issue(Vsrc + k0 * kld, kld, nkeys - (int)k0, D);
+    if constexpr (G::DQ < D) skc.issue(Ksrc + k0 * kld + qcol0, kld, nkeys - (int)k0, G::DQ);
+  };
+  if constexpr (G::PREFETCH) { if (ntiles > 0) issue(0); }
+  const float s0 = -lse2 / c2;
+  for (int t = 0; t < ntiles; ++t) {
+    __syncthreads();      // every wave is done with tile t - 1
+    if constexpr (!G::PREFETCH) issue(t);
+    sk.template commit_p<G::RS>(Krow);
+    sv.template commit_p<G::RS>(Vrow);
+    if constexpr (G::DQ < D) skc.template commit_p<G::CSQ>(Kcol);
+    else sk.template commit_p<G::CSQ>(Kcol);
+    __syncthreads();
+    if constexpr (G::PREFETCH) { if (t + 1 < ntiles) issue(t + 1); }
+    f32x16 st, dp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { st[r] = s0; dp[r] = -delta; }
+#pragma unroll
+    for (int kk = 0; kk < G::NKK; ++kk) st = mma32(load_frag_row_p<T, G::RS>(Krow, li, kk * 16), qf[kk], st);
+#pragma unroll
+    for (int kk = 0; kk < G::NKK; ++kk) dp = mma32(load_frag_row_p<T, G::RS>(Vrow, li, kk * 16), df[kk], dp);
+    const int k0 = t * G::KVB;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float p = (k0 + acc_row(r, lane) < nkeys) ? fast_exp2(st[r] * c2) : 0.f;      // (keys past the split: zero rows of the tile)
+      st[r] = p * dp[r];
+    }
+    Frag<T> dsf[G::NPF];
+#pragma unroll
+    for (int c = 0; c < G::NPF; ++c) dsf[c] = acc_to_frag<T>(st, c);
+#pragma unroll
+    for (int c = 0; c < G::NPF; ++c)
+#pragma unroll
+      for (int db = 0; db < G::NDQ; ++db) o[db] = mma32(load_frag_tr_p<T, G::CSQ, 2>(Kcol, c * 16, db * 32), dsf[c], o[db]);
+  }
+
+  if (gridDim.z == 1) {
+    T* out = reinterpret_cast<T*>(a.dqkv) + row * rs + hd * D + qcol0;
+#pragma unroll
+    for (int db = 0; db < G::NDQ; ++db) {
+      float v[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) v[r] = o[db][r] * scale;
+      store_row_block<T>(out + db * 32, v, h, qvalid);
+    }
+  } else {
+    float* out = a.part_dq + ((long)z * a.B * a.S + row) * a.E + hd * D + qcol0;
+#pragma unroll
+    for (int db = 0; db < G::NDQ; ++db) {
+      float v[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) v[r] = o[db][r];
+      store_row_block<float>(out + db * 32, v, h, qvalid);
+    }
+  }
+}
+
+// The splits' partial dQ summed in split order (no atomics: the same bits on every run) and scaled into dqkv's Q columns; one thread per (test row, 4 columns)
+template <typename T>
+__global__ __launch_bounds__(256) void attn_bwd_cache_merge_kernel(AttnCacheBwdArgs a, int nsplit, float scale) {
+  const long rows = (long)a.B * a.S, c4n = a.E / 4, total = rows * c4n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long row = i / c4n;
+    const int c = (int)(i - row * c4n) * 4;
+    f32x4 acc = *reinterpret_cast<const f32x4*>(a.part_dq + row * a.E + c);
+    for (int z = 1; z < nsplit; ++z) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(a.part_dq + (z * rows + row) * a.E + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] += v[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] *= scale;
+    store4<T>(reinterpret_cast<T*>(a.dqkv) + row * 3L * a.E + c, acc);
   }
 }
 
@@ -1756,6 +1941,32 @@ int launch_attn_fwd_cache(const AttnArgs& a_in, int precision, hipStream_t s) {
   a.pingpong = g_attn_pingpong;
   a.q_begin = 0; a.sep_of = nullptr; a.q_from_sep = 0; a.p_drop = 0.f; a.xq = nullptr;
   PFN_ATTN_DISPATCH(launch_fwd_cache_t, return (launch_fwd_cache_t<float, 256>(a, s)))
+}
+template <typename T, int D> static int launch_bwd_cache_t(const AttnCacheBwdArgs& a_in, hipStream_t s) {
+  using C = AttnCfg<T, D>;
+  using G = BwdCacheCfg<T, D>;
+  static_assert(G::LDS <= 160 * 1024, "cached attention backward: tile buffers exceed the CU's LDS");
+  AttnCacheBwdArgs a = a_in;
+  int nsplit = attn_cache_splits(a.B, a.S, a.E, a.H, a.sep, sizeof(T) == 4 ? PFN_PREC_F32 : PFN_PREC_BF16);      // the forward's rule
+  if (g_attn_cache_split_cap > 0) nsplit = std::min(nsplit, g_attn_cache_split_cap);
+  const int ntiles = (a.sep + G::KVB - 1) / G::KVB;
+  a.split_keys = nsplit > 1 ? (ntiles + nsplit - 1) / nsplit * G::KVB : std::max(a.sep, 1);
+  const int nz = nsplit > 1 ? (a.sep + a.split_keys - 1) / a.split_keys : 1;
+  if (nz > 1 && !a.part_dq) return PFN_ERR_ARGUMENT;
+  static LdsAllowance allowance;
+  allowance.ensure(attn_bwd_cache_kernel<T, D>, G::LDS);
+  const dim3 grid(((a.S + C::QBLK - 1) / C::QBLK) * a.H * a.B, D / G::DQ, nz);
+  hipLaunchKernelGGL((attn_bwd_cache_kernel<T, D>), grid, dim3(C::NT), G::LDS, s, a);
+  if (nz > 1) {
+    const long work = (long)a.B * a.S * (a.E / 4);
+    hipLaunchKernelGGL(attn_bwd_cache_merge_kernel<T>, dim3((unsigned)std::min<long>((work + 255) / 256, 4096)), dim3(256), 0, s, a, nz, 1.f / sqrtf((float)D));
+  }
+  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+}
+int launch_attn_bwd_cache(const AttnCacheBwdArgs& a, int precision, hipStream_t s) {
+  if (a.B <= 0 || a.S <= 0 || a.H <= 0 || a.E % a.H || a.sep < 0 || (a.sep > 0 && !a.kv) || !a.qkv || !a.ctx || !a.lse || !a.dctx || !a.dqkv) return PFN_ERR_ARGUMENT;
+  if ((a.E * prec_esize(precision)) % 16 || (a.kv_ld * prec_esize(precision)) % 16) return PFN_ERR_ALIGNMENT;
+  PFN_ATTN_DISPATCH(launch_bwd_cache_t, return (launch_bwd_cache_t<float, 256>(a, s)))
 }
 void attn_bwd_ds_dims(int S, int sep, int* rows, int* ld) {
   *rows = (sep + 63) / 64 * 64;       // whole key tiles of the dQ pass

@@ -106,6 +106,16 @@ __global__ __launch_bounds__(256) void bar_nll_bwd_kernel(BarArgs a) {
   }
 }
 
+// mean of bucket i: its midpoint, or for full support the half-normal tail means (bar_distribution.py:110-117)
+__device__ __forceinline__ float bar_bucket_mean(const BarArgs& a, int i) {
+  const int nb = a.nbars;
+  float bm = a.borders[i] + 0.5f * (a.borders[i + 1] - a.borders[i]);
+  if (a.full_support) {
+    if (i == 0) bm = a.borders[1] - (a.borders[1] - a.borders[0]) / HALFNORMAL_ICDF_HALF * SQRT_2_OVER_PI;
+    if (i == nb - 1) bm = a.borders[nb - 1] + (a.borders[nb] - a.borders[nb - 1]) / HALFNORMAL_ICDF_HALF * SQRT_2_OVER_PI;
+  }
+  return bm;
+}
 // mean of the bar distribution: softmax(logits) . bucket_means (bar_distribution.py:35-38,110-117)
 __global__ __launch_bounds__(256) void bar_mean_kernel(BarArgs a) {
   const int lane = threadIdx.x & 63;
@@ -115,16 +125,22 @@ __global__ __launch_bounds__(256) void bar_mean_kernel(BarArgs a) {
     float mx, se;
     row_max_sumexp(row, nb, lane, mx, se);
     float acc = 0.f;
-    for (int i = lane; i < nb; i += 64) {
-      float bm = a.borders[i] + 0.5f * (a.borders[i + 1] - a.borders[i]);
-      if (a.full_support) {
-        if (i == 0) bm = a.borders[1] - (a.borders[1] - a.borders[0]) / HALFNORMAL_ICDF_HALF * SQRT_2_OVER_PI;
-        if (i == nb - 1) bm = a.borders[nb - 1] + (a.borders[nb] - a.borders[nb - 1]) / HALFNORMAL_ICDF_HALF * SQRT_2_OVER_PI;
-      }
-      acc += __expf(row[i] - mx) * bm;
-    }
+    for (int i = lane; i < nb; i += 64) acc += __expf(row[i] - mx) * bar_bucket_mean(a, i);
     acc = wave_sum(acc);
     if (lane == 0) a.mean_out[r] = acc / se;
+  }
+}
+// its gradient: d mean / d logit_j = p_j (c_j - mean), times the incoming gout; one wave per row
+__global__ __launch_bounds__(256) void bar_mean_bwd_kernel(BarArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int nb = a.nbars;
+  for (long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6); r < a.R; r += (long)gridDim.x * 4) {
+    const float* row = a.logits + r * a.ld;
+    float* drow = a.dlogits + r * a.ld;
+    float mx, se;
+    row_max_sumexp(row, nb, lane, mx, se);
+    const float mean = a.mean_out[r], g = a.gout[r] / se;
+    for (int i = lane; i < nb; i += 64) drow[i] = g * __expf(row[i] - mx) * (bar_bucket_mean(a, i) - mean);
   }
 }
 
@@ -144,6 +160,11 @@ int launch_bar_nll_bwd(const BarArgs& a, hipStream_t s) {
 int launch_bar_mean(const BarArgs& a, hipStream_t s) {
   if (a.R == 0) return PFN_OK;
   hipLaunchKernelGGL(bar_mean_kernel, dim3(rows_grid(a.R)), dim3(256), 0, s, a);
+  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+}
+int launch_bar_mean_bwd(const BarArgs& a, hipStream_t s) {
+  if (a.R == 0) return PFN_OK;
+  hipLaunchKernelGGL(bar_mean_bwd_kernel, dim3(rows_grid(a.R)), dim3(256), 0, s, a);
   return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 

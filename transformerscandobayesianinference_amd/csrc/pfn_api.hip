@@ -267,6 +267,48 @@ PredictWs carve_predict(const pfn_model_desc& d, int B, int n, char* base) {
   return w;
 }
 
+// Workspace of a predict pass that keeps what its backward reads (pfn_stack_predict_saved / pfn_stack_predict_backward): every layer's q|k|v, ctx, lse, both pre-LayerNorm
+// sums with their row statistics, the GELU derivative and the layer output (the next layer's input); the decoder's GELU derivative.  Behind it the backward's scratch:
+// one set of gradient rows (the chain runs one layer at a time), the attention's split partials (the forward's, re-used) and the sink of the LayerNorm kernels' parameter sums.
+struct PredictLayerWs { char *qkv, *ctx, *hpre, *x2_t; float *lse, *y1, *mean1, *rstd1, *y2, *mean2, *rstd2, *x2; };
+struct PredictGradWs {
+  float* x0; char* x0_t;                       // the embedding output (layer 0's input)
+  std::vector<PredictLayerWs> layer;
+  float* x1; char *x1_t, *h;                   // read inside a layer only: shared
+  char *xt_t, *dt, *dpre;                      // the decoder's input rows (t B + b), its GELU output and derivative
+  float *part_o, *part_ml;                     // attention splits (forward), then the backward's partial dQ
+  // backward
+  char *dlog_t, *dd_t, *dy2_t, *dh_t, *dy1_t, *dctx_t, *dqkv_t, *gA_t;
+  float *dxt, *gA, *lscale, *sink;
+  int64_t bytes;
+};
+PredictGradWs carve_predict_grad(const pfn_model_desc& d, int B, int n, char* base) {
+  PredictGradWs w;
+  const int64_t M = (int64_t)B * n, E = d.emsize, F = d.nhid, es = esize(d.precision);
+  const int64_t nsplit = attn_cache_splits(B, n, d.emsize, d.nhead, -1, d.precision);
+  const int64_t npad = make_layout(d).n_out_pad;
+  int64_t cur = 0;
+  auto take = [&](int64_t nbytes) { char* p = base ? base + cur : nullptr; cur = align_up(cur + nbytes, 256); return p; };
+  w.x0 = (float*)take(M * E * 4); w.x0_t = take(M * E * es);
+  w.layer.resize(d.nlayers);
+  for (auto& l : w.layer) {
+    l.qkv = take(M * 3 * E * es); l.ctx = take(M * E * es); l.lse = (float*)take((int64_t)B * d.nhead * n * 4);
+    l.y1 = (float*)take(M * E * 4); l.mean1 = (float*)take(M * 4); l.rstd1 = (float*)take(M * 4);
+    l.hpre = take(M * F * es);
+    l.y2 = (float*)take(M * E * 4); l.mean2 = (float*)take(M * 4); l.rstd2 = (float*)take(M * 4);
+    l.x2 = (float*)take(M * E * 4); l.x2_t = take(M * E * es);
+  }
+  w.x1 = (float*)take(M * E * 4); w.x1_t = take(M * E * es); w.h = take(M * F * es);
+  w.xt_t = take(M * E * es); w.dt = take(M * F * es); w.dpre = take(M * F * es);
+  w.part_o = (float*)take(nsplit > 1 ? nsplit * M * E * 4 : 0); w.part_ml = (float*)take(nsplit > 1 ? nsplit * M * d.nhead * 8 : 0);
+  w.dlog_t = take(M * npad * es); w.dd_t = take(M * F * es);
+  w.dy2_t = take(M * E * es); w.dh_t = take(M * F * es); w.dy1_t = take(M * E * es); w.dctx_t = take(M * E * es); w.dqkv_t = take(M * 3 * E * es);
+  w.gA_t = take(M * E * es); w.dxt = (float*)take(M * E * 4); w.gA = (float*)take(M * E * 4);
+  w.lscale = (float*)take(256); w.sink = (float*)take(3 * E * 4);
+  w.bytes = cur;
+  return w;
+}
+
 GemmNT nt(const void* A, long lda, const void* B, long ldb, int M, int N, int K, int flags) {
   GemmNT g;
   memset(&g, 0, sizeof(g));
@@ -682,17 +724,30 @@ int64_t pfn_predict_workspace_bytes(const pfn_model_desc* d, int B, int n) {
   if (check_desc(d) != PFN_OK || B < 1 || n < 0) return -1;
   return carve_predict(*d, B, n, nullptr).bytes;
 }
-// The test rows alone, layer by layer, each against its layer's cached keys: the forward's schedule (same kernels, same fusion rules) on B n rows
-int pfn_stack_predict(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep,
-                      const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes, float* logits, void* stream) {
+int64_t pfn_predict_grad_workspace_bytes(const pfn_model_desc* d, int B, int n) {
+  if (check_desc(d) != PFN_OK || B < 1 || n < 0) return -1;
+  return carve_predict_grad(*d, B, n, nullptr).bytes;
+}
+// The test rows alone, layer by layer, each against its layer's cached keys: the forward's schedule (same kernels, same fusion rules) on B n rows.
+// sv == nullptr: pfn_stack_predict (two alternating row sets in w); else pfn_stack_predict_saved (every layer's buffers kept in sv, the attention's lse written).
+static int stack_predict_impl(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep,
+                              const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes, float* logits, void* stream,
+                              bool saved) {
   PFN_TRY(check_desc(d));
   if (B < 1 || n < 0 || sep < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d n=%d sep=%d", B, n, sep);
   const Context c = context_layout(*d, B, sep);
   if (sep > 0 && d->nlayers > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context with sep=%d", sep);
   if (context_bytes < c.bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)c.bytes);
   if (!params || !shadow || !workspace || (n > 0 && (!x || !logits))) return fail(PFN_ERR_ARGUMENT, "null pointer");
-  PredictWs w = carve_predict(*d, B, n, (char*)workspace);
-  if (workspace_bytes < w.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)w.bytes);
+  PredictWs w;
+  PredictGradWs sv;
+  if (saved) {
+    sv = carve_predict_grad(*d, B, n, (char*)workspace);
+    if (workspace_bytes < sv.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)sv.bytes);
+  } else {
+    w = carve_predict(*d, B, n, (char*)workspace);
+    if (workspace_bytes < w.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)w.bytes);
+  }
   if (n == 0) return PFN_OK;
   hipStream_t s = (hipStream_t)stream;
   const int prec = d->precision, es = esize(prec);
@@ -700,29 +755,46 @@ int pfn_stack_predict(const pfn_model_desc* d, const float* params, const void* 
   Layout L = make_layout(*d);
   const char* sh = (const char*)shadow;
   auto W = [&](int64_t off) { return (const void*)(sh + off * es); };
+  // the buffers of layer l: the layer input (set 2 / the previous layer's output), q|k|v, ctx, set 1, h, hpre and the output (set 2 again / kept)
+  struct LayerBufs { float *xin; char* xin_t; char *qkv, *ctx; float* lse; float *y1, *mean1, *rstd1, *x1; char *x1_t, *h, *hpre; float *y2, *mean2, *rstd2, *x2; char* x2_t; };
+  auto bufs = [&](int l) {
+    LayerBufs u;
+    if (!saved) {
+      u = LayerBufs{w.x2, w.x2_t, w.qkv, w.ctx, nullptr, w.y1, w.mean1, w.rstd1, w.x1, w.x1_t, w.h, w.hpre, w.y2, w.mean2, w.rstd2, w.x2, w.x2_t};
+    } else {
+      const PredictLayerWs& k = sv.layer[l];
+      u = LayerBufs{l == 0 ? sv.x0 : sv.layer[l - 1].x2, l == 0 ? sv.x0_t : sv.layer[l - 1].x2_t, k.qkv, k.ctx, k.lse, k.y1, k.mean1, k.rstd1, sv.x1, sv.x1_t,
+                    sv.h, k.hpre, k.y2, k.mean2, k.rstd2, k.x2, k.x2_t};
+    }
+    return u;
+  };
+  float* x0 = saved ? sv.x0 : w.x2;
+  char* x0_t = saved ? sv.x0_t : w.x2_t;
   {  // the x embedding only: test rows carry no y
     EmbedArgs e; memset(&e, 0, sizeof(e));
     e.x = x; e.x_st = x_st; e.x_sb = x_sb; e.y = x; e.y_st = 0; e.y_sb = 0;      // (y is not read below sep = 0)
     e.wx = params + L.enc_w; e.bx = params + L.enc_b; e.wy = params + L.yenc_w; e.by = params + L.yenc_b;
-    e.out_f32 = w.x2; e.out_t = w.x2_t; e.S = n; e.B = B; e.nf = d->num_features; e.E = E; e.sep = 0;
+    e.out_f32 = x0; e.out_t = x0_t; e.S = n; e.B = B; e.nf = d->num_features; e.E = E; e.sep = 0;
     PFN_TRY(launch_embed_fwd(e, prec, s));
   }
   // the forward's fusion rules (stack_forward_impl) for the same descriptor and these rows
-  Ws probe_ws; probe_ws.x0 = w.x2; probe_ws.x0_t = w.x2_t;
+  Ws probe_ws; probe_ws.x0 = x0; probe_ws.x0_t = x0_t;
   const bool ln_ok = ln_gemm_probe(*d, probe_ws, params, sh, M);
   const bool fuse_ln = prec_is16(prec) && ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE));
   const bool y16 = residual16(*d) && ln_ok;
   const bool y16u = residual16_separate_ln(*d, ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE)));
   struct Resid { const float* plain; const void* y; const float* mean; const float* rstd; const float* gamma; const float* beta; };
-  Resid res = {w.x2, nullptr, nullptr, nullptr, nullptr, nullptr};
+  Resid res = {x0, nullptr, nullptr, nullptr, nullptr, nullptr};
   auto set_resid = [](GemmLN& g, const Resid& r) { g.resid = r.plain; g.ry = r.y; g.rmean = r.mean; g.rrstd = r.rstd; g.rgamma = r.gamma; g.rbeta = r.beta; };
+  float* xout = x0;      // the last layer's f32 output
   for (int l = 0; l < d->nlayers; ++l) {
     const LayerP& p = L.layer[l];
+    const LayerBufs u = bufs(l);
     const bool last = l == d->nlayers - 1;
     const char* kv = (const char*)context + l * c.layer_bytes;
     {  // packed q/k/v projection; the self keys shifted by the vector that centred the cached ones
-      GemmNT g = nt(w.x2_t, E, W(p.w_in), E, M, 3 * E, E, EPI_BIAS | EPI_OUT_T);
-      g.bias = params + p.b_in; g.out_t = w.qkv; g.ld_out_t = 3 * E;
+      GemmNT g = nt(u.xin_t, E, W(p.w_in), E, M, 3 * E, E, EPI_BIAS | EPI_OUT_T);
+      g.bias = params + p.b_in; g.out_t = u.qkv; g.ld_out_t = 3 * E;
       if (c.shift_bytes && sep > 0) {
         g.flags |= EPI_ROWSHIFT; g.rowshift = (const float*)(kv + c.kv_bytes); g.rs_ld = E; g.rs_S = n; g.rs_n0 = E; g.rs_n1 = 2 * E;
       }
@@ -730,61 +802,193 @@ int pfn_stack_predict(const pfn_model_desc* d, const float* params, const void* 
     }
     {
       AttnArgs at; memset(&at, 0, sizeof(at));
-      at.qkv = w.qkv; at.ctx = w.ctx; at.B = B; at.S = n; at.E = E; at.H = H; at.sep = sep;
-      at.kv = kv; at.kv_ld = 2L * E; at.kv_sb = (long)sep * 2 * E; at.part_o = w.part_o; at.part_ml = w.part_ml;
+      at.qkv = u.qkv; at.ctx = u.ctx; at.lse = u.lse; at.B = B; at.S = n; at.E = E; at.H = H; at.sep = sep;
+      at.kv = kv; at.kv_ld = 2L * E; at.kv_sb = (long)sep * 2 * E; at.part_o = saved ? sv.part_o : w.part_o; at.part_ml = saved ? sv.part_ml : w.part_ml;
       PFN_TRY(launch_attn_fwd_cache(at, prec, s));
     }
     if (fuse_ln) {  // x1 = LN1(x + out_proj(ctx))
       GemmLN g; memset(&g, 0, sizeof(g));
-      g.A = w.ctx; g.lda = E; g.B = W(p.w_o); g.ldb = E; g.M = M; g.N = E; g.K = E; g.bias = params + p.b_o;
+      g.A = u.ctx; g.lda = E; g.B = W(p.w_o); g.ldb = E; g.M = M; g.N = E; g.K = E; g.bias = params + p.b_o;
       set_resid(g, res);
       g.gamma = params + p.g1; g.beta = params + p.be1; g.eps = d->ln_eps;
-      g.y = w.y1; g.mean = w.mean1; g.rstd = w.rstd1; g.x_t = w.x1_t; g.y16 = y16;
+      g.y = u.y1; g.mean = u.mean1; g.rstd = u.rstd1; g.x_t = u.x1_t; g.y16 = y16;
       PFN_TRY(launch_gemm_ln(g, prec, s));
-      res = Resid{nullptr, w.y1, w.mean1, w.rstd1, params + p.g1, params + p.be1};
+      res = Resid{nullptr, u.y1, u.mean1, u.rstd1, params + p.g1, params + p.be1};
     } else {
-      GemmNT g = nt(w.ctx, E, W(p.w_o), E, M, E, E, EPI_BIAS | EPI_RESID | EPI_OUT_F32);
-      g.bias = params + p.b_o; g.resid = w.x2; g.ld_resid = E; g.out_f32 = w.y1; g.ld_out_f32 = E;
-      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = w.x2_t; g.ld_aux = E; g.out_t = w.y1; g.ld_out_t = E; }
+      GemmNT g = nt(u.ctx, E, W(p.w_o), E, M, E, E, EPI_BIAS | EPI_RESID | EPI_OUT_F32);
+      g.bias = params + p.b_o; g.resid = u.xin; g.ld_resid = E; g.out_f32 = u.y1; g.ld_out_f32 = E;
+      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = u.xin_t; g.ld_aux = E; g.out_t = u.y1; g.ld_out_t = E; }
       PFN_TRY(launch_gemm_nt(g, prec, s));
-      PFN_TRY(launch_layernorm_fwd(w.y1, params + p.g1, params + p.be1, y16u ? nullptr : w.x1, w.x1_t, w.mean1, w.rstd1, M, E, d->ln_eps, prec, s, y16u));
+      PFN_TRY(launch_layernorm_fwd(u.y1, params + p.g1, params + p.be1, y16u ? nullptr : u.x1, u.x1_t, u.mean1, u.rstd1, M, E, d->ln_eps, prec, s, y16u));
     }
     {  // linear1 + GELU
-      GemmNT g = nt(w.x1_t, E, W(p.w1), E, M, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
-      g.bias = params + p.b1; g.out_t = w.h; g.ld_out_t = F; g.out2_t = w.hpre; g.ld_out2 = F;
+      GemmNT g = nt(u.x1_t, E, W(p.w1), E, M, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
+      g.bias = params + p.b1; g.out_t = u.h; g.ld_out_t = F; g.out2_t = u.hpre; g.ld_out2 = F;
       PFN_TRY(launch_gemm_nt(g, prec, s));
     }
     if (fuse_ln) {  // x2 = LN2(x1 + linear2(h)), over the layer input (read by out_proj only)
       GemmLN g; memset(&g, 0, sizeof(g));
-      g.A = w.h; g.lda = F; g.B = W(p.w2); g.ldb = F; g.M = M; g.N = E; g.K = F; g.bias = params + p.b2;
+      g.A = u.h; g.lda = F; g.B = W(p.w2); g.ldb = F; g.M = M; g.N = E; g.K = F; g.bias = params + p.b2;
       set_resid(g, res);
       g.gamma = params + p.g2; g.beta = params + p.be2; g.eps = d->ln_eps;
-      g.y = w.y2; g.mean = w.mean2; g.rstd = w.rstd2; g.x_t = w.x2_t; g.y16 = y16;
-      g.x_f32 = last ? w.x2 : nullptr;
+      g.y = u.y2; g.mean = u.mean2; g.rstd = u.rstd2; g.x_t = u.x2_t; g.y16 = y16;
+      g.x_f32 = last ? u.x2 : nullptr;
       PFN_TRY(launch_gemm_ln(g, prec, s));
-      res = Resid{nullptr, w.y2, w.mean2, w.rstd2, params + p.g2, params + p.be2};
+      res = Resid{nullptr, u.y2, u.mean2, u.rstd2, params + p.g2, params + p.be2};
     } else {
-      GemmNT g = nt(w.h, F, W(p.w2), F, M, E, F, EPI_BIAS | EPI_RESID | EPI_OUT_F32);
-      g.bias = params + p.b2; g.resid = w.x1; g.ld_resid = E; g.out_f32 = w.y2; g.ld_out_f32 = E;
-      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = w.x1_t; g.ld_aux = E; g.out_t = w.y2; g.ld_out_t = E; }
+      GemmNT g = nt(u.h, F, W(p.w2), F, M, E, F, EPI_BIAS | EPI_RESID | EPI_OUT_F32);
+      g.bias = params + p.b2; g.resid = u.x1; g.ld_resid = E; g.out_f32 = u.y2; g.ld_out_f32 = E;
+      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = u.x1_t; g.ld_aux = E; g.out_t = u.y2; g.ld_out_t = E; }
       PFN_TRY(launch_gemm_nt(g, prec, s));
-      PFN_TRY(launch_layernorm_fwd(w.y2, params + p.g2, params + p.be2, (y16u && !last) ? nullptr : w.x2, w.x2_t, w.mean2, w.rstd2, M, E, d->ln_eps, prec, s, y16u));
+      PFN_TRY(launch_layernorm_fwd(u.y2, params + p.g2, params + p.be2, (y16u && !last) ? nullptr : u.x2, u.x2_t, u.mean2, u.rstd2, M, E, d->ln_eps, prec, s, y16u));
     }
+    xout = u.x2;
   }
   // [B, n] token order -> the caller's rows t B + b; then the decoder on them (set 1 and the q|k|v buffer are free now)
-  if (O == 0) return launch_gather_test_rows(w.x2, logits, n, B, E, 0, PFN_PREC_F32, s);
-  PFN_TRY(launch_gather_test_rows(w.x2, w.x1_t, n, B, E, 0, prec, s));
+  if (O == 0) return launch_gather_test_rows(xout, logits, n, B, E, 0, PFN_PREC_F32, s);
+  char* xt_t = saved ? sv.xt_t : w.x1_t;
+  char* dt = saved ? sv.dt : w.h;
+  char* dpre = saved ? sv.dpre : w.hpre;
+  PFN_TRY(launch_gather_test_rows(xout, xt_t, n, B, E, 0, prec, s));
   {
-    GemmNT g = nt(w.x1_t, E, W(L.dec0_w), E, M, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
-    g.bias = params + L.dec0_b; g.out_t = w.h; g.ld_out_t = F; g.out2_t = w.hpre; g.ld_out2 = F;
+    GemmNT g = nt(xt_t, E, W(L.dec0_w), E, M, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
+    g.bias = params + L.dec0_b; g.out_t = dt; g.ld_out_t = F; g.out2_t = dpre; g.ld_out2 = F;
     PFN_TRY(launch_gemm_nt(g, prec, s));
   }
   {
-    GemmNT g = nt(w.h, F, W(L.dec2_w), F, M, O, F, EPI_BIAS | EPI_OUT_F32);
+    GemmNT g = nt(dt, F, W(L.dec2_w), F, M, O, F, EPI_BIAS | EPI_OUT_F32);
     g.bias = params + L.dec2_b; g.out_f32 = logits; g.ld_out_f32 = O;
     PFN_TRY(launch_gemm_nt(g, prec, s));
   }
   return PFN_OK;
+}
+int pfn_stack_predict(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep,
+                      const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes, float* logits, void* stream) {
+  return stack_predict_impl(d, params, shadow, context, context_bytes, sep, x, x_st, x_sb, B, n, workspace, workspace_bytes, logits, stream, false);
+}
+int pfn_stack_predict_saved(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep,
+                            const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes, float* logits, void* stream) {
+  return stack_predict_impl(d, params, shadow, context, context_bytes, sep, x, x_st, x_sb, B, n, workspace, workspace_bytes, logits, stream, true);
+}
+
+// d(x_test) of a saved predict pass: the data-gradient chain of stack_backward_impl on the B n test rows -- decoder, then every layer's LN2 backward, d(hpre), LN1
+// backward, d(ctx), the cached-attention backward (launch_attn_bwd_cache) and dx -- with no weight-gradient launch; the LayerNorm kernels' parameter sums go to a sink
+// in the workspace.  The context and every parameter stay untouched.
+int pfn_stack_predict_backward(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep, int B, int n,
+                               void* workspace, int64_t workspace_bytes, const float* dlogits, float* dx, int64_t dx_st, int64_t dx_sb, void* stream) {
+  PFN_TRY(check_desc(d));
+  if (B < 1 || n < 0 || sep < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d n=%d sep=%d", B, n, sep);
+  const Context c = context_layout(*d, B, sep);
+  if (sep > 0 && d->nlayers > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context with sep=%d", sep);
+  if (context_bytes < c.bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)c.bytes);
+  if (!params || !shadow || !workspace || (n > 0 && (!dlogits || !dx))) return fail(PFN_ERR_ARGUMENT, "null pointer");
+  PredictGradWs w = carve_predict_grad(*d, B, n, (char*)workspace);
+  if (workspace_bytes < w.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)w.bytes);
+  if (n == 0) return PFN_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int prec = d->precision, es = esize(prec);
+  const int E = d->emsize, F = d->nhid, H = d->nhead, O = d->n_out, M = B * n;
+  Layout L = make_layout(*d);
+  const int npad = L.n_out_pad;
+  const char* sh = (const char*)shadow;
+  auto WT = [&](int64_t off) { return (const void*)(sh + (L.total + off) * es); };
+  // the forward's layout decisions (stack_predict_impl), and the training backward's for the LayerNorm backward
+  Ws probe_ws; probe_ws.x0 = w.x0; probe_ws.x0_t = w.x0_t;
+  const bool ln_ok = ln_gemm_probe(*d, probe_ws, params, sh, M);
+  const bool y16 = (residual16(*d) && ln_ok) || residual16_separate_ln(*d, ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE)));
+  float* sg = w.sink;                      // dgamma | dbeta | dbias sums nobody reads
+  float *sb = w.sink + E, *sx = w.sink + 2 * E;
+  const float* lsc = nullptr;
+  if (prec == PFN_PREC_FP16) {      // the training backward's loss scale: the chain runs on dlogits * 2^k, dx leaves without it
+    PFN_TRY(launch_absmax(dlogits, (long)M * (O > 0 ? O : E), w.lscale, s));
+    lsc = w.lscale;
+  }
+  // ---- decoder: d(test rows) [M, E] f32 in the caller's row order t B + b ----
+  const float* dxt = dlogits;
+  if (O == 0) {
+    if (lsc) { PFN_TRY(launch_scale_copy(dlogits, w.dxt, (long)M * E, lsc, s)); dxt = w.dxt; }
+  } else {
+    PFN_TRY(launch_cast_rows(dlogits, O, w.dlog_t, npad, M, O, prec, s, lsc));
+    {
+      GemmNT g = nt(w.dlog_t, npad, WT(L.dec2_wt), npad, M, F, npad % 64 == 0 ? npad : O, EPI_GELU_BWD | EPI_OUT_T);
+      g.aux = w.dpre; g.ld_aux = F; g.out_t = w.dd_t; g.ld_out_t = F;
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+    }
+    {
+      GemmNT g = nt(w.dd_t, F, WT(L.dec0_wt), F, M, E, F, EPI_OUT_F32);
+      g.out_f32 = w.dxt; g.ld_out_f32 = E;
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+    }
+    dxt = w.dxt;
+  }
+  // -> [B, n] token order, f32 (the top layer's LN2 backward reads it as it is)
+  PFN_TRY(launch_scatter_test_rows(dxt, w.gA, n, B, E, 0, PFN_PREC_F32, s));
+  auto lnb = [&](const void* A, long lda, const void* Bw, long ldb, int K, const void* aux, const void* y, const float* mean, const float* rstd,
+                 const float* gamma, void* dx_t) {
+    GemmLNB g; memset(&g, 0, sizeof(g));
+    g.A = A; g.lda = lda; g.B = Bw; g.ldb = ldb; g.M = M; g.N = E; g.K = K; g.aux = aux;
+    g.y = y; g.mean = mean; g.rstd = rstd; g.gamma = gamma; g.dx_t = dx_t; g.dgamma = sg; g.dbeta = sb; g.scale_amax = lsc; g.y16 = y16;
+    return g;
+  };
+  bool fuse_lnb = !(d->schedule & PFN_SCHED_DETERMINISTIC) && !(d->schedule & PFN_SCHED_SEPARATE_LNBWD) && prec_is16(prec) && d->nlayers > 0 &&
+                  (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE));
+  if (fuse_lnb) {
+    const LayerP& p = L.layer[0]; const LayerP& t = L.layer_t[0]; const PredictLayerWs& a = w.layer[0];
+    fuse_lnb = gemm_lnbwd_supported(lnb(w.dh_t, F, WT(t.w1), F, F, w.dy2_t, a.y1, a.mean1, a.rstd1, params + p.g1, w.dy1_t)) &&
+               gemm_lnbwd_supported(lnb(w.dqkv_t, 3 * E, WT(t.w_in), 3 * E, 3 * E, w.dy1_t, a.y2, a.mean2, a.rstd2, params + p.g2, w.dy2_t));
+  }
+  const bool last_t = d->nlayers == 0 || prec_is16(prec);      // the embedding's gradient: operand precision from a 16-bit chain (gA_t), else f32 (gA)
+  for (int l = d->nlayers - 1; l >= 0; --l) {
+    const LayerP &p = L.layer[l], &t = L.layer_t[l];
+    const PredictLayerWs& a = w.layer[l];
+    const char* kv = (const char*)context + l * c.layer_bytes;
+    if (!fuse_lnb || l == d->nlayers - 1)      // LN2: from gA (f32, the top layer) or gA_t (operand precision, the layer above's dx)
+      PFN_TRY(launch_layernorm_bwd(l == d->nlayers - 1 ? (const void*)w.gA : (const void*)w.gA_t, l == d->nlayers - 1 ? 0 : 1, a.y2, params + p.g2, a.mean2, a.rstd2,
+                                   nullptr, w.dy2_t, sg, sb, sx, M, E, prec, s, nullptr, lsc, y16));
+    {  // d(hpre) = (dy2 . W2) * gelu'(hpre)
+      GemmNT g = nt(w.dy2_t, E, WT(t.w2), E, M, F, E, EPI_GELU_BWD | EPI_OUT_T);
+      g.aux = a.hpre; g.ld_aux = F; g.out_t = w.dh_t; g.ld_out_t = F;
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+    }
+    if (fuse_lnb) {  // dy1 = LN1 backward of (dh . W1 + dy2)
+      PFN_TRY(launch_gemm_lnbwd(lnb(w.dh_t, F, WT(t.w1), F, F, w.dy2_t, a.y1, a.mean1, a.rstd1, params + p.g1, w.dy1_t), prec, s));
+    } else {
+      {  // dx1 = dh . W1 + dy2
+        GemmNT g = nt(w.dh_t, F, WT(t.w1), F, M, E, F, EPI_RESID_T | EPI_OUT_T);
+        g.aux = w.dy2_t; g.ld_aux = E; g.out_t = w.gA_t; g.ld_out_t = E;
+        PFN_TRY(launch_gemm_nt(g, prec, s));
+      }
+      PFN_TRY(launch_layernorm_bwd(w.gA_t, 1, a.y1, params + p.g1, a.mean1, a.rstd1, nullptr, w.dy1_t, sg, sb, sx, M, E, prec, s, nullptr, lsc, y16));
+    }
+    {  // d(ctx) = dy1 . Wo
+      GemmNT g = nt(w.dy1_t, E, WT(t.w_o), E, M, E, E, EPI_OUT_T);
+      g.out_t = w.dctx_t; g.ld_out_t = E;
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+    }
+    {
+      AttnCacheBwdArgs at; memset(&at, 0, sizeof(at));
+      at.qkv = a.qkv; at.ctx = a.ctx; at.lse = a.lse; at.dctx = w.dctx_t; at.dqkv = w.dqkv_t;
+      at.kv = kv; at.kv_ld = 2L * E; at.kv_sb = (long)sep * 2 * E; at.part_dq = w.part_o;
+      at.B = B; at.S = n; at.E = E; at.H = H; at.sep = sep;
+      PFN_TRY(launch_attn_bwd_cache(at, prec, s));
+    }
+    if (fuse_lnb && l > 0) {  // dy2 of the layer below = its LN2 backward of (dqkv . Win + dy1)
+      const LayerP& pb = L.layer[l - 1];
+      const PredictLayerWs& ab = w.layer[l - 1];
+      PFN_TRY(launch_gemm_lnbwd(lnb(w.dqkv_t, 3 * E, WT(t.w_in), 3 * E, 3 * E, w.dy1_t, ab.y2, ab.mean2, ab.rstd2, params + pb.g2, w.dy2_t), prec, s));
+    } else {  // dx = dqkv . Win + dy1
+      GemmNT g = nt(w.dqkv_t, 3 * E, WT(t.w_in), 3 * E, M, E, 3 * E, EPI_RESID_T | (l == 0 && !last_t ? EPI_OUT_F32 : EPI_OUT_T));
+      g.aux = w.dy1_t; g.ld_aux = E; g.out_f32 = w.gA; g.ld_out_f32 = E; g.out_t = w.gA_t; g.ld_out_t = E;
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+    }
+  }
+  // ---- embedding: dx = d(src) . W_enc ----
+  EmbedInGradArgs e; memset(&e, 0, sizeof(e));
+  const bool from_t = d->nlayers > 0 && last_t;
+  e.dsrc = from_t ? (const void*)w.gA_t : (const void*)w.gA; e.dsrc_prec = from_t ? prec : PFN_PREC_F32;
+  e.wx = params + L.enc_w; e.wy = params + L.yenc_w; e.dx = dx; e.dx_st = dx_st; e.dx_sb = dx_sb; e.dy = nullptr;
+  e.S = n; e.B = B; e.nf = d->num_features; e.E = E; e.sep = 0; e.scale_amax = lsc;
+  return launch_embed_input_grad(e, s);
 }
 
 int pfn_stack_backward_ragged(const pfn_model_desc* d, const float* params, const void* shadow,
@@ -1084,6 +1288,38 @@ static int stack_backward_impl(const pfn_model_desc* d, const float* params, con
     e.S = S; e.B = B; e.nf = d->num_features; e.E = E; e.sep = sep; e.sep_of = sep_of; e.single_block = det ? 1 : 0; e.scale_amax = lsc;
     PFN_TRY(launch_embed_bwd(e, s));
   }
+  return PFN_OK;
+}
+
+// d(x) [S, B, F] and d(y) [S, B] of a fused-embedding forward, after pfn_stack_backward / _split on the same workspace: the backward leaves d(src) -- the gradient
+// of the embedding output -- in gA_t (operand precision, loss-scaled: the embedding's weight gradients ran as a GEMM) or in gA (f32), by the rule it used (emb_gemm).
+int pfn_stack_input_grads(const pfn_model_desc* d, const float* params, int B, int S, int sep, const void* workspace, int64_t workspace_bytes,
+                          float* dx, int64_t dx_st, int64_t dx_sb, float* dy, int64_t dy_st, int64_t dy_sb, void* stream) {
+  PFN_TRY(check_desc(d));
+  if (B < 1 || S < 1 || sep < 0 || sep > S) return fail(PFN_ERR_ARGUMENT, "bad B=%d S=%d sep=%d", B, S, sep);
+  if (!params || !workspace || !dx) return fail(PFN_ERR_ARGUMENT, "null pointer");
+  Ws w = carve(*d, B, S, (char*)workspace);
+  if (workspace_bytes < w.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)w.bytes);
+  const int prec = d->precision, E = d->emsize;
+  const Layout L = make_layout(*d);
+  hipStream_t s = (hipStream_t)stream;
+  const bool emb_gemm = prec_is16(prec) && d->nlayers > 0 && emb_aug_width(d->num_features) > 0 && E % 8 == 0;      // (stack_backward_impl, fused embedding)
+  EmbedInGradArgs e; memset(&e, 0, sizeof(e));
+  e.dsrc = emb_gemm ? (const void*)w.gA_t : (const void*)w.gA; e.dsrc_prec = emb_gemm ? prec : PFN_PREC_F32;
+  e.wx = params + L.enc_w; e.wy = params + L.yenc_w;
+  e.dx = dx; e.dx_st = dx_st; e.dx_sb = dx_sb; e.dy = dy; e.dy_st = dy_st; e.dy_sb = dy_sb;
+  e.S = S; e.B = B; e.nf = d->num_features; e.E = E; e.sep = sep;
+  e.scale_amax = (prec == PFN_PREC_FP16 && sep < S) ? w.lscale : nullptr;
+  return launch_embed_input_grad(e, s);
+}
+
+int pfn_bar_mean_backward(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support, const float* mean, const float* gout,
+                          float* dlogits, void* stream) {
+  if (R < 0 || nbars < 1 || (R > 0 && (!logits || !borders || !mean || !gout || !dlogits))) return fail(PFN_ERR_ARGUMENT, "bad bar_mean_backward arguments");
+  BarArgs a; memset(&a, 0, sizeof(a));
+  a.logits = logits; a.ld = ld; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support;
+  a.mean_out = const_cast<float*>(mean); a.gout = gout; a.dlogits = dlogits;
+  PFN_TRY(launch_bar_mean_bwd(a, (hipStream_t)stream));
   return PFN_OK;
 }
 

@@ -255,6 +255,20 @@ struct AttnArgs {
 int attn_cache_splits(int B, int n, int E, int H, int sep, int precision);
 int launch_attn_fwd_cache(const AttnArgs& a, int precision, hipStream_t stream);
 void set_attn_cache_split_cap(int splits);      // PFN_TUNE_ATTN_CACHE_SPLITS: 0 = the rule, k > 0 = at most k splits
+// Backward of a predict pass's attention w.r.t. the test rows' q | k | v (pfn_stack_predict_backward): the cached keys and values are constants, so nothing
+// flows into the context.  S = n test rows per dataset, `sep` cached keys; the splits of the key range follow attn_cache_splits (as the forward's).
+struct AttnCacheBwdArgs {
+  const void* qkv;        // [B, n, 3E] T: the test rows' q | k | v (forward)
+  const void* ctx;        // [B, n, E] T: the attention output O (forward)
+  const float* lse;       // [B, H, n] f32: its log-sum-exp (natural units; launch_attn_fwd_cache with AttnArgs::lse)
+  const void* dctx;       // [B, n, E] T: dO
+  void* dqkv;             // [B, n, 3E] T: out
+  const void* kv; long kv_ld, kv_sb;      // the context's K | V rows of this layer (AttnArgs' predict fields)
+  float* part_dq;         // more than one split: [nsplit, B, n, E] f32 partial dQ (unscaled), summed in split order by the merge kernel
+  int B, S, E, H, sep;
+  int split_keys;         // filled by the launcher
+};
+int launch_attn_bwd_cache(const AttnCacheBwdArgs& a, int precision, hipStream_t stream);
 void set_attn_pingpong(int mask);
 void set_attn_bwd_group(int datasets);      // 0 = all datasets of a call in one launch pair
 enum : int { ATTN_BWD_DELTA = 1, ATTN_BWD_KV = 2, ATTN_BWD_DQ = 4 };
@@ -325,6 +339,16 @@ int launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s);
 // the GEMM form: acc[E, aug] = d(src)^T . xaug (launch_gemm_tn), aug = emb_aug_width(nf) -> dwx += acc[:, :nf], dwy += acc[:, nf], dby += acc[:, nf + 1]
 // (xaug_amax: the column scales of xaug_t, multiplied back out; nullptr = none)
 int launch_embed_grad_scatter(const float* acc, float* dwx, float* dwy, float* dby, int E, int nf, const float* xaug_amax, hipStream_t s);
+// input gradients of the fused embedding: dx[t, b, :] = d(src)[b S + t] . W_enc ([E] x [E, nf]) and, for t < sep, dy[t, b] = d(src)[b S + t] . w_y (0 for t >= sep)
+struct EmbedInGradArgs {
+  const void* dsrc; int dsrc_prec;       // [B S, E] rows b S + t: f32 (PFN_PREC_F32) or operand precision
+  const float* wx; const float* wy;      // encoder.weight [E, nf], y_encoder.weight [E]
+  float* dx; long dx_st, dx_sb;          // [S, B, nf] (strides in elements)
+  float* dy; long dy_st, dy_sb;          // nullptr: no y gradient
+  int S, B, nf, E, sep;
+  const float* scale_amax;               // fp16 backward: d(src) carries the loss scale, dx / dy leave without it (nullptr = none)
+};
+int launch_embed_input_grad(const EmbedInGradArgs& a, hipStream_t s);
 
 // src given in the reference layout [S,B,E] f32 (custom encoders): copy into [B,S,E] f32 + T
 int launch_sbe_to_bse(const float* src, float* out_f32, void* out_t, int S, int B, int E, int precision, hipStream_t s);
@@ -386,6 +410,7 @@ struct BarArgs {
 int launch_bar_nll_fwd(const BarArgs& a, hipStream_t s);
 int launch_bar_nll_bwd(const BarArgs& a, hipStream_t s);
 int launch_bar_mean(const BarArgs& a, hipStream_t s);
+int launch_bar_mean_bwd(const BarArgs& a, hipStream_t s);      // dlogits = gout p (c - mean): mean_out holds the forward's means (read only)
 
 // ---- optimizer (optim.hip) ----------------------------------------------------------------------
 struct AdamArgs {

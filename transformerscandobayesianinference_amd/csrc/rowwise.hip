@@ -483,6 +483,72 @@ int launch_embed_grad_scatter(const float* acc, float* dwx, float* dwy, float* d
   hipLaunchKernelGGL(embed_grad_scatter_kernel, dim3((E * (nf + 2) + 255) / 256), dim3(256), 0, s, acc, dwx, dwy, dby, E, nf, xaug_amax);
   return PFN_LAUNCH_OK();
 }
+// Input gradients of the fused embedding (pfn_stack_input_grads, pfn_stack_predict_backward): a workgroup stages the d(src) rows of R tokens in LDS (f32, loss scale
+// removed), then W_enc in chunks of fc columns, transposed (row stride E + 1: conflict-free on both sides), and 16-lane groups form the (token, feature) dots.
+// d(src) is read once; W_enc (at most 2 MB) once per R tokens from L2.
+__global__ __launch_bounds__(256) void embed_input_grad_kernel(EmbedInGradArgs a, int R, int fc) {
+  extern __shared__ float eig_sm[];
+  float* ds = eig_sm;                  // [R, E]
+  float* wt = eig_sm + (long)R * a.E;  // [fc, E + 1]
+  const int E = a.E, WS = E + 1;
+  const long M = (long)a.B * a.S, m0 = (long)blockIdx.x * R;
+  const int nr = (int)std::min<long>(R, M - m0);
+  const float osc = loss_scale_down(a.scale_amax);
+  for (int i = threadIdx.x; i < nr * E; i += 256) {
+    const long k = m0 * E + i;
+    float v;
+    if (a.dsrc_prec == PFN_PREC_F32) v = reinterpret_cast<const float*>(a.dsrc)[k];
+    else if (a.dsrc_prec == PFN_PREC_BF16) v = (float)reinterpret_cast<const bf16*>(a.dsrc)[k];
+    else v = (float)reinterpret_cast<const f16*>(a.dsrc)[k];
+    ds[i] = v * osc;
+  }
+  __syncthreads();
+  const int g = threadIdx.x >> 4, l16 = threadIdx.x & 15;
+  auto sum16 = [](float v) {
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+  };
+  if (a.dy) {
+    for (int r = g; r < nr; r += 16) {
+      const long m = m0 + r, b = m / a.S, t = m % a.S;
+      float v = 0.f;
+      if (t < a.sep)
+        for (int e = l16; e < E; e += 16) v += ds[r * E + e] * a.wy[e];
+      v = sum16(v);
+      if (l16 == 0) a.dy[t * a.dy_st + b * a.dy_sb] = v;
+    }
+  }
+  for (int f0 = 0; f0 < a.nf; f0 += fc) {
+    const int nfc = min(fc, a.nf - f0);
+    __syncthreads();      // (the previous chunk's readers are done)
+    for (int i = threadIdx.x; i < nfc * E; i += 256) {
+      const int e = i / nfc, j = i - e * nfc;
+      wt[j * WS + e] = a.wx[(long)e * a.nf + f0 + j];
+    }
+    __syncthreads();
+    for (int p = g; p < nr * nfc; p += 16) {
+      const int r = p / nfc, j = p - r * nfc;
+      float v = 0.f;
+      for (int e = l16; e < E; e += 16) v += ds[r * E + e] * wt[j * WS + e];
+      v = sum16(v);
+      const long m = m0 + r, b = m / a.S, t = m % a.S;
+      if (l16 == 0) a.dx[t * a.dx_st + b * a.dx_sb + f0 + j] = v;
+    }
+  }
+}
+int launch_embed_input_grad(const EmbedInGradArgs& a, hipStream_t s) {
+  const long M = (long)a.B * a.S;
+  if (M == 0) return PFN_OK;
+  if (!a.dsrc || !a.wx || !a.dx || (a.dy && !a.wy) || a.E < 1 || a.nf < 1) return PFN_ERR_ARGUMENT;
+  const int R = std::max(4, std::min(64, 16384 / a.E));                  // d(src) rows: <= 64 KB
+  const int fc = std::max(1, std::min(a.nf, 8192 / (a.E + 1)));         // W_enc columns per chunk: <= 32 KB
+  const size_t lds = ((size_t)R * a.E + (size_t)fc * (a.E + 1)) * sizeof(float);
+  static LdsAllowance allowance;
+  allowance.ensure(embed_input_grad_kernel, lds);
+  hipLaunchKernelGGL(embed_input_grad_kernel, dim3((unsigned)((M + R - 1) / R)), dim3(256), lds, s, a, R, fc);
+  return PFN_LAUNCH_OK();
+}
 int launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s) {
   const long ntok = (long)a.B * a.S;
   const int nf8 = (a.nf + 2 + 7) / 8 * 8;

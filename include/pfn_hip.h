@@ -309,6 +309,41 @@ int pfn_bar_mean(const float* logits, int64_t ld, const float* borders, int64_t 
 int pfn_bar_mean_backward(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
                           const float* mean, const float* gout, float* dlogits, void* stream);
 
+/* ---- posterior summaries and draws (ABI 10, additive: a binding detects them by symbol).  pfn_bar_stats generalises
+ * BarDistribution.quantile / mode / ei (bar_distribution.py:40-80) and adds variance, CDF and an inverse CDF at any level; one pass
+ * over each logits row computes K <= PFN_BAR_STATS_MAX of them, no [R, nbars] intermediate.  The definitions (conditional bucket CDF
+ * with the half-normal tails of the full-support class, variance, gradients) are in the header of this section of csrc/bar.hip.
+ *   kinds: HOST array of K PFN_BAR_STAT_* values.
+ *   args: DEVICE, one float per statistic -- y for CDF, the level u for ICDF, best_f for EI_MAX / EI_MIN, ignored for MEAN / VARIANCE / MODE.
+ *     arg_ld == 0: K values shared by all rows; otherwise [R, arg_ld] with arg_ld >= K (a best_f per dataset, a target per row).
+ *   MODE (bar_distribution.py:64-67): midpoint of the bucket with the largest logit, lowest index on ties, plain midpoint in the tails; zero gradient.
+ *   EI_MAX / EI_MIN (bar_distribution.py:69-80): the reference formula for both classes -- the outer buckets count as [b_0, b_1] and [b_{n-1}, b_n].
+ *   ICDF (generalises bar_distribution.py:40-62): linear inside a bucket, the half-normal tails inverted for full support; u <= 0 gives b_0 / -inf, u >= 1 b_n / +inf.
+ *   out [R, K] f32.  The arguments are not differentiated.
+ * pfn_bar_stats_backward: dlogits[r, :] (row stride ld) = sum_k gout[r, k] d out[r, k] / d logits[r, :], one read of the row and one write; `out` is what
+ *   the forward returned for the same arguments.
+ * pfn_bar_sample: out[s, r] = ICDF_r(u(seed, r, s)), s < n_samples, with
+ *     a = mix32(lo32(seed) ^ lo32(r) * 0x9E3779B1), b = mix32(a ^ hi32(seed) ^ hi32(r) * 0x85EBCA77), h = mix32(b ^ s * 0xC2B2AE35), u = ((h >> 9) + 0.5) * 2^-23
+ *   (mix32: h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16; products modulo 2^32): a function of (seed, row, draw) only,
+ *   bit-identical to the ICDF statistic at the same u.  No cap on nbars.
+ * PFN_ERR_ARGUMENT before anything is launched: NULL pointers, K outside 1 .. 16, an unknown kind, nbars < 1 (< 2 with full_support), ld < nbars,
+ *   0 < arg_ld < K, R < 0, n_samples < 0.  R == 0 or n_samples == 0: PFN_OK, nothing launched. */
+#define PFN_BAR_STATS_MAX 16
+#define PFN_BAR_STAT_MEAN 0
+#define PFN_BAR_STAT_VARIANCE 1
+#define PFN_BAR_STAT_MODE 2
+#define PFN_BAR_STAT_CDF 3
+#define PFN_BAR_STAT_ICDF 4
+#define PFN_BAR_STAT_EI_MAX 5
+#define PFN_BAR_STAT_EI_MIN 6
+int pfn_bar_stats(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                  const int32_t* kinds, int K, const float* args, int64_t arg_ld, float* out, void* stream);
+int pfn_bar_stats_backward(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                           const int32_t* kinds, int K, const float* args, int64_t arg_ld, const float* out, const float* gout,
+                           float* dlogits, void* stream);
+int pfn_bar_sample(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                   int n_samples, uint64_t seed, float* out, void* stream);
+
 /* ---- optimizer: replaces clip_grad_norm_(params, 1.) + Adam.step() + zero_grad()
  * (train.py:55,95-97).  One fused pass over the flat buffers; the clip coefficient is computed on
  * the device (no host sync).  grad_scale multiplies g first (1/world for DP averaging).

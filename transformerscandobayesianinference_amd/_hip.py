@@ -88,6 +88,12 @@ SIGNATURES = {
     'pfn_bar_mean': (_I, [_P, _L, _P, _L, _I, _I, _P, _P]),
     # (logits, ld, borders, R, nbars, full_support, mean, gout, dlogits, stream)
     'pfn_bar_mean_backward': (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _P, _P]),
+    # (logits, ld, borders, R, nbars, full_support, kinds [host int32], K, args, arg_ld, out, stream)      -- ABI 10, additive
+    'pfn_bar_stats': (_I, [_P, _L, _P, _L, _I, _I, _P, _I, _P, _L, _P, _P]),
+    # (logits, ld, borders, R, nbars, full_support, kinds, K, args, arg_ld, out, gout, dlogits, stream)
+    'pfn_bar_stats_backward': (_I, [_P, _L, _P, _L, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P]),
+    # (logits, ld, borders, R, nbars, full_support, n_samples, seed, out, stream)
+    'pfn_bar_sample': (_I, [_P, _L, _P, _L, _I, _I, _I, _U64, _P, _P]),
     'pfn_clip_adam_step': (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P]),
     'pfn_gp_workspace_bytes': (_L, [_I, _I]),
     'pfn_gp_prior_sample': (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P, _P]),

@@ -4,6 +4,11 @@
 :35-38 / :110-117) run in fused HIP kernels (csrc/bar.hip) through the C ABI; the evaluation-only
 helpers (`quantile`, `mode`, `ei`) and the one-off border construction `get_bucket_limits` are
 PyTorch plumbing exactly as in the reference.  The loss kernels have no CPU fallback.
+
+`stats` computes any set of posterior summaries (mean, variance, mode, CDF, inverse CDF, expected
+improvement) in one fused pass per logits row, differentiable in the logits; `variance`, `cdf`,
+`icdf`, `median`, `pi`, `ucb` are thin wrappers, and `sample` draws from the predictive distribution
+through the same inverse CDF (pfn_bar_stats / pfn_bar_stats_backward / pfn_bar_sample).  GPU only.
 """
 import torch
 from torch import nn
@@ -75,6 +80,104 @@ def _bar_mean(logits, borders, full_support):
     return _BarMeanFunction.apply(flat, borders, full_support).view(shape)
 
 
+STAT_MEAN, STAT_VARIANCE, STAT_MODE, STAT_CDF, STAT_ICDF, STAT_EI_MAX, STAT_EI_MIN = range(7)      # PFN_BAR_STAT_* (include/pfn_hip.h)
+MAX_STATS = 16                                                                                    # PFN_BAR_STATS_MAX
+_STAT_KINDS = {'mean': STAT_MEAN, 'variance': STAT_VARIANCE, 'mode': STAT_MODE, 'cdf': STAT_CDF, 'icdf': STAT_ICDF,
+               'ei': STAT_EI_MAX, 'ei_max': STAT_EI_MAX, 'ei_min': STAT_EI_MIN}
+_STAT_NO_ARG = (STAT_MEAN, STAT_VARIANCE, STAT_MODE)
+_SHARED_ARGS = {}
+
+
+class _BarStatsFunction(torch.autograd.Function):
+    """out[r, k] = statistic kinds[k] of row r (pfn_bar_stats); backward pfn_bar_stats_backward.  Differentiable in the logits only."""
+
+    @staticmethod
+    def forward(ctx, flat, borders, full_support, kinds, args, arg_ld):
+        import ctypes
+        R, nbars = flat.shape
+        K = len(kinds)
+        ckinds = (ctypes.c_int32 * K)(*kinds)
+        out = torch.empty(R, K, device=flat.device, dtype=torch.float32)
+        _hip.check(_hip.lib().pfn_bar_stats(flat.data_ptr(), nbars, borders.data_ptr(), R, nbars, int(full_support), ctypes.addressof(ckinds), K,
+                                            args.data_ptr(), arg_ld, out.data_ptr(), _hip.stream_ptr(flat.device)), 'pfn_bar_stats')
+        ctx.save_for_backward(flat, borders, args, out)
+        ctx.spec = (full_support, tuple(kinds), arg_ld)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        import ctypes
+        flat, borders, args, out = ctx.saved_tensors
+        full_support, kinds, arg_ld = ctx.spec
+        R, nbars = flat.shape
+        K = len(kinds)
+        ckinds = (ctypes.c_int32 * K)(*kinds)
+        gout = gout.contiguous().float()
+        dlogits = torch.empty_like(flat)
+        _hip.check(_hip.lib().pfn_bar_stats_backward(flat.data_ptr(), nbars, borders.data_ptr(), R, nbars, int(full_support), ctypes.addressof(ckinds), K,
+                                                     args.data_ptr(), arg_ld, out.data_ptr(), gout.data_ptr(), dlogits.data_ptr(),
+                                                     _hip.stream_ptr(flat.device)), 'pfn_bar_stats_backward')
+        return dlogits, None, None, None, None, None
+
+
+def _bar_stats(logits, borders, full_support, spec):
+    _hip.require_gpu_tensor(logits, 'logits')
+    spec = [(s,) if isinstance(s, str) else tuple(s) for s in spec]
+    if not 1 <= len(spec) <= MAX_STATS:
+        raise ValueError(f'stats: {len(spec)} statistics requested, 1 .. {MAX_STATS} per call')
+    shape = logits.shape[:-1]
+    flat = logits.reshape(-1, logits.shape[-1]).contiguous().float()
+    R = flat.shape[0]
+    kinds, vals = [], []
+    for s in spec:
+        name = s[0]
+        if name not in _STAT_KINDS:
+            raise ValueError(f'stats: unknown statistic {name!r} (one of {sorted(_STAT_KINDS)})')
+        kind = _STAT_KINDS[name]
+        rest = s[1:]
+        if name == 'ei' and len(rest) == 2:      # ('ei', best_f, maximize)
+            kind = STAT_EI_MAX if rest[1] else STAT_EI_MIN
+            rest = rest[:1]
+        if len(rest) != (0 if kind in _STAT_NO_ARG else 1):
+            raise ValueError(f'stats: {s!r} takes {"no" if kind in _STAT_NO_ARG else "one"} argument')
+        v = rest[0] if rest else 0.
+        if torch.is_tensor(v) and v.requires_grad:
+            raise ValueError(f'stats: the argument of {name!r} requires grad; the statistics are differentiable in the logits only')
+        kinds.append(kind)
+        vals.append(v)
+    if any(torch.is_tensor(v) and v.numel() > 1 for v in vals):      # per-row arguments: [R, K]
+        cols = [torch.broadcast_to(torch.as_tensor(v, dtype=torch.float32, device=flat.device), shape).reshape(-1) for v in vals]
+        args, arg_ld = torch.stack(cols, -1).contiguous(), len(vals)
+    else:      # K values shared by all rows: the device copy is kept, an evaluation loop passes the same ones again and again
+        key = (tuple(float(v) for v in vals), flat.device)
+        args, arg_ld = _SHARED_ARGS.get(key), 0
+        if args is None:
+            if len(_SHARED_ARGS) >= 256:
+                _SHARED_ARGS.clear()
+            args = _SHARED_ARGS[key] = torch.tensor(key[0], dtype=torch.float32).to(flat.device)
+    if R == 0:
+        return flat.new_empty(*shape, len(kinds))
+    borders = borders.detach().contiguous().float().to(flat.device)
+    return _BarStatsFunction.apply(flat, borders, full_support, kinds, args, arg_ld).view(*shape, len(kinds))
+
+
+def _bar_sample(logits, borders, full_support, n, seed):
+    _hip.require_gpu_tensor(logits, 'logits')
+    if n < 0:
+        raise ValueError(f'sample: n = {n}')
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # from torch's (CPU) generator: torch.manual_seed makes the draws repeatable
+    shape = logits.shape[:-1]
+    flat = logits.detach().reshape(-1, logits.shape[-1]).contiguous().float()
+    R = flat.shape[0]
+    out = torch.empty(n, R, device=flat.device, dtype=torch.float32)
+    if n > 0 and R > 0:
+        borders = borders.detach().contiguous().float().to(flat.device)
+        _hip.check(_hip.lib().pfn_bar_sample(flat.data_ptr(), flat.shape[1], borders.data_ptr(), R, flat.shape[1], int(full_support), n,
+                                             int(seed) & (2 ** 64 - 1), out.data_ptr(), _hip.stream_ptr(flat.device)), 'pfn_bar_sample')
+    return out.view(n, *shape)
+
+
 class BarDistribution(nn.Module):
     """Piecewise-constant density over sorted `borders` (min, ..., max); bucket k is (b_k, b_{k+1}].
 
@@ -112,9 +215,48 @@ class BarDistribution(nn.Module):
     def mean(self, logits):
         return _bar_mean(logits, self.borders, self._full_support)
 
+    def stats(self, logits, spec):
+        """Several posterior summaries in one fused pass over each logits row (pfn_bar_stats; GPU only, like `mean`): [..., K].
+        `spec` lists up to 16 statistics: ('mean',), ('variance',), ('mode',), ('cdf', y), ('icdf', u), ('ei', best_f[, maximize]),
+        ('ei_max', best_f), ('ei_min', best_f).  An argument is a Python float or a tensor broadcastable to logits.shape[:-1] (a best_f
+        per dataset, a target per row).  Differentiable in the logits only (pfn_bar_stats_backward); an argument that requires grad raises.
+        The definitions -- half-normal tails of the full-support class included -- are in the header of csrc/bar.hip."""
+        assert logits.shape[-1] == self.num_bars, f'{logits.shape[-1]} vs {self.num_bars}'
+        return _bar_stats(logits, self.borders, self._full_support, spec)
+
+    def variance(self, logits):
+        return self.stats(logits, [('variance',)])[..., 0]
+
+    def cdf(self, logits, y):
+        """P(Y <= y)."""
+        return self.stats(logits, [('cdf', y)])[..., 0]
+
+    def icdf(self, logits, p):
+        """The level-`p` quantile: linear inside a bucket, the half-normal tails inverted for full support."""
+        return self.stats(logits, [('icdf', p)])[..., 0]
+
+    def median(self, logits):
+        return self.icdf(logits, .5)
+
+    def pi(self, logits, best_f, maximize=True):
+        """Probability of improvement over `best_f`."""
+        c = self.cdf(logits, best_f)
+        return 1 - c if maximize else c
+
+    def ucb(self, logits, rest_prob=.05, maximize=True):
+        """Upper (lower when minimising) confidence bound: the quantile that leaves `rest_prob` beyond it."""
+        return self.icdf(logits, 1 - rest_prob if maximize else rest_prob)
+
+    def sample(self, logits, n, seed=None):
+        """`n` draws per row from the predictive distribution (pfn_bar_sample): [n, ...].  Counter-based: a function of (seed, row, draw index);
+        seed=None takes one from torch's generator."""
+        assert logits.shape[-1] == self.num_bars, f'{logits.shape[-1]} vs {self.num_bars}'
+        return _bar_sample(logits, self.borders, self._full_support, n, seed)
+
     def quantile(self, logits, center_prob=.682):
         """Central interval [lower, upper] with mass `center_prob`, linear inside a bucket
-        (reference :40-62; vectorised over rows instead of the reference's Python loop)."""
+        (reference :40-62; vectorised over rows instead of the reference's Python loop).  Host-side PyTorch ending in .cpu();
+        `stats(logits, [('icdf', side), ('icdf', 1 - side)])` is the fused, differentiable form on the device."""
         shape = logits.shape
         probs = logits.reshape(-1, shape[-1]).softmax(-1)
         side = (1 - center_prob) / 2

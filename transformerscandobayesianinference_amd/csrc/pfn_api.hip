@@ -1349,6 +1349,60 @@ int pfn_bar_mean(const float* logits, int64_t ld, const float* borders, int64_t 
   return PFN_OK;
 }
 
+// the checks shared by pfn_bar_stats / pfn_bar_stats_backward / pfn_bar_sample; fills the common fields
+static int bar_stats_common(BarStatsArgs& a, const char* what, const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support) {
+  if (R < 0) return fail(PFN_ERR_ARGUMENT, "%s: R = %lld", what, (long long)R);
+  if (nbars < 1 || (full_support && nbars < 2)) return fail(PFN_ERR_ARGUMENT, "%s: nbars = %d%s", what, nbars, full_support ? " (full support needs two buckets)" : "");
+  if (ld < nbars) return fail(PFN_ERR_ARGUMENT, "%s: ld %lld < nbars %d", what, (long long)ld, nbars);
+  if (!logits || !borders) return fail(PFN_ERR_ARGUMENT, "%s: null pointer", what);
+  memset(&a, 0, sizeof(a));
+  a.logits = logits; a.ld = ld; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support ? 1 : 0;
+  return PFN_OK;
+}
+static int bar_stats_spec(BarStatsArgs& a, const char* what, const int32_t* kinds, int K, const float* args, int64_t arg_ld) {
+  if (K < 1 || K > PFN_BAR_STATS_MAX) return fail(PFN_ERR_ARGUMENT, "%s: K = %d outside 1 .. %d", what, K, PFN_BAR_STATS_MAX);
+  if (!kinds || !args) return fail(PFN_ERR_ARGUMENT, "%s: null pointer", what);
+  if (arg_ld != 0 && arg_ld < K) return fail(PFN_ERR_ARGUMENT, "%s: arg_ld %lld < K %d", what, (long long)arg_ld, K);
+  for (int k = 0; k < K; ++k) {
+    if (kinds[k] < PFN_BAR_STAT_MEAN || kinds[k] > PFN_BAR_STAT_EI_MIN) return fail(PFN_ERR_ARGUMENT, "%s: unknown statistic %d at position %d", what, (int)kinds[k], k);
+    a.kinds[k] = kinds[k];
+    a.has_var |= kinds[k] == PFN_BAR_STAT_VARIANCE; a.has_icdf |= kinds[k] == PFN_BAR_STAT_ICDF;
+  }
+  a.K = K; a.args = args; a.arg_ld = arg_ld;
+  return PFN_OK;
+}
+int pfn_bar_stats(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                  const int32_t* kinds, int K, const float* args, int64_t arg_ld, float* out, void* stream) {
+  BarStatsArgs a;
+  PFN_TRY(bar_stats_common(a, "pfn_bar_stats", logits, ld, borders, R, nbars, full_support));
+  PFN_TRY(bar_stats_spec(a, "pfn_bar_stats", kinds, K, args, arg_ld));
+  if (!out) return fail(PFN_ERR_ARGUMENT, "pfn_bar_stats: null pointer");
+  a.out = out;
+  PFN_TRY(launch_bar_stats(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_bar_stats_backward(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                           const int32_t* kinds, int K, const float* args, int64_t arg_ld, const float* out, const float* gout,
+                           float* dlogits, void* stream) {
+  BarStatsArgs a;
+  PFN_TRY(bar_stats_common(a, "pfn_bar_stats_backward", logits, ld, borders, R, nbars, full_support));
+  PFN_TRY(bar_stats_spec(a, "pfn_bar_stats_backward", kinds, K, args, arg_ld));
+  if (!out || !gout || !dlogits) return fail(PFN_ERR_ARGUMENT, "pfn_bar_stats_backward: null pointer");
+  a.out = const_cast<float*>(out); a.gout = gout; a.dlogits = dlogits;
+  PFN_TRY(launch_bar_stats_bwd(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_bar_sample(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                   int n_samples, uint64_t seed, float* out, void* stream) {
+  BarStatsArgs a;
+  PFN_TRY(bar_stats_common(a, "pfn_bar_sample", logits, ld, borders, R, nbars, full_support));
+  if (n_samples < 0) return fail(PFN_ERR_ARGUMENT, "pfn_bar_sample: n_samples = %d", n_samples);
+  if (!out) return fail(PFN_ERR_ARGUMENT, "pfn_bar_sample: null pointer");
+  a.n_samples = n_samples; a.seed = seed; a.samples = out;
+  PFN_TRY(launch_bar_sample(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
 int pfn_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
                        float beta2, float eps, float max_norm, float grad_scale, int step, int zero_grad, float* scratch, void* stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || !scratch || n < 0 || step < 1) return fail(PFN_ERR_ARGUMENT, "bad clip_adam arguments");

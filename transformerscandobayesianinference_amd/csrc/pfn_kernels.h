@@ -411,6 +411,21 @@ int launch_bar_nll_fwd(const BarArgs& a, hipStream_t s);
 int launch_bar_nll_bwd(const BarArgs& a, hipStream_t s);
 int launch_bar_mean(const BarArgs& a, hipStream_t s);
 int launch_bar_mean_bwd(const BarArgs& a, hipStream_t s);      // dlogits = gout p (c - mean): mean_out holds the forward's means (read only)
+// posterior summaries and draws (definitions: the header of that section of bar.hip)
+struct BarStatsArgs {
+  const float* logits; long ld;  // [R, nbars]
+  const float* borders;          // [nbars+1]
+  long R; int nbars; int full_support;
+  int K; int kinds[PFN_BAR_STATS_MAX];      // PFN_BAR_STAT_*
+  int has_var, has_icdf;                    // any statistic of that kind among the K
+  const float* args; long arg_ld;           // [K] (arg_ld == 0) or [R, arg_ld]
+  float* out;                               // [R, K] (read by the backward)
+  const float* gout; float* dlogits;        // backward: [R, K], [R, nbars] with row stride ld
+  int n_samples; unsigned long long seed; float* samples;      // draws: [n_samples, R]
+};
+int launch_bar_stats(const BarStatsArgs& a, hipStream_t s);
+int launch_bar_stats_bwd(const BarStatsArgs& a, hipStream_t s);
+int launch_bar_sample(const BarStatsArgs& a, hipStream_t s);
 
 // ---- optimizer (optim.hip) ----------------------------------------------------------------------
 struct AdamArgs {

@@ -294,6 +294,46 @@ int pfn_stack_input_grads(const pfn_model_desc* d, const float* params, int B, i
                           const void* workspace, int64_t workspace_bytes,
                           float* dx, int64_t dx_st, int64_t dx_sb, float* dy, int64_t dy_st, int64_t dy_sb, void* stream);
 
+/* ---- CONDITION AND PREDICT WITH A DIFFERENT TRAINING-SET SIZE PER DATASET (ABI 10, additive: a binding detects these four by symbol).  Tabular tasks of different
+ * sizes, Bayesian-optimisation runs at different iteration counts, or one dataset at many train sizes (a learning curve) as ONE batch.  The four calls mirror
+ * pfn_stack_condition / pfn_stack_predict / pfn_stack_predict_saved / pfn_stack_predict_backward with `sep` replaced by sep_max and sep_of:
+ *   sep_of: [B] int32 in DEVICE memory, dataset b's train-row count len_b; sep_max >= every len_b is the row count of the padded x / y arrays of the condition call
+ *     and the context's rows per dataset.
+ *   SEMANTICS: for every dataset b, row t of column b of the ragged predict equals
+ *       pfn_stack_forward(cat(x_b[:len_b], x_test_b), cat(y_b[:len_b], anything), sep = len_b)   run alone on that dataset, up to rounding order.
+ *   PADDING RULE: rows t >= len_b of the padded x / y (any finite values) reach NO output, not even at rounding level.  Padding with real rows would not do: a padded
+ *     train row is a key every query sees.  The condition pass treats these rows as test rows of the ragged forward (embedded without y, attending to [0, len_b)
+ *     plus themselves, outside the key-shift sample); their K | V land in the context and are never read.  It runs B * sep_max rows.
+ *   len_b = 0 is allowed inside a batch with sep_max > 0: that dataset's test rows attend to themselves only (zero key shift).
+ *   CLAMPING: the values behind sep_of cannot be checked on the host without a synchronise.  Every kernel that reads them clamps them to [0, sep_max] (the condition
+ *     pass works on a clamped copy), so no value can carry a read outside the context; a value outside the range gives the clamped dataset's result.
+ *   CONTEXT and WORKSPACES keep the uniform sizes and layout at sep_max: pfn_context_bytes(d, B, sep_max) (dataset stride sep_max rows; the per-layer [B, E] key shift
+ *     where keys are centred), pfn_workspace_bytes(d, B, sep_max), pfn_predict_workspace_bytes / pfn_predict_grad_workspace_bytes(d, B, n).  A context made by
+ *     pfn_stack_condition_ragged is read with the SAME sep_max and sep_of.  With every len_b == sep_max the calls run the uniform calls' arithmetic bit for bit.
+ *   The attention's key-range splits (one launch geometry per call) are sized for sep_max; a split beyond a dataset's last key does no work.
+ * NULL sep_of, B < 1, sep_max < 0, n < 0, a NULL context with sep_max > 0, a context or workspace that is too small return PFN_ERR_ARGUMENT before anything is
+ * launched.  sep_max == 0: nothing to condition, as pfn_stack_condition at sep = 0. */
+int pfn_stack_condition_ragged(const pfn_model_desc* d, const float* params, const void* shadow,
+                               const float* x, int64_t x_st, int64_t x_sb,
+                               const float* y, int64_t y_st, int64_t y_sb,
+                               int B, int sep_max, const int32_t* sep_of,
+                               void* workspace, int64_t workspace_bytes,
+                               void* context, int64_t context_bytes, void* stream);
+int pfn_stack_predict_ragged(const pfn_model_desc* d, const float* params, const void* shadow,
+                             const void* context, int64_t context_bytes, int sep_max, const int32_t* sep_of,
+                             const float* x, int64_t x_st, int64_t x_sb,
+                             int B, int n,
+                             void* workspace, int64_t workspace_bytes, float* logits, void* stream);
+int pfn_stack_predict_saved_ragged(const pfn_model_desc* d, const float* params, const void* shadow,
+                                   const void* context, int64_t context_bytes, int sep_max, const int32_t* sep_of,
+                                   const float* x, int64_t x_st, int64_t x_sb,
+                                   int B, int n,
+                                   void* workspace, int64_t workspace_bytes, float* logits, void* stream);
+int pfn_stack_predict_backward_ragged(const pfn_model_desc* d, const float* params, const void* shadow,
+                                      const void* context, int64_t context_bytes, int sep_max, const int32_t* sep_of, int B, int n,
+                                      void* workspace, int64_t workspace_bytes, const float* dlogits,
+                                      float* dx, int64_t dx_st, int64_t dx_sb, void* stream);
+
 /* ---- bar distribution: replaces BarDistribution / FullSupportBarDistribution.forward and .mean
  * (bar_distribution.py:19-38, 83-117).  logits [R, nbars] f32 (row stride ld), y [R], borders
  * [nbars+1] sorted.  nll [R].  lse [R] and bucket [R] are saved for the backward. */

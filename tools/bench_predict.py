@@ -1,10 +1,14 @@
 """Condition once, predict many, timed at the configs[1] model shape (18 features, emsize 512, 4 heads, nhid 1024, 6 layers, 1000 bars), sep = 2000:
 one inference forward at sep + n rows, `condition` once, `predict` repeated -- for n in {1, 16, 256, 2048}, B in {1, 64}, exact-f32 inference and fp16.
 HIP events around the calls; one JSON line per (format, B, n) and a last line with the summary.
-    python tools/bench_predict.py [--quick] [--reps R] [--no-split] [--grad]
+    python tools/bench_predict.py [--quick] [--reps R] [--no-split] [--grad] [--ragged [--uniform-only] [--rounds K]]
 --quick: B = 1, n in {1, 16} only (the rocprofv3 kernel-trace run); --no-split: PFN_TUNE_ATTN_CACHE_SPLITS = 1 (one pass over the keys, no merge).
 --grad: the input gradient at B = 64, n = 256 instead: predict_saved + predict_backward (pfn_stack_predict_backward) against predict, and against the only
-alternative without them, a full forward + backward over sep + n rows with x requiring grad (which runs the training-precision kernels, fp16)."""
+alternative without them, a full forward + backward over sep + n rows with x requiring grad (which runs the training-precision kernels, fp16).
+--ragged: datasets of different sizes as one batch (condition(src, train_lengths) + predict) at B = 64, n = 256, seeded lengths spread over [200, 2000] with the
+maximum 2000, fp16 and f32: (a) the ragged calls, (b) the uniform calls at sep = 2000, (d) what a user does without them, 64 x (condition + predict) at B = 1 with
+every dataset's own length.  (a), (b) and (d) alternate over --rounds rounds in one process; the spread of (b) over the rounds is the noise floor the others are
+read against.  --uniform-only times (b) alone and uses nothing but the uniform calls, so the same file also runs against an older library."""
 import argparse
 import json
 import os
@@ -89,15 +93,76 @@ def grad_rows(reps):
     return rows
 
 
+def ragged_lengths(B, lo=200, hi=SEP, seed=0):
+    v = torch.randint(lo, hi + 1, (B,), generator=torch.Generator().manual_seed(seed)).tolist()
+    v[0], v[1] = lo, hi
+    return v
+
+
+def ragged_rows(reps, rounds, uniform_only):
+    B, n = 64, 256
+    lengths = ragged_lengths(B)
+    rows = []
+
+    def stats(v):
+        v = sorted(v)
+        med = v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+        return dict(median_ms=med, min_ms=v[0], max_ms=v[-1], spread=(v[-1] - v[0]) / med, rounds=v)
+
+    for fmt in ('fp16', 'f32'):
+        model = model_for(fmt)
+        g = torch.Generator().manual_seed(B)
+        x = torch.randn(SEP + n, B, F, generator=g).cuda()
+        y = torch.randn(SEP + n, B, generator=g).cuda()
+        xt = x[SEP:]
+        singles = [(x[:s, b:b + 1].contiguous(), y[:s, b:b + 1].contiguous(), xt[:, b:b + 1].contiguous()) for b, s in enumerate(lengths)]
+        t = dict(a_condition=[], a_predict=[], b_condition=[], b_predict=[], d_total=[])
+        with torch.no_grad():
+            cu = model.condition((x[:SEP], y[:SEP]))
+            cr = None if uniform_only else model.condition((x[:SEP], y[:SEP]), train_lengths=lengths)
+
+            def per_dataset():
+                for xs, ys, xq in singles:
+                    model.predict(model.condition((xs, ys)), xq)
+            for _ in range(rounds):
+                if not uniform_only:
+                    t['a_condition'].append(timed(lambda: model.condition((x[:SEP], y[:SEP]), train_lengths=lengths), max(2, reps // 2)))
+                    t['a_predict'].append(timed(lambda: model.predict(cr, xt), reps))
+                t['b_condition'].append(timed(lambda: model.condition((x[:SEP], y[:SEP])), max(2, reps // 2)))
+                t['b_predict'].append(timed(lambda: model.predict(cu, xt), reps))
+                if not uniform_only:
+                    t['d_total'].append(timed(per_dataset, 2))
+        r = dict(format=fmt, B=B, n=n, sep_max=SEP, lengths_min=min(lengths), lengths_max=max(lengths), lengths_mean=sum(lengths) / B,
+                 uniform_condition=stats(t['b_condition']), uniform_predict=stats(t['b_predict']))
+        r['uniform_total_ms'] = r['uniform_condition']['median_ms'] + r['uniform_predict']['median_ms']
+        if not uniform_only:
+            r.update(ragged_condition=stats(t['a_condition']), ragged_predict=stats(t['a_predict']), per_dataset_B1=stats(t['d_total']))
+            r['ragged_total_ms'] = r['ragged_condition']['median_ms'] + r['ragged_predict']['median_ms']
+            r['per_dataset_over_ragged'] = r['per_dataset_B1']['median_ms'] / r['ragged_total_ms']
+            r['ragged_predict_over_uniform_predict'] = r['ragged_predict']['median_ms'] / r['uniform_predict']['median_ms']
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+        del cu, cr, model
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--quick', action='store_true')
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--no-split', action='store_true')
     ap.add_argument('--grad', action='store_true')
+    ap.add_argument('--ragged', action='store_true')
+    ap.add_argument('--uniform-only', action='store_true')
+    ap.add_argument('--rounds', type=int, default=5)
     args = ap.parse_args()
     if args.no_split:
         _hip.check(_hip.lib().pfn_set_tuning(PFN_TUNE_ATTN_CACHE_SPLITS, 1), 'pfn_set_tuning')
+    if args.ragged:
+        rows = ragged_rows(args.reps, args.rounds, args.uniform_only)
+        print(json.dumps(dict(summary='bench_predict --ragged', uniform_only=args.uniform_only, rows=len(rows), device=torch.cuda.get_device_name(0))), flush=True)
+        return
     if args.grad:
         rows = grad_rows(args.reps)
         print(json.dumps(dict(summary='bench_predict --grad', no_split=args.no_split, rows=len(rows), device=torch.cuda.get_device_name(0))), flush=True)

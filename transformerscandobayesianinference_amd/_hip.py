@@ -81,6 +81,14 @@ SIGNATURES = {
     'pfn_stack_predict_saved': (_I, [_D, _P, _P, _P, _L, _I, _P, _L, _L, _I, _I, _P, _L, _P, _P]),
     # (d, params, shadow, context, context_bytes, sep, B, n, ws, ws_bytes, dlogits, dx, dx_st, dx_sb, stream)
     'pfn_stack_predict_backward': (_I, [_D, _P, _P, _P, _L, _I, _I, _I, _P, _L, _P, _P, _L, _L, _P]),
+    # a different train-row count per dataset (ABI 10, additive): `sep` -> sep_max, sep_of [B] int32 on the device
+    # (d, params, shadow, x, x_st, x_sb, y, y_st, y_sb, B, sep_max, sep_of, ws, ws_bytes, context, context_bytes, stream)
+    'pfn_stack_condition_ragged': (_I, [_D, _P, _P, _P, _L, _L, _P, _L, _L, _I, _I, _P, _P, _L, _P, _L, _P]),
+    # (d, params, shadow, context, context_bytes, sep_max, sep_of, x, x_st, x_sb, B, n, ws, ws_bytes, logits, stream)
+    'pfn_stack_predict_ragged': (_I, [_D, _P, _P, _P, _L, _I, _P, _P, _L, _L, _I, _I, _P, _L, _P, _P]),
+    'pfn_stack_predict_saved_ragged': (_I, [_D, _P, _P, _P, _L, _I, _P, _P, _L, _L, _I, _I, _P, _L, _P, _P]),
+    # (d, params, shadow, context, context_bytes, sep_max, sep_of, B, n, ws, ws_bytes, dlogits, dx, dx_st, dx_sb, stream)
+    'pfn_stack_predict_backward_ragged': (_I, [_D, _P, _P, _P, _L, _I, _P, _I, _I, _P, _L, _P, _P, _L, _L, _P]),
     # (d, params, B, S, sep, ws, ws_bytes, dx, dx_st, dx_sb, dy, dy_st, dy_sb, stream)
     'pfn_stack_input_grads': (_I, [_D, _P, _I, _I, _I, _P, _L, _P, _L, _L, _P, _L, _L, _P]),
     'pfn_bar_nll_forward': (_I, [_P, _L, _P, _P, _L, _I, _I, _P, _P, _P, _P]),

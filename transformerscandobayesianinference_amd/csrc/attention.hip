@@ -191,6 +191,16 @@ constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 constexpr float RESCALE_THR = 6.f;  // log2 units: lazily raised running max of the online softmax (see attn_fwd_kernel)
 
+// Predict against a K / V cache whose datasets hold DIFFERENT numbers of train rows (pfn_stack_*_ragged): sep_of [B] on the device, `sep` the context's rows per
+// dataset (the longest one; the launch geometry is sized for it).  The count is clamped to [0, sep], so no value behind the pointer can carry a read outside the
+// context; it is one scalar load per workgroup (b comes from the block index).  nullptr = every dataset at `sep` (the uniform calls: nothing changes for them).
+PFN_DEV int cache_sep(const int* sep_of, int b, int sep) { return sep_of ? min(max(sep_of[b], 0), sep) : sep; }
+// EMPTY SPLITS: a split z > 0 whose key range starts at or beyond its dataset's last key writes NOTHING (it returns ahead of every barrier), and the merge kernels
+// read the first cache_live_splits partials of a dataset only -- split 0 always exists (it holds the self key), so no row is ever empty.
+PFN_DEV int cache_live_splits(const int* sep_of, int b, int sep, int split_keys, int nsplit) {
+  return sep_of ? max(1, min(nsplit, (cache_sep(sep_of, b, sep) + split_keys - 1) / split_keys)) : nsplit;
+}
+
 // =============================================================================================
 // forward
 // =============================================================================================
@@ -259,7 +269,8 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
   const int qc = min(qi, a.S - 1);
   // keys streamed by this workgroup: [0, sep) of qkv, or (CACHE) `sep` keys of the context from k_lo on
   const int k_lo = CACHE ? (int)blockIdx.z * a.split_keys : 0;
-  const int sep = CACHE ? min(a.sep - k_lo, a.split_keys) : a.sep_of ? a.sep_of[b] : a.sep;      // (wave-uniform: b comes from the block index)
+  const int sep = CACHE ? min(cache_sep(a.sep_of, b, a.sep) - k_lo, a.split_keys) : a.sep_of ? a.sep_of[b] : a.sep;      // (wave-uniform: b comes from the block index)
+  if constexpr (CACHE) { if (blockIdx.z > 0 && sep <= 0) return; }      // ragged context: an empty split (cache_live_splits), ahead of every barrier and LDS access
   const long kld = CACHE ? a.kv_ld : rs;
   const T* Ksrc = CACHE ? reinterpret_cast<const T*>(a.kv) + b * a.kv_sb + k_lo * kld + hd * D : Kp;
   const T* Vsrc = CACHE ? Ksrc + a.E + vcol0 : Vp;
@@ -534,11 +545,12 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(AttnArgs a, int nsplit,
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long row = i / c4n;
     const int c = (int)(i - row * c4n) * 4, hd = c / D;
+    const int nz = cache_live_splits(a.sep_of, (int)(row / a.S), a.sep, a.split_keys, nsplit);      // (the splits beyond wrote nothing)
     float mx = -INFINITY;
-    for (int z = 0; z < nsplit; ++z) mx = fmaxf(mx, a.part_ml[2 * ((z * rows + row) * a.H + hd)]);
+    for (int z = 0; z < nz; ++z) mx = fmaxf(mx, a.part_ml[2 * ((z * rows + row) * a.H + hd)]);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float l = 0.f;
-    for (int z = 0; z < nsplit; ++z) {
+    for (int z = 0; z < nz; ++z) {
       const float2 ml = *reinterpret_cast<const float2*>(a.part_ml + 2 * ((z * rows + row) * a.H + hd));
       const float w = fast_exp2(ml.x - mx);
       l += w * ml.y;
@@ -599,7 +611,8 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_cache_kernel(Att
   const T* orow = reinterpret_cast<const T*>(a.ctx) + row * a.E + hd * D;
   const T* dorow = reinterpret_cast<const T*>(a.dctx) + row * a.E + hd * D;
   const int z = blockIdx.z, k_lo = z * a.split_keys;
-  const int nkeys = max(0, min(a.sep - k_lo, a.split_keys));
+  const int nkeys = max(0, min(cache_sep(a.sep_of, b, a.sep) - k_lo, a.split_keys));      // (wave-uniform, as the forward's)
+  if (z > 0 && nkeys == 0) return;      // ragged context: an empty split leaves no partial (cache_live_splits); the self-key terms belong to split 0
   const long kld = a.kv_ld;
   const T* Ksrc = reinterpret_cast<const T*>(a.kv) + b * a.kv_sb + k_lo * kld + hd * D;
   const T* Vsrc = Ksrc + a.E;
@@ -725,8 +738,9 @@ __global__ __launch_bounds__(256) void attn_bwd_cache_merge_kernel(AttnCacheBwdA
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long row = i / c4n;
     const int c = (int)(i - row * c4n) * 4;
+    const int nz = cache_live_splits(a.sep_of, (int)(row / a.S), a.sep, a.split_keys, nsplit);
     f32x4 acc = *reinterpret_cast<const f32x4*>(a.part_dq + row * a.E + c);
-    for (int z = 1; z < nsplit; ++z) {
+    for (int z = 1; z < nz; ++z) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(a.part_dq + (z * rows + row) * a.E + c);
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[e] += v[e];
@@ -1939,7 +1953,7 @@ int launch_attn_fwd_cache(const AttnArgs& a_in, int precision, hipStream_t s) {
   if ((a_in.E * prec_esize(precision)) % 16 || (a_in.kv_ld * prec_esize(precision)) % 16) return PFN_ERR_ALIGNMENT;
   AttnArgs a = a_in;
   a.pingpong = g_attn_pingpong;
-  a.q_begin = 0; a.sep_of = nullptr; a.q_from_sep = 0; a.p_drop = 0.f; a.xq = nullptr;
+  a.q_begin = 0; a.q_from_sep = 0; a.p_drop = 0.f; a.xq = nullptr;      // (sep_of: per-dataset key counts of a ragged context, or nullptr)
   PFN_ATTN_DISPATCH(launch_fwd_cache_t, return (launch_fwd_cache_t<float, 256>(a, s)))
 }
 template <typename T, int D> static int launch_bwd_cache_t(const AttnCacheBwdArgs& a_in, hipStream_t s) {
@@ -1967,6 +1981,17 @@ int launch_attn_bwd_cache(const AttnCacheBwdArgs& a, int precision, hipStream_t 
   if (a.B <= 0 || a.S <= 0 || a.H <= 0 || a.E % a.H || a.sep < 0 || (a.sep > 0 && !a.kv) || !a.qkv || !a.ctx || !a.lse || !a.dctx || !a.dqkv) return PFN_ERR_ARGUMENT;
   if ((a.E * prec_esize(precision)) % 16 || (a.kv_ld * prec_esize(precision)) % 16) return PFN_ERR_ALIGNMENT;
   PFN_ATTN_DISPATCH(launch_bwd_cache_t, return (launch_bwd_cache_t<float, 256>(a, s)))
+}
+// dst[b] = min(max(src[b], 0), hi): the condition pass of a ragged context hands the embedding, key-shift and attention kernels of the training path (which trust
+// their sep_of) a copy that cannot carry them outside [0, sep_max]
+__global__ __launch_bounds__(256) void clamp_sep_of_kernel(const int* src, int* dst, int B, int hi) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < B) dst[b] = min(max(src[b], 0), hi);
+}
+int launch_clamp_sep_of(const int* src, int* dst, int B, int hi, hipStream_t s) {
+  if (!src || !dst || B < 1 || hi < 0) return PFN_ERR_ARGUMENT;
+  hipLaunchKernelGGL(clamp_sep_of_kernel, dim3((B + 255) / 256), dim3(256), 0, s, src, dst, B, hi);
+  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 void attn_bwd_ds_dims(int S, int sep, int* rows, int* ld) {
   *rows = (sep + 63) / 64 * 64;       // whole key tiles of the dQ pass

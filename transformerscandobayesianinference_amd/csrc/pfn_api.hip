@@ -491,7 +491,9 @@ static int stack_forward_impl(const pfn_model_desc* d, const float* params, cons
   // ragged batch (pfn_stack_forward_ragged): every dataset has its own eval position (rg->sep_of, device), `sep` is their maximum, the decoder's compact
   // rows are dataset-major (rg->row_off) and there are rg->test_rows of them; the top layer then runs on every row
   const int* sep_of = rg ? rg->sep_of : nullptr;
-  if (rg && (src_sbe || rg->test_rows < 0 || rg->test_rows > (int64_t)B * S || !rg->sep_of || !rg->row_off)) return fail(PFN_ERR_ARGUMENT, "bad ragged-batch arguments");
+  // (row_off places the decoder's compact rows: the condition pass of a ragged context -- sink, no test row, the top layer ends at its projection -- has none)
+  if (rg && (src_sbe || rg->test_rows < 0 || rg->test_rows > (int64_t)B * S || !rg->sep_of || (!rg->row_off && !(sink && rg->test_rows == 0))))
+    return fail(PFN_ERR_ARGUMENT, "bad ragged-batch arguments");
   const int M = B * S, Mt = rg ? (int)rg->test_rows : (S - sep) * B;
   const char* sh = (const char*)shadow;
   auto W = [&](int64_t off) { return (const void*)(sh + off * es); };
@@ -720,6 +722,29 @@ int pfn_stack_condition(const pfn_model_desc* d, const float* params, const void
   if (!x || !y) return fail(PFN_ERR_ARGUMENT, "need x and y");
   return stack_forward_impl(d, params, shadow, x, x_st, x_sb, y, y_st, y_sb, nullptr, B, sep, sep, workspace, workspace_bytes, nullptr, stream, false, 0, nullptr, &sink);
 }
+// ---- ... with a different training-set size per dataset (ABI 10, additive) ----
+// The condition pass is the ragged forward at S = sep_max: rows t >= sep_of[b] of dataset b behave as TEST rows there -- embedded without y, attending to [0, sep_of[b])
+// plus themselves, outside the key-shift sample -- so the K | V of rows [0, sep_of[b]) and the dataset's key shift are those of the dataset run alone.  The padded
+// rows' K | V land in the context (dataset stride sep_max) and no predict kernel reads them.  The kernels of the training path trust their sep_of, so they get a
+// clamped copy (launch_clamp_sep_of) in the workspace's attention-backward scratch, which a forward leaves alone.
+int pfn_stack_condition_ragged(const pfn_model_desc* d, const float* params, const void* shadow,
+                               const float* x, int64_t x_st, int64_t x_sb, const float* y, int64_t y_st, int64_t y_sb,
+                               int B, int sep_max, const int32_t* sep_of, void* workspace, int64_t workspace_bytes, void* context, int64_t context_bytes, void* stream) {
+  PFN_TRY(check_desc(d));
+  if (B < 1 || sep_max < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d sep_max=%d", B, sep_max);
+  if (!sep_of) return fail(PFN_ERR_ARGUMENT, "null sep_of");
+  const KvSink sink = {(char*)context, context_layout(*d, B, sep_max)};
+  if (sep_max > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context");
+  if (context_bytes < sink.c.bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)sink.c.bytes);
+  if (sep_max == 0 || d->nlayers == 0) return PFN_OK;
+  if (!x || !y || !params || !shadow || !workspace) return fail(PFN_ERR_ARGUMENT, "null pointer");
+  const Ws w = carve(*d, B, sep_max, (char*)workspace);
+  if (workspace_bytes < w.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)w.bytes);
+  int32_t* clamped = (int32_t*)w.delta;      // [2 B H sep_max] f32 of backward scratch: B int32 fit
+  PFN_TRY(launch_clamp_sep_of(sep_of, clamped, B, sep_max, (hipStream_t)stream));
+  const Ragged rg = {clamped, nullptr, 0, 0};
+  return stack_forward_impl(d, params, shadow, x, x_st, x_sb, y, y_st, y_sb, nullptr, B, sep_max, sep_max, workspace, workspace_bytes, nullptr, stream, false, 0, &rg, &sink);
+}
 int64_t pfn_predict_workspace_bytes(const pfn_model_desc* d, int B, int n) {
   if (check_desc(d) != PFN_OK || B < 1 || n < 0) return -1;
   return carve_predict(*d, B, n, nullptr).bytes;
@@ -732,8 +757,9 @@ int64_t pfn_predict_grad_workspace_bytes(const pfn_model_desc* d, int B, int n) 
 // sv == nullptr: pfn_stack_predict (two alternating row sets in w); else pfn_stack_predict_saved (every layer's buffers kept in sv, the attention's lse written).
 static int stack_predict_impl(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep,
                               const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes, float* logits, void* stream,
-                              bool saved) {
+                              bool saved, bool ragged = false, const int32_t* sep_of = nullptr) {
   PFN_TRY(check_desc(d));
+  if (ragged && !sep_of) return fail(PFN_ERR_ARGUMENT, "null sep_of");
   if (B < 1 || n < 0 || sep < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d n=%d sep=%d", B, n, sep);
   const Context c = context_layout(*d, B, sep);
   if (sep > 0 && d->nlayers > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context with sep=%d", sep);
@@ -802,7 +828,7 @@ static int stack_predict_impl(const pfn_model_desc* d, const float* params, cons
     }
     {
       AttnArgs at; memset(&at, 0, sizeof(at));
-      at.qkv = u.qkv; at.ctx = u.ctx; at.lse = u.lse; at.B = B; at.S = n; at.E = E; at.H = H; at.sep = sep;
+      at.qkv = u.qkv; at.ctx = u.ctx; at.lse = u.lse; at.B = B; at.S = n; at.E = E; at.H = H; at.sep = sep; at.sep_of = sep_of;
       at.kv = kv; at.kv_ld = 2L * E; at.kv_sb = (long)sep * 2 * E; at.part_o = saved ? sv.part_o : w.part_o; at.part_ml = saved ? sv.part_ml : w.part_ml;
       PFN_TRY(launch_attn_fwd_cache(at, prec, s));
     }
@@ -870,12 +896,38 @@ int pfn_stack_predict_saved(const pfn_model_desc* d, const float* params, const 
                             const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes, float* logits, void* stream) {
   return stack_predict_impl(d, params, shadow, context, context_bytes, sep, x, x_st, x_sb, B, n, workspace, workspace_bytes, logits, stream, true);
 }
+// ... against a ragged context (pfn_stack_condition_ragged): `sep` becomes sep_max (the context's rows per dataset) and dataset b's queries see its first sep_of[b] keys
+// (the cached-K/V attention kernels clamp the count to [0, sep_max]); a dataset without train rows has a zero key shift, so its self keys leave unshifted
+int pfn_stack_predict_ragged(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep_max,
+                             const int32_t* sep_of, const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes, float* logits,
+                             void* stream) {
+  return stack_predict_impl(d, params, shadow, context, context_bytes, sep_max, x, x_st, x_sb, B, n, workspace, workspace_bytes, logits, stream, false, true, sep_of);
+}
+int pfn_stack_predict_saved_ragged(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep_max,
+                                   const int32_t* sep_of, const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes,
+                                   float* logits, void* stream) {
+  return stack_predict_impl(d, params, shadow, context, context_bytes, sep_max, x, x_st, x_sb, B, n, workspace, workspace_bytes, logits, stream, true, true, sep_of);
+}
 
 // d(x_test) of a saved predict pass: the data-gradient chain of stack_backward_impl on the B n test rows -- decoder, then every layer's LN2 backward, d(hpre), LN1
 // backward, d(ctx), the cached-attention backward (launch_attn_bwd_cache) and dx -- with no weight-gradient launch; the LayerNorm kernels' parameter sums go to a sink
 // in the workspace.  The context and every parameter stay untouched.
+static int stack_predict_backward_impl(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep,
+                                       const int32_t* sep_of, int B, int n, void* workspace, int64_t workspace_bytes, const float* dlogits, float* dx, int64_t dx_st,
+                                       int64_t dx_sb, void* stream);
 int pfn_stack_predict_backward(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep, int B, int n,
                                void* workspace, int64_t workspace_bytes, const float* dlogits, float* dx, int64_t dx_st, int64_t dx_sb, void* stream) {
+  return stack_predict_backward_impl(d, params, shadow, context, context_bytes, sep, nullptr, B, n, workspace, workspace_bytes, dlogits, dx, dx_st, dx_sb, stream);
+}
+int pfn_stack_predict_backward_ragged(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep_max,
+                                      const int32_t* sep_of, int B, int n, void* workspace, int64_t workspace_bytes, const float* dlogits, float* dx, int64_t dx_st,
+                                      int64_t dx_sb, void* stream) {
+  if (!sep_of) return fail(PFN_ERR_ARGUMENT, "null sep_of");
+  return stack_predict_backward_impl(d, params, shadow, context, context_bytes, sep_max, sep_of, B, n, workspace, workspace_bytes, dlogits, dx, dx_st, dx_sb, stream);
+}
+static int stack_predict_backward_impl(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep,
+                                       const int32_t* sep_of, int B, int n, void* workspace, int64_t workspace_bytes, const float* dlogits, float* dx, int64_t dx_st,
+                                       int64_t dx_sb, void* stream) {
   PFN_TRY(check_desc(d));
   if (B < 1 || n < 0 || sep < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d n=%d sep=%d", B, n, sep);
   const Context c = context_layout(*d, B, sep);
@@ -969,7 +1021,7 @@ int pfn_stack_predict_backward(const pfn_model_desc* d, const float* params, con
       AttnCacheBwdArgs at; memset(&at, 0, sizeof(at));
       at.qkv = a.qkv; at.ctx = a.ctx; at.lse = a.lse; at.dctx = w.dctx_t; at.dqkv = w.dqkv_t;
       at.kv = kv; at.kv_ld = 2L * E; at.kv_sb = (long)sep * 2 * E; at.part_dq = w.part_o;
-      at.B = B; at.S = n; at.E = E; at.H = H; at.sep = sep;
+      at.B = B; at.S = n; at.E = E; at.H = H; at.sep = sep; at.sep_of = sep_of;
       PFN_TRY(launch_attn_bwd_cache(at, prec, s));
     }
     if (fuse_lnb && l > 0) {  // dy2 of the layer below = its LN2 backward of (dqkv . Win + dy1)

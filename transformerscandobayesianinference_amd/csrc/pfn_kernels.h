@@ -228,6 +228,7 @@ struct AttnArgs {
       float* part_o;      // more than one split: [nsplit, B, n, E] f32 unnormalised outputs ...
       float* part_ml;     // ... and [nsplit, B, n, H] (running max in log2 units, row sum) pairs; attn_merge_kernel writes ctx from them
       int split_keys;     // filled by the launcher: keys per split (whole tiles); split z = blockIdx.z streams keys [z * split_keys, min(sep, (z + 1) * split_keys))
+                          // (ragged context: sep_of above gives every dataset its own key count <= sep; splits beyond it write nothing and the merge skips them)
     };
   };
   int pingpong;  // filled by the launcher (PFN_TUNE_ATTN_PINGPONG): bit 0 forward, bit 1 key-block pass
@@ -267,7 +268,10 @@ struct AttnCacheBwdArgs {
   float* part_dq;         // more than one split: [nsplit, B, n, E] f32 partial dQ (unscaled), summed in split order by the merge kernel
   int B, S, E, H, sep;
   int split_keys;         // filled by the launcher
+  const int* sep_of;      // ragged context: per-dataset key counts [B] on the device (clamped to [0, sep] by the kernels); nullptr = every dataset at `sep`
 };
+// a ragged context's per-dataset train-row counts clamped to [0, hi] (dst [B] int32 on the device): what the condition pass hands the training-path kernels
+int launch_clamp_sep_of(const int* src, int* dst, int B, int hi, hipStream_t stream);
 int launch_attn_bwd_cache(const AttnCacheBwdArgs& a, int precision, hipStream_t stream);
 void set_attn_pingpong(int mask);
 void set_attn_bwd_group(int datasets);      // 0 = all datasets of a call in one launch pair

@@ -71,6 +71,29 @@ def run_test(model, device='cuda:0', step_size=100, start_pos=1, batch_size=1000
 
 
 @torch.no_grad()
+def learning_curve(model, x, y, positions):
+    """The learning curve of FIXED datasets x [T, B, F], y [T, B]: for every p in `positions` (0 <= p < T) the criterion's NLL and the posterior mean of row p
+    given rows [:p], as two tensors [len(positions), B] -- what `model((x[:p + 1], y[:p + 1]), single_eval_pos=p)` gives position by position, from ONE ragged
+    condition (the datasets side by side once per position, each copy with its own train-row count p) and ONE predict with a single test row per copy.
+    (`run_test` draws fresh datasets per position, as the notebook does, and has nothing to share between positions.)"""
+    positions = [int(p) for p in positions]
+    T, B = y.shape
+    if not positions or min(positions) < 0 or max(positions) >= T:
+        raise ValueError(f'learning_curve: positions must lie in [0, {T - 1}]')
+    P, sep_max = len(positions), max(positions)
+    was_training = model.training
+    model.eval()
+    lengths = [p for p in positions for _ in range(B)]                    # copy k of dataset b is column k B + b
+    context = model.condition((x[:sep_max].repeat(1, P, 1), y[:sep_max].repeat(1, P)), train_lengths=lengths)
+    logits = model.predict(context, x[positions].reshape(1, P * B, x.shape[2]))      # [1, P B, n_out]
+    target = y[positions].reshape(P * B).to(logits.device)
+    nll = model.criterion(logits[0], target).reshape(P, B)
+    mean = model.criterion.mean(logits)[0].reshape(P, B)
+    model.train(was_training)
+    return nll, mean
+
+
+@torch.no_grad()
 def gp_baseline(device='cuda:0', step_size=100, start_pos=1, batch_size=1000, sub_batch_size=100, seq_len=2000,
                 num_features=5, hyperparameters=None):
     """The exact-GP curve on the same prior: (eval_positions, mean_mse [n], nll [n], nll_confidence [n]).  One draw of

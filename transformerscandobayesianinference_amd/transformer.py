@@ -191,9 +191,14 @@ class _PredictFunction(torch.autograd.Function):
         ws_bytes = _hip.check(lib.pfn_predict_grad_workspace_bytes(ctypes.byref(desc), B, n), 'pfn_predict_grad_workspace_bytes')
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         out = torch.empty((n, B, desc.n_out or desc.emsize), dtype=torch.float32, device=dev)
-        _hip.check(lib.pfn_stack_predict_saved(ctypes.byref(desc), model._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(), context.buffer.numel(),
-                                               context.sep, x.data_ptr(), x.stride(0), x.stride(1), B, n, ws.data_ptr(), ws_bytes, out.data_ptr(), stream),
-                   'pfn_stack_predict_saved')
+        if context.lengths is not None:      # a ragged context: every dataset against its own train rows
+            _hip.check(lib.pfn_stack_predict_saved_ragged(ctypes.byref(desc), model._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(),
+                                                          context.buffer.numel(), context.sep, context.sep_of.data_ptr(), x.data_ptr(), x.stride(0), x.stride(1),
+                                                          B, n, ws.data_ptr(), ws_bytes, out.data_ptr(), stream), 'pfn_stack_predict_saved_ragged')
+        else:
+            _hip.check(lib.pfn_stack_predict_saved(ctypes.byref(desc), model._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(), context.buffer.numel(),
+                                                   context.sep, x.data_ptr(), x.stride(0), x.stride(1), B, n, ws.data_ptr(), ws_bytes, out.data_ptr(), stream),
+                       'pfn_stack_predict_saved')
         ctx.state = (model, context, desc, shadow, ws, x.shape)
         return out
 
@@ -203,9 +208,15 @@ class _PredictFunction(torch.autograd.Function):
         lib = _hip.lib()
         dout = dout.contiguous().float()
         dx = torch.empty((n, B, F), dtype=torch.float32, device=dout.device)
-        _hip.check(lib.pfn_stack_predict_backward(ctypes.byref(desc), model._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(), context.buffer.numel(),
-                                                  context.sep, B, n, ws.data_ptr(), ws.numel(), dout.data_ptr(), dx.data_ptr(), dx.stride(0), dx.stride(1),
-                                                  _hip.stream_ptr(dout.device)), 'pfn_stack_predict_backward')
+        if context.lengths is not None:
+            _hip.check(lib.pfn_stack_predict_backward_ragged(ctypes.byref(desc), model._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(),
+                                                             context.buffer.numel(), context.sep, context.sep_of.data_ptr(), B, n, ws.data_ptr(), ws.numel(),
+                                                             dout.data_ptr(), dx.data_ptr(), dx.stride(0), dx.stride(1), _hip.stream_ptr(dout.device)),
+                       'pfn_stack_predict_backward_ragged')
+        else:
+            _hip.check(lib.pfn_stack_predict_backward(ctypes.byref(desc), model._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(), context.buffer.numel(),
+                                                      context.sep, B, n, ws.data_ptr(), ws.numel(), dout.data_ptr(), dx.data_ptr(), dx.stride(0), dx.stride(1),
+                                                      _hip.stream_ptr(dout.device)), 'pfn_stack_predict_backward')
         ctx.state = None
         return dx, None, None, None, None
 
@@ -225,17 +236,64 @@ def ragged_layout(T, widths, single_eval_positions):
     return seps, per_dataset, offs
 
 
+def check_train_lengths(train_lengths, B, sep_max):
+    """`condition(src, train_lengths=...)`: one train-row count per dataset, as a sequence or an integer tensor [B], each within [0, sep_max] (the rows of the
+    padded src).  Returns them as a tuple of ints; anything else raises ValueError.  (Host side only: the kernels clamp what they read, they do not report it.)"""
+    if isinstance(train_lengths, torch.Tensor):
+        if train_lengths.dim() != 1 or train_lengths.dtype.is_floating_point or train_lengths.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise ValueError(f'train_lengths: expected an integer tensor [B], got {train_lengths.dtype} of shape {tuple(train_lengths.shape)}')
+        train_lengths = train_lengths.tolist()
+    lengths = []
+    for v in train_lengths:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f'train_lengths: {v!r} is not an integer')
+        lengths.append(int(v))
+    if len(lengths) != B:
+        raise ValueError(f'train_lengths has {len(lengths)} entries, the batch has B={B} datasets')
+    for b, v in enumerate(lengths):
+        if v < 0 or v > sep_max:
+            raise ValueError(f'train_lengths[{b}] = {v} is outside [0, {sep_max}] (the rows of the padded training set)')
+    return tuple(lengths)
+
+
+def pad_datasets(datasets):
+    """[(x_b [s_b, F], y_b [s_b]), ...] -> (x [sep_max, B, F], y [sep_max, B], lengths): the datasets side by side, zero-filled behind their own rows (the values
+    there reach nothing: `TransformerModel.condition(src, train_lengths)`), sep_max = the longest.  Pure tensor code, on whatever device the datasets live."""
+    if len(datasets) == 0:
+        raise ValueError('pad_datasets: no dataset')
+    x0 = datasets[0][0]
+    if x0.dim() != 2:
+        raise ValueError(f'pad_datasets: x of dataset 0 has shape {tuple(x0.shape)}, expected [s, F]')
+    F = x0.shape[1]
+    lengths = []
+    for b, (xb, yb) in enumerate(datasets):
+        if xb.dim() != 2 or xb.shape[1] != F or tuple(yb.shape) != (xb.shape[0],):
+            raise ValueError(f'pad_datasets: dataset {b} has x {tuple(xb.shape)} and y {tuple(yb.shape)}, expected [s, {F}] and [s]')
+        lengths.append(xb.shape[0])
+    sep_max = max(lengths)
+    x = x0.new_zeros((sep_max, len(datasets), F))
+    y = datasets[0][1].new_zeros((sep_max, len(datasets)))
+    for b, (xb, yb) in enumerate(datasets):
+        x[:lengths[b], b] = xb
+        y[:lengths[b], b] = yb
+    return x, y, tuple(lengths)
+
+
 class PredictContext:
     """A conditioned training set (`TransformerModel.condition`): every layer's keys and values of the train rows in one device buffer
     (include/pfn_hip.h pfn_context_bytes), with what they were made from -- the parameter version, the descriptor, B, F, sep and the device.
-    `TransformerModel.predict` refuses a context whose model has changed since."""
+    `TransformerModel.predict` refuses a context whose model has changed since.
+    A ragged context (`condition(src, train_lengths)`) also carries `lengths` (host tuple, one train-row count per dataset) and `sep_of` (the same as int32 on
+    the device); `sep` is then their padded maximum.  Both are None for a uniform context."""
 
-    def __init__(self, buffer, param_version, desc_key, B, F, sep, device):
+    def __init__(self, buffer, param_version, desc_key, B, F, sep, device, lengths=None, sep_of=None):
         self.buffer, self.param_version, self.desc_key = buffer, param_version, desc_key
         self.B, self.F, self.sep, self.device = B, F, sep, device
+        self.lengths, self.sep_of = lengths, sep_of
 
     def __repr__(self):
-        return f'PredictContext(B={self.B}, F={self.F}, sep={self.sep}, {self.buffer.numel()} bytes on {self.device})'
+        ragged = '' if self.lengths is None else f', lengths {min(self.lengths)}..{max(self.lengths)}'
+        return f'PredictContext(B={self.B}, F={self.F}, sep={self.sep}{ragged}, {self.buffer.numel()} bytes on {self.device})'
 
 
 class TransformerModel(nn.Module):
@@ -548,11 +606,16 @@ class TransformerModel(nn.Module):
         return (self._param_version(), getattr(self, '_param_updates', 0))
 
     @torch.no_grad()
-    def condition(self, src):
+    def condition(self, src, train_lengths=None):
         """Run the training set src = (x_train [sep, B, F], y_train [sep, B]) once and keep every layer's keys and values: the returned PredictContext
-        serves any number of `predict` calls (pfn_stack_condition)."""
+        serves any number of `predict` calls (pfn_stack_condition).
+
+        train_lengths (a sequence or integer tensor [B], 0 <= value <= sep): dataset b has only its first train_lengths[b] rows; the rows behind them are padding
+        whose values reach no output (pfn_stack_condition_ragged).  Column b of every later `predict` is then what the dataset's own rows alone would give --
+        tabular tasks or optimisation runs of different sizes as one batch, instead of one B = 1 call each."""
         self._check_predict_model()
         x, y = src
+        lengths = None if train_lengths is None else check_train_lengths(train_lengths, x.shape[1], x.shape[0])
         _hip.require_gpu_tensor(x, 'x')
         _hip.require_gpu_tensor(next(self.parameters()), 'model parameters')
         sep, B, F = x.shape
@@ -566,6 +629,15 @@ class TransformerModel(nn.Module):
         desc, shadow = self._predict_operands(stream)
         nbytes = _hip.check(lib.pfn_context_bytes(ctypes.byref(desc), B, sep), 'pfn_context_bytes')
         buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        if lengths is not None:
+            sep_of = torch.tensor(lengths, dtype=torch.int32).to(x.device)
+            if sep > 0:
+                ws_bytes = _hip.check(lib.pfn_workspace_bytes(ctypes.byref(desc), B, sep), 'pfn_workspace_bytes')
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+                _hip.check(lib.pfn_stack_condition_ragged(ctypes.byref(desc), self._flat.data_ptr(), shadow.data_ptr(), x.data_ptr(), x.stride(0), x.stride(1),
+                                                          y.data_ptr(), y.stride(0), y.stride(1), B, sep, sep_of.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                          buf.data_ptr(), nbytes, stream), 'pfn_stack_condition_ragged')
+            return PredictContext(buf, self._predict_version(), desc.key(), B, F, sep, x.device, lengths, sep_of)
         if sep > 0:
             ws_bytes = _hip.check(lib.pfn_workspace_bytes(ctypes.byref(desc), B, sep), 'pfn_workspace_bytes')
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
@@ -573,6 +645,12 @@ class TransformerModel(nn.Module):
                                                y.data_ptr(), y.stride(0), y.stride(1), B, sep, ws.data_ptr(), ws_bytes, buf.data_ptr(), nbytes, stream),
                        'pfn_stack_condition')
         return PredictContext(buf, self._predict_version(), desc.key(), B, F, sep, x.device)
+
+    def condition_datasets(self, datasets):
+        """`condition` for datasets of different sizes given one by one: [(x_b [s_b, F], y_b [s_b]), ...] on the model's device, zero-padded to the longest
+        (`pad_datasets`) and conditioned with their own lengths."""
+        x, y, lengths = pad_datasets(datasets)
+        return self.condition((x, y), train_lengths=lengths)
 
     def predict(self, context, x_test):
         """Posterior-predictive logits [n, B, n_out] of the test rows x_test [n, B, F] given the conditioned training set: what model.eval() under
@@ -623,9 +701,14 @@ class TransformerModel(nn.Module):
             if ws is None or ws.numel() < ws_bytes:
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x_test.device)
             xc = x_test[t0:t0 + m]
-            _hip.check(lib.pfn_stack_predict(ctypes.byref(desc), self._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(), context.buffer.numel(),
-                                             context.sep, xc.data_ptr(), xc.stride(0), xc.stride(1), B, m, ws.data_ptr(), ws.numel(), out[t0:t0 + m].data_ptr(),
-                                             stream), 'pfn_stack_predict')
+            if context.lengths is not None:
+                _hip.check(lib.pfn_stack_predict_ragged(ctypes.byref(desc), self._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(),
+                                                        context.buffer.numel(), context.sep, context.sep_of.data_ptr(), xc.data_ptr(), xc.stride(0), xc.stride(1),
+                                                        B, m, ws.data_ptr(), ws.numel(), out[t0:t0 + m].data_ptr(), stream), 'pfn_stack_predict_ragged')
+            else:
+                _hip.check(lib.pfn_stack_predict(ctypes.byref(desc), self._flat.data_ptr(), shadow.data_ptr(), context.buffer.data_ptr(), context.buffer.numel(),
+                                                 context.sep, xc.data_ptr(), xc.stride(0), xc.stride(1), B, m, ws.data_ptr(), ws.numel(), out[t0:t0 + m].data_ptr(),
+                                                 stream), 'pfn_stack_predict')
         return self.decoder(out) if self._custom_decoder else out
 
     # ---- forward ----

@@ -424,6 +424,30 @@ int pfn_gp_posterior(const float* x, const float* y, float* K_ws, int64_t K_ws_b
                      int B, int S, int nf, int kernel, float* nll, float* mean, float* var,
                      int32_t* info, void* stream);
 
+/* ---- GP hyper-parameter fit (ABI 10, additive: a binding detects these three by symbol): the MAP-II baseline of the mixture-of-GPs prior, reference
+ * priors/fast_gp_mix.py:156-169 (`get_fitted_model`: botorch fit_gpytorch_model on gpytorch's ExactMarginalLogLikelihood).  Problem p uses the first
+ * n = n_of[p] rows of x[p] [S,nf] and y[p] [S]; its parameters are theta[p] [nf+3] = (log lengthscale_d, log outputscale, log(noise - noise_floor), constant
+ * mean c) and the objective is
+ *   J = -(1/n) [ log N(y_:n; c 1, K) + sum_d lg(l_d; a_l, b_l) + lg(os; a_o, b_o) + lg(noise; a_n, b_n) ],   K = os k(x, x; l) + noise I,
+ *   lg(v; a, b) = a log b - lgamma(a) + (a - 1) log v - b v         (Gamma log densities on the natural values, no Jacobian term, as gpytorch),
+ * prior [8] = (a_l, b_l, a_o, b_o, a_n, b_n, noise_floor, 0) on the device.  kernel as in pfn_gp_prior_sample.
+ * pfn_gp_mll_grad: value [P] = J, grad [P,nf+3] = dJ/dtheta (null: value only).  flags bit 0: c is held fixed, grad[c] = 0.  A non-positive pivot gives
+ *   info[p] = pivot + 1, value[p] = +inf, grad[p,:] = 0; the other problems are unaffected.  The result for problem p is a deterministic function of
+ *   (x[p], y[p], n_of[p], theta[p]): no atomics, independent of P and of the other problems of the call.
+ * pfn_gp_fit_predict: factorises by itself; for every test point x_test[p,j] the posterior under theta[p]: mean = c + (L^-1 k*) . (L^-1 (y - c)),
+ *   var = os + noise - |L^-1 k*|^2 (observation noise included).
+ * Both: caller-owned buffers, stream-ordered, no allocation, no device synchronisation.  S % 4 == 0, nf <= 126, P <= 65535.  n_of null = all S rows, else
+ * read on the device and clamped to [1, S]; rows >= n_of[p] of x / y are never read.  ws: pfn_gp_fit_workspace_bytes(P, S) bytes (two [P,Sp,Sp] f32
+ * matrices, Sp = S rounded up to 64: the factor / K^-1 and L^-1, plus vectors and per-tile partial sums); smaller returns PFN_ERR_ARGUMENT.  info [P] is
+ * written by the call (0 = ok). */
+int64_t pfn_gp_fit_workspace_bytes(int P, int S);
+int pfn_gp_mll_grad(const float* x, const float* y, const int32_t* n_of, const float* theta, const float* prior,
+                    int P, int S, int nf, int kernel, int flags, void* ws, int64_t ws_bytes,
+                    float* value, float* grad, int32_t* info, void* stream);
+int pfn_gp_fit_predict(const float* x, const float* y, const int32_t* n_of, const float* theta, const float* prior,
+                       int P, int S, int nf, int kernel, const float* x_test, int m, void* ws, int64_t ws_bytes,
+                       float* mean, float* var, int32_t* info, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

@@ -106,6 +106,11 @@ SIGNATURES = {
     'pfn_gp_workspace_bytes': (_L, [_I, _I]),
     'pfn_gp_prior_sample': (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P, _P]),
     'pfn_gp_posterior': (_I, [_P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    # GP hyper-parameter fit (ABI 10, additive).  (x, y, n_of, theta, prior, P, S, nf, kernel, flags, ws, ws_bytes, value, grad, info, stream)
+    'pfn_gp_fit_workspace_bytes': (_L, [_I, _I]),
+    'pfn_gp_mll_grad': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P]),
+    # (x, y, n_of, theta, prior, P, S, nf, kernel, x_test, m, ws, ws_bytes, mean, var, info, stream)
+    'pfn_gp_fit_predict': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P]),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

@@ -849,6 +849,14 @@ int launch_gp_sample(const GpArgs& a, hipStream_t s) {
     if (lds > 64 * 1024) return PFN_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(gp_gram_kernel, dim3(t * (t + 1) / 2, B), dim3(256), lds, s, a);
   }
+  return launch_gp_factor(a, s);
+}
+
+// The panel loop alone, on a matrix that is already filled (a.K lower triangle; posterior mode also a.y = the residual): what launch_gp_sample runs after its
+// Gram kernel, and what the hyper-parameter fit (gp_fit.hip) runs after its own masked Gram kernel.
+int launch_gp_factor(const GpArgs& a, hipStream_t s) {
+  const int S = a.S, B = a.B;
+  if (S % 4) return PFN_ERR_UNSUPPORTED;
   // Two-level right-looking blocked Cholesky.  Per 256-wide outer block:
   //   narrow chain (touches only the block's own <= 256 rows, at most B..4B workgroups, harmless to whatever
   //   shares the GPU): 64-wide panels  potrf -> trsm -> rank-64 update, all restricted to rows < kend;

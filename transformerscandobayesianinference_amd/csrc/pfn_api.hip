@@ -1507,6 +1507,41 @@ int pfn_gp_posterior(const float* x, const float* y, float* K_ws, int64_t K_ws_b
   return PFN_OK;
 }
 
+// ---- GP hyper-parameter fit (gp_fit.hip; ABI 10, additive) ----
+int64_t pfn_gp_fit_workspace_bytes(int P, int S) {
+  if (P < 1 || S < 1) return -1;
+  return gp_fit_workspace_bytes(P, S);
+}
+static int gp_fit_check(const float* x, const float* y, const float* theta, const float* prior, int P, int S, int nf, int kernel, void* ws, int64_t ws_bytes, int32_t* info) {
+  if (!x || !y || !theta || !prior || !ws || !info || P < 1 || S < 1 || nf < 1) return fail(PFN_ERR_ARGUMENT, "bad gp_fit arguments");
+  if (P > 65535) return fail(PFN_ERR_UNSUPPORTED, "P %d > 65535 problems per call", P);
+  if (S % 4) return fail(PFN_ERR_UNSUPPORTED, "S %d is not a multiple of 4", S);
+  if (nf > 126) return fail(PFN_ERR_UNSUPPORTED, "nf %d > 126 (the tiles stage 128 rows of x in 64 KB of LDS)", nf);
+  if (kernel < 0 || kernel > 3) return fail(PFN_ERR_UNSUPPORTED, "kernel %d (0 = RBF, 1 / 2 / 3 = Matern nu 5/2, 3/2, 1/2)", kernel);
+  if (ws_bytes < gp_fit_workspace_bytes(P, S)) return fail(PFN_ERR_ARGUMENT, "ws_bytes %lld < pfn_gp_fit_workspace_bytes = %lld", (long long)ws_bytes, (long long)gp_fit_workspace_bytes(P, S));
+  return PFN_OK;
+}
+int pfn_gp_mll_grad(const float* x, const float* y, const int32_t* n_of, const float* theta, const float* prior, int P, int S, int nf, int kernel, int flags,
+                    void* ws, int64_t ws_bytes, float* value, float* grad, int32_t* info, void* stream) {
+  if (int rc = gp_fit_check(x, y, theta, prior, P, S, nf, kernel, ws, ws_bytes, info)) return rc;
+  if (!value) return fail(PFN_ERR_ARGUMENT, "bad gp_mll_grad arguments");
+  GpFitArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.theta = theta; a.prior = prior; a.P = P; a.S = S; a.nf = nf; a.kernel = kernel; a.flags = flags;
+  a.ws = ws; a.value = value; a.grad = grad; a.info = info;
+  PFN_TRY(launch_gp_mll_grad(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_gp_fit_predict(const float* x, const float* y, const int32_t* n_of, const float* theta, const float* prior, int P, int S, int nf, int kernel,
+                       const float* x_test, int m, void* ws, int64_t ws_bytes, float* mean, float* var, int32_t* info, void* stream) {
+  if (int rc = gp_fit_check(x, y, theta, prior, P, S, nf, kernel, ws, ws_bytes, info)) return rc;
+  if (m < 0 || (m > 0 && (!x_test || !mean || !var))) return fail(PFN_ERR_ARGUMENT, "bad gp_fit_predict arguments");
+  GpFitArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.theta = theta; a.prior = prior; a.P = P; a.S = S; a.nf = nf; a.kernel = kernel; a.flags = 0;
+  a.ws = ws; a.x_test = x_test; a.m = m; a.mean = mean; a.var = var; a.info = info;
+  PFN_TRY(launch_gp_fit_predict(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
 int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
                           float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
                           uint64_t seed, uint64_t offset, void* stream) {

@@ -466,9 +466,31 @@ struct GpArgs {
 int64_t gp_workspace_bytes(int B, int S);      // K [B,S,S] f32 + the plane scratch
 void gp_attach_planes(GpArgs& a);               // points a.planes behind a.K (a workspace of gp_workspace_bytes)
 int launch_gp_sample(const GpArgs& a, hipStream_t s);
+int launch_gp_factor(const GpArgs& a, hipStream_t s);      // the blocked Cholesky (+ y = L z / w = L^-1 y) on an a.K that is already filled
 // Sequential exact-GP predictions from ONE factorisation: for every t, the posterior at x_t given points 0..t-1.
 //   mean[b,t], var[b,t] (with observation noise), nll[b,t] = -log N(y_t; mean, var);  resid_ws / w_ws: [B,S] scratch
 int launch_gp_posterior(const GpArgs& a, const float* y_data, float* nll, float* mean, float* var, hipStream_t s);
+
+// ---- GP hyper-parameter fit (gp_fit.hip): marginal likelihood + hyper-prior, its gradient, the fitted posterior ------
+struct GpFitArgs {
+  const float* x;        // [P,S,nf]
+  const float* y;        // [P,S]
+  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [1,S]); null = S
+  const float* theta;    // [P,nf+3]: log lengthscale_d, log outputscale, log(noise - floor), constant mean
+  const float* prior;    // [8]: a_l, b_l, a_o, b_o, a_n, b_n, noise_floor, 0
+  int P, S, nf, kernel, flags;
+  void* ws;              // gp_fit_workspace_bytes(P, S)
+  float* value;          // [P]
+  float* grad;           // [P,nf+3] or null
+  const float* x_test;   // [P,m,nf]   (predict)
+  int m;
+  float* mean;           // [P,m]
+  float* var;            // [P,m]
+  int32_t* info;         // [P]
+};
+int64_t gp_fit_workspace_bytes(int P, int S);
+int launch_gp_mll_grad(const GpFitArgs& a, hipStream_t s);
+int launch_gp_fit_predict(const GpFitArgs& a, hipStream_t s);
 
 // ---- BNN prior sampler (mlp_prior.hip) -----------------------------------------------------------
 struct MlpPriorArgs {

@@ -194,3 +194,48 @@ def qkv_projection(x, w_in, b_in, sep, center=True, sep_of=None):
     _hip.check(_hip.lib().pfn_op_qkv_projection(x.data_ptr(), w_in.data_ptr(), b_in.data_ptr(), qkv.data_ptr(), ks.data_ptr(), B, S, E, sep,
                                                 _hip.ptr(sep_of), int(center), PREC_OF[x.dtype], sp()), 'pfn_op_qkv_projection')
     return qkv, ks
+
+
+# ---- GP hyper-parameter fit (csrc/gp_fit.hip; include/pfn_hip.h "GP hyper-parameter fit") ----
+def gp_fit_workspace(P, S, device):
+    """The caller-owned workspace of pfn_gp_mll_grad / pfn_gp_fit_predict for P problems of S rows; reusable across calls of the same shape."""
+    return torch.empty(int(_hip.lib().pfn_gp_fit_workspace_bytes(P, S)), dtype=torch.uint8, device=device)
+
+
+def _gp_fit_inputs(x, y, theta, prior, n_of):
+    _hip.require_gpu_tensor(x, 'x')
+    P, S, F = x.shape
+    assert S % 4 == 0, 'S must be a multiple of 4 (pad and mask the padding through n_of)'
+    assert y.shape == (P, S) and theta.shape == (P, F + 3) and prior.shape == (8,)
+    for t in (x, y, theta, prior):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
+    if n_of is not None:
+        assert n_of.dtype == torch.int32 and n_of.shape == (P,) and n_of.is_contiguous() and n_of.device == x.device
+    return P, S, F
+
+
+def gp_mll_grad(x, y, theta, prior, kernel, n_of=None, flags=0, want_grad=True, ws=None):
+    """J(theta) and dJ/dtheta of the MAP-II objective per problem (pfn_gp_mll_grad).  x [P,S,F], y [P,S], theta [P,F+3], prior [8], n_of [P] int32 or None:
+    contiguous f32 / int32 tensors on the GPU.  Returns (value [P], grad [P,F+3] or None, info [P])."""
+    P, S, F = _gp_fit_inputs(x, y, theta, prior, n_of)
+    ws = gp_fit_workspace(P, S, x.device) if ws is None else ws
+    value = torch.empty(P, dtype=torch.float32, device=x.device)
+    grad = torch.empty(P, F + 3, dtype=torch.float32, device=x.device) if want_grad else None
+    info = torch.empty(P, dtype=torch.int32, device=x.device)
+    _hip.check(_hip.lib().pfn_gp_mll_grad(x.data_ptr(), y.data_ptr(), _hip.ptr(n_of), theta.data_ptr(), prior.data_ptr(), P, S, F, int(kernel), int(flags),
+                                          ws.data_ptr(), ws.numel(), value.data_ptr(), _hip.ptr(grad), info.data_ptr(), _hip.stream_ptr(x.device)), 'pfn_gp_mll_grad')
+    return value, grad, info
+
+
+def gp_fit_predict(x, y, theta, prior, kernel, x_test, n_of=None, ws=None):
+    """Posterior of the GP with parameters theta at x_test [P,m,F] (pfn_gp_fit_predict).  Returns (mean [P,m], var [P,m] with observation noise, info [P])."""
+    P, S, F = _gp_fit_inputs(x, y, theta, prior, n_of)
+    m = x_test.shape[1]
+    assert x_test.shape == (P, m, F) and x_test.dtype == torch.float32 and x_test.is_contiguous() and x_test.device == x.device
+    ws = gp_fit_workspace(P, S, x.device) if ws is None else ws
+    mean = torch.empty(P, m, dtype=torch.float32, device=x.device)
+    var = torch.empty(P, m, dtype=torch.float32, device=x.device)
+    info = torch.empty(P, dtype=torch.int32, device=x.device)
+    _hip.check(_hip.lib().pfn_gp_fit_predict(x.data_ptr(), y.data_ptr(), _hip.ptr(n_of), theta.data_ptr(), prior.data_ptr(), P, S, F, int(kernel), x_test.data_ptr(), m,
+                                             ws.data_ptr(), ws.numel(), mean.data_ptr(), var.data_ptr(), info.data_ptr(), _hip.stream_ptr(x.device)), 'pfn_gp_fit_predict')
+    return mean, var, info

@@ -15,14 +15,26 @@ gpytorch's memory and has no effect on the distribution, so the argument is acce
 divisibility check.  `y_minmax_norm`, `sigmoid` (:100-103) and the `fix_to_range` rejection step (:104-122) are
 kept.  Always exact Cholesky; nu in {0.5, 1.5, 2.5} (gpytorch MaternKernel's closed forms; the reference default is 2.5, :40).
 
-Model fitting / MCMC comparison code of the reference file (get_fitted_model, get_mcmc_model, evaluate_, :156-287)
-needs gpytorch / botorch / pyro and is out of scope.
+The MAP-II baseline of the reference (`get_fitted_model`, :156-169: botorch `fit_gpytorch_model` on gpytorch's ExactMarginalLogLikelihood, and
+`evaluate = partial(fast_gp.evaluate, get_model_on_device=get_fitted_model)`) is `fit_hyperparameters` / `get_fitted_model` / `evaluate` below: the
+objective and its gradient come from the device (`pfn_gp_mll_grad`, csrc/gp_fit.hip: one read of K^-1 for all ARD lengthscales), a batched L-BFGS in
+torch ops drives every problem of the batch at once, and `FittedGP.posterior` is `pfn_gp_fit_predict`.  The objective is gpytorch's (marginal log
+likelihood plus Gamma hyper-priors on the natural values, divided by n) in LOG parameters with the noise floor built into the parameterisation
+(noise = 1e-4 + exp(eta)) -- INTEGRATION.md lists both as deliberate deviations from softplus + an L-BFGS-B box.
+
+A pathology of the DEFAULT hyper-prior: outputscale_concentration = 0.5 makes the outputscale log-prior (a - 1) log os unbounded as os -> 0, so J has
+no minimum there (J -> -inf with the data explained by noise alone).  L-BFGS started at gpytorch's defaults (ln 2) finds the interior local optimum when
+there is one, as botorch does; `FittedGP.converged` and `.outputscale` show when it did not (a run-away outputscale ends at max_iter with
+converged False).  The tests fit with outputscale_concentration = 2.
+
+The MCMC comparison code of the reference file (get_mcmc_model, evaluate_, :172-287: pyro NUTS) is out of scope.
 """
+import math
 
 import torch
 from torch import nn
 
-from transformerscandobayesianinference_amd import _hip
+from transformerscandobayesianinference_amd import _hip, hipops
 from transformerscandobayesianinference_amd.bar_distribution import BarDistribution
 from transformerscandobayesianinference_amd.priors import fast_gp
 from transformerscandobayesianinference_amd.priors.utils import get_batch_to_dataloader
@@ -182,3 +194,261 @@ def get_model(x, y, hyperparameters: dict, sample=True):
                                   'fitting / MCMC baselines need gpytorch / botorch and are outside the MI355X hot path (SURVEY.md 2)')
     model = SampledGP(x, hyperparameters)
     return model, model.likelihood
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MAP-II: hyper-parameters fitted to the observed points (reference :156-169)
+# ---------------------------------------------------------------------------------------------------------------------
+def hyperprior_vector(hyperparameters, device=None, dtype=torch.float32):
+    """prior [8] of pfn_gp_mll_grad: (a_l, b_l, a_o, b_o, a_n, b_n, noise_floor, 0) with the keys and defaults of `sample_hyperparameters`."""
+    hp = hyperparameters or {}
+    return torch.tensor([hp.get('lengthscale_concentration', 3.0), hp.get('lengthscale_rate', 6.0), hp.get('outputscale_concentration', .5),
+                         hp.get('outputscale_rate', 0.15), hp.get('noise_concentration', 1.1), hp.get('noise_rate', 0.05), MIN_INFERRED_NOISE_LEVEL, 0.],
+                        dtype=dtype, device=device)
+
+
+def default_theta(P, num_features, hyperparameters, device=None, dtype=torch.float32):
+    """The start point, gpytorch's defaults: lengthscale_d = outputscale = softplus(0) = ln 2, noise = the prior mode (a_n - 1) / b_n (the prior mean when
+    the mode is not above the floor), constant mean 0.  theta = (log l_d, log os, log(noise - floor), c)."""
+    hp = hyperparameters or {}
+    a_n, b_n = float(hp.get('noise_concentration', 1.1)), float(hp.get('noise_rate', 0.05))
+    noise = (a_n - 1.) / b_n
+    if not noise > 2 * MIN_INFERRED_NOISE_LEVEL:
+        noise = max(a_n / b_n, 2 * MIN_INFERRED_NOISE_LEVEL)
+    theta = torch.zeros(P, num_features + 3, dtype=dtype, device=device)
+    theta[:, :num_features + 1] = math.log(math.log(2.))
+    theta[:, num_features + 1] = math.log(noise - MIN_INFERRED_NOISE_LEVEL)
+    return theta
+
+
+def batched_lbfgs(fun, theta0, max_iter=200, gtol=1e-5, ftol=1e-7, history=10, c1=1e-4, max_backtracks=20, sync_every=10, callback=None):
+    """L-BFGS (two-loop recursion over the last `history` pairs, Armijo backtracking) on P independent problems at once, in torch ops on [P, D] tensors of
+    theta0's device and dtype.  fun(theta [P,D]) -> (value [P], grad [P,D]) evaluates all of them in one call.  Every pass of the loop is ONE call of `fun`
+    at every problem's own trial point: a problem whose trial passes the Armijo test takes the step, updates its own history and direction and tries
+    step 1 next; one whose trial fails (or is not finite: a rejected step) halves its own step.  A problem is frozen by masking once it is done -- its
+    parameters are never written again -- and the batch is not resized.  Done means converged (|grad|_inf <= gtol; or an accepted step lowered the value
+    by <= ftol max(|f|, 1); or the quasi-Newton step predicts a decrease -g.d <= ftol max(|f|, 1)), failed (non-finite value at the start, or
+    `max_backtracks` halvings in a row twice with a reset to steepest descent in between), or out of iterations (max_iter accepted steps).  The host
+    looks at the device once every `sync_every` passes, to test "all done".
+    Returns dict(theta, objective, grad, iterations [accepted steps], converged, evaluations)."""
+    theta = theta0.clone()
+    P, D = theta.shape
+    f, g = fun(theta)
+    f, g = f.clone(), g.clone()
+    fin = torch.isfinite(f) & torch.isfinite(g).all(1)
+    g = torch.where(fin[:, None], g, torch.zeros_like(g))
+    converged = fin & (g.abs().amax(1) <= gtol)
+    done = converged | ~fin
+    iters = torch.zeros(P, dtype=torch.int64, device=theta.device)
+    backtracks = torch.zeros_like(iters)
+    restarted = torch.zeros(P, dtype=torch.bool, device=theta.device)
+    Sh = theta.new_zeros(history, P, D)
+    Yh = theta.new_zeros(history, P, D)
+    rho = theta.new_zeros(history, P)
+    one = theta.new_ones(P)
+
+    def first_step(g):
+        return torch.minimum(one, 1. / g.abs().sum(1).clamp_min(1e-30))
+
+    def direction(g, Sh, Yh, rho):
+        q = g.clone()
+        a = []
+        for i in range(history - 1, -1, -1):
+            ai = rho[i] * (Sh[i] * q).sum(1)
+            q = q - ai[:, None] * Yh[i]
+            a.append(ai)
+        yy = (Yh[-1] * Yh[-1]).sum(1)
+        gamma = torch.where(rho[-1] > 0, 1. / (rho[-1] * yy).clamp_min(1e-30), one)
+        r = gamma[:, None] * q
+        for i in range(history):
+            b = rho[i] * (Yh[i] * r).sum(1)
+            r = r + Sh[i] * (a[history - 1 - i] - b)[:, None]
+        return -r
+
+    d = -g
+    gd = (g * d).sum(1)
+    alpha = first_step(g)
+    evaluations = 1
+    for it in range(3 * max_iter + 2 * max_backtracks):
+        if it % sync_every == 0 and bool(done.all()):
+            break
+        trial = torch.where(done[:, None], theta, theta + alpha[:, None] * d)
+        ft, gt = fun(trial)
+        evaluations += 1
+        ok = ~done & torch.isfinite(ft) & torch.isfinite(gt).all(1)
+        ok = ok & (torch.where(ok, ft, f) <= f + c1 * alpha * gd)
+        okc = ok[:, None]
+        gt = torch.where(okc, gt, g)
+        # accepted steps: the pair (s, y) joins that problem's history when its curvature is positive
+        s, yv = trial - theta, gt - g
+        sy, yy = (s * yv).sum(1), (yv * yv).sum(1)
+        push = ok & (sy > 1e-10 * yy) & (yy > 0)
+        pc = push[None, :, None]
+        Sh = torch.where(pc, torch.cat([Sh[1:], s[None]]), Sh)
+        Yh = torch.where(pc, torch.cat([Yh[1:], yv[None]]), Yh)
+        rho = torch.where(push[None], torch.cat([rho[1:], (1. / torch.where(push, sy, one))[None]]), rho)
+        fscale = torch.maximum(torch.maximum(f.abs(), torch.where(ok, ft, f).abs()), one)
+        conv_f = ok & (f - ft <= ftol * fscale)
+        theta = torch.where(okc, trial, theta)
+        f = torch.where(ok, ft, f)
+        g = gt
+        iters = iters + ok
+        conv_g = ok & (g.abs().amax(1) <= gtol)
+        # rejected steps: halve; too many in a row: once from steepest descent with an empty history, then give up
+        rej = ~done & ~ok
+        backtracks = torch.where(rej, backtracks + 1, torch.zeros_like(backtracks))
+        stuck = rej & (backtracks > max_backtracks)
+        give_up = stuck & (restarted | (rho.amax(0) <= 0))
+        restart = stuck & ~give_up
+        restarted = (restarted | restart) & ~ok
+        rho = torch.where(restart[None], torch.zeros_like(rho), rho)
+        backtracks = torch.where(restart, torch.zeros_like(backtracks), backtracks)
+        d_new = direction(g, Sh, Yh, rho)
+        gd_new = (g * d_new).sum(1)
+        uphill = (ok | restart) & ~(gd_new < 0)
+        rho = torch.where(uphill[None], torch.zeros_like(rho), rho)
+        d_new = torch.where(uphill[:, None], -g, d_new)
+        gd_new = torch.where(uphill, -(g * g).sum(1), gd_new)
+        fresh = ok | restart
+        conv_d = ok & (-gd_new <= ftol * torch.maximum(f.abs(), one))
+        d = torch.where(fresh[:, None], d_new, d)
+        gd = torch.where(fresh, gd_new, gd)
+        alpha = torch.where(fresh, torch.where(rho.amax(0) > 0, one, first_step(g)), alpha * 0.5)
+        newly = conv_f | conv_g | conv_d
+        converged = converged | newly
+        done = done | newly | give_up | (iters >= max_iter)
+        if callback is not None:
+            callback(it, theta, done)
+    return dict(theta=theta, objective=f, grad=g, iterations=iters, converged=converged, evaluations=evaluations)
+
+
+class FittedGP:
+    """The GP with hyper-parameters fitted to (x, y) by MAP-II, one independent fit per problem of the batch: `lengthscale [P,F]`, `outputscale [P]`,
+    `noise [P]`, `mean [P]` (the constant mean), `objective [P]` (J at the optimum, nats per point), `iterations [P]`, `converged [P]`, `info [P]`
+    (0, or index + 1 of a non-positive pivot at the final point), `nu`, `kernel`.  Stands for both the model and the likelihood of the reference's
+    `get_fitted_model`; `posterior(x_test)` is the predictive distribution of y at x_test (observation noise included)."""
+
+    def __init__(self, x, y, n_of, theta, prior, kernel, nu, objective, iterations, converged, info, evaluations=None):
+        F = x.shape[-1]
+        self._x, self._y, self._n_of, self.theta, self._prior = x, y, n_of, theta, prior
+        self.kernel, self.nu = kernel, nu
+        self.lengthscale = theta[:, :F].exp()
+        self.outputscale = theta[:, F].exp()
+        self.noise = theta[:, F + 1].exp() + MIN_INFERRED_NOISE_LEVEL
+        self.mean = theta[:, F + 2].clone()
+        self.objective, self.iterations, self.converged, self.info, self.evaluations = objective, iterations, converged, info, evaluations
+        self.likelihood = self
+
+    @torch.no_grad()
+    def posterior(self, x_test):
+        """(mean [P,m], var [P,m]) at x_test [P,m,F] through pfn_gp_fit_predict."""
+        x_test = x_test.to(self._x.device).float()
+        if x_test.dim() == 2:
+            x_test = x_test.unsqueeze(0)
+        mean, var, _ = hipops.gp_fit_predict(self._x, self._y, self.theta, self._prior, self.kernel, x_test.contiguous(), n_of=self._n_of)
+        return mean, var
+
+
+def _kernel_of(hyperparameters, kernel):
+    nu = float((hyperparameters or {}).get('nu', 2.5))
+    if kernel is not None:
+        return int(kernel), nu
+    if nu not in fast_gp.MATERN_KERNEL_OF_NU:
+        raise ValueError(f'priors.fast_gp_mix: Matern nu must be 0.5, 1.5 or 2.5 (gpytorch MaternKernel, reference :40), got {nu}')
+    return fast_gp.MATERN_KERNEL_OF_NU[nu], nu
+
+
+@torch.no_grad()
+def fit_hyperparameters(x, y, hyperparameters=None, n_of=None, init=None, max_iter=200, gtol=1e-5, fit_mean=True, ftol=1e-7, kernel=None):
+    """MAP-II fit of P independent GPs: x [P,S,F], y [P,S] on the GPU; problem p uses its first n_of[p] rows (all S when None).  `hyperparameters` holds
+    the Gamma hyper-prior (keys and defaults of `sample_hyperparameters`) and `nu`; `kernel` overrides the covariance function (fast_gp.KERNEL_*).
+    init: a theta [P,F+3] tensor replacing the start point (`default_theta`).  fit_mean=False keeps the constant mean at its start value.
+    Returns a `FittedGP`."""
+    if x.device.type != 'cuda':
+        raise _hip.HipExtensionError(f'the GP hyper-parameter fit runs on the GPU only (got device {x.device}); no CPU fallback')
+    kernel, nu = _kernel_of(hyperparameters, kernel)
+    dev = x.device
+    P, S, F = x.shape
+    xp, yp = x.float(), y.float().reshape(P, S)
+    n_of = torch.full((P,), S, dtype=torch.int32, device=dev) if n_of is None else torch.as_tensor(n_of, device=dev).to(torch.int32).clamp(1, S).contiguous()
+    Sp = (S + 3) // 4 * 4
+    if Sp != S:      # padded rows are masked through n_of: nothing in them is read
+        xp = torch.cat([xp, xp.new_zeros(P, Sp - S, F)], 1)
+        yp = torch.cat([yp, yp.new_zeros(P, Sp - S)], 1)
+    xp, yp = xp.contiguous(), yp.contiguous()
+    prior = hyperprior_vector(hyperparameters, dev)
+    theta0 = default_theta(P, F, hyperparameters, dev) if init is None else torch.as_tensor(init, dtype=torch.float32, device=dev).reshape(P, F + 3).clone()
+    ws = hipops.gp_fit_workspace(P, Sp, dev)
+    flags = 0 if fit_mean else 1
+
+    def fun(theta):
+        value, grad, _ = hipops.gp_mll_grad(xp, yp, theta.contiguous(), prior, kernel, n_of=n_of, flags=flags, ws=ws)
+        return value, grad
+
+    res = batched_lbfgs(fun, theta0, max_iter=max_iter, gtol=gtol, ftol=ftol)
+    theta = res['theta'].contiguous()
+    _, _, info = hipops.gp_mll_grad(xp, yp, theta, prior, kernel, n_of=n_of, flags=flags, want_grad=False, ws=ws)
+    return FittedGP(xp, yp, n_of, theta, prior, kernel, nu, res['objective'], res['iterations'], res['converged'], info, res['evaluations'])
+
+
+def _reject_output_warping(hyperparameters):
+    hp = hyperparameters or {}
+    assert not (hp.get('sigmoid') or hp.get('y_minmax_norm')), 'Sigmoid and y_minmax_norm can only be used to sample models...'      # reference :54
+
+
+def get_fitted_model(x, y, hyperparameters, device):
+    """Reference :156-169: the model with hyper-parameters fitted to (x, y) and its likelihood -- here one object plays both parts.  x [n,F] or [P,n,F],
+    y [n], [n,1] or [P,n].  Does not go through `get_model(sample=False)`, which keeps raising."""
+    _reject_output_warping(hyperparameters)
+    x = torch.as_tensor(x).to(device).float()
+    x = x if x.dim() == 3 else x.unsqueeze(0)
+    y = torch.as_tensor(y).to(device).float().reshape(x.shape[0], x.shape[1])
+    model = fit_hyperparameters(x, y, hyperparameters)
+    return model, model.likelihood
+
+
+EVALUATE_MEMORY_SHARE = 0.125      # a group of problems keeps its workspace inside this share of the free device memory, as the prefetching loaders do
+EVALUATE_MAX_GROUP = 4096
+
+
+@torch.no_grad()
+def evaluate(x, y, y_non_noisy, use_mse=False, hyperparameters={}, device=default_device, step_size=1, start_pos=0):
+    """The MAP-II baseline (reference: `partial(fast_gp.evaluate, get_model_on_device=get_fitted_model)`): for every t in
+    range(max(start_pos, 1), T, step_size) and every dataset b, hyper-parameters are fitted on rows [:t] of (x[:, b], y[:, b]) and the loss is taken at row
+    t -- the negative log density of y[t] under the fitted predictive, or the squared error of its mean.  x [T,B,F], y [T,B]; returns what
+    `fast_gp.evaluate` returns: (losses [n_t, B] on the CPU, their means per t with a leading 0. when start_pos == 0, seconds).  All (t, b) problems are
+    batched: they are grouped by n = t rounded up to a multiple of 64 (so padding costs at most a bucket) and every group is cut to
+    EVALUATE_MEMORY_SHARE of the free device memory."""
+    import time
+    start_time = time.time()
+    _reject_output_warping(hyperparameters)
+    dev = torch.device(device)
+    T, B, F = x.shape
+    xb = x.to(dev).float().transpose(0, 1).contiguous()
+    yb = y.to(dev).float().reshape(T, B).transpose(0, 1).contiguous()
+    ts = list(range(max(start_pos, 1), T, step_size))
+    losses = torch.zeros(len(ts), B, dtype=torch.float32, device=dev)
+    buckets = {}
+    for i, t in enumerate(ts):
+        buckets.setdefault((t + 63) // 64 * 64, []).append(i)
+    for Sb, members in sorted(buckets.items()):
+        xs, ys = xb[:, :Sb], yb[:, :Sb]
+        if Sb > T:
+            xs = torch.cat([xs, xs.new_zeros(B, Sb - T, F)], 1)
+            ys = torch.cat([ys, ys.new_zeros(B, Sb - T)], 1)
+        per_problem = max(1, int(_hip.lib().pfn_gp_fit_workspace_bytes(1, Sb)) + 8 * Sb * (F + 1))
+        cap = max(1, min(EVALUATE_MAX_GROUP, int(EVALUATE_MEMORY_SHARE * torch.cuda.mem_get_info(dev)[0]) // per_problem))
+        ii = torch.as_tensor([i for i in members for _ in range(B)], dtype=torch.long, device=dev)
+        tt = torch.as_tensor([ts[i] for i in members for _ in range(B)], dtype=torch.long, device=dev)
+        bb = torch.arange(B, device=dev).repeat(len(members))
+        for lo in range(0, len(tt), cap):
+            i_, t_, b_ = ii[lo:lo + cap], tt[lo:lo + cap], bb[lo:lo + cap]
+            model = fit_hyperparameters(xs[b_], ys[b_], hyperparameters, n_of=t_)
+            mean, var = model.posterior(xb[b_, t_].unsqueeze(1))
+            mean, var, target = mean[:, 0], var[:, 0], yb[b_, t_]
+            losses[i_, b_] = (mean - target) ** 2 if use_mse else 0.5 * torch.log(2 * math.pi * var) + (target - mean) ** 2 / (2 * var)
+    per_t = losses.mean(1)
+    if start_pos == 0:
+        per_t = torch.cat([per_t.new_zeros(1), per_t])
+    torch.cuda.synchronize(dev)
+    return losses.to('cpu'), per_t.to('cpu'), time.time() - start_time

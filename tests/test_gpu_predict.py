@@ -64,6 +64,8 @@ CASES = [
     ('fp16', 'f32', 256, 2, 437, 7, 3),         # an fp16 model's default inference: the exact-f32 kernels
     ('fp16', 'f32', 512, 4, 2000, 300, 8),
     ('fp16', 'f32', 128, 4, 1, 1, 1),
+    ('fp16', 'same', 1024, 4, 63, 7, 3),        # fp16 sums ahead of a separate LayerNorm (emsize 1024)
+    ('bf16', 'same', 64, 2, 63, 7, 3),          # a narrow width that no fused kernel takes
 ]
 BOUND = {'f32': 2.5e-6, 'fp16': 1e-3, 'bf16': 6e-3}      # measured 1.0e-6 / 5.7e-4 / 2.6e-3 (profiles/r07_predict_bounds_measured.json); fp16 at the issue's ceiling
 

@@ -169,8 +169,9 @@ static bool key_centering(const pfn_model_desc& d) {
 // (The buffers keep their f32 size: a descriptor-only rule must not decide a layout the pointer-alignment probe in the forward can still overrule.)
 static bool residual16(const pfn_model_desc& d) {
   const int E = d.emsize;
+  const bool wide = (d.schedule & PFN_SCHED_FUSE_LN_WIDE) != 0;
   return d.precision == PFN_PREC_FP16 && !(d.schedule & PFN_SCHED_F32_RESIDUAL) && d.nlayers > 0 && d.dropout == 0.f && d.nhid % 32 == 0 &&
-         (E == 128 || E == 256 || E == 512 || (E == 1024 && (d.schedule & PFN_SCHED_FUSE_LN_WIDE)));
+         (E == 128 || E == 256 || E == 512 || (E == 1024 && wide));
 }
 // ... and where the LayerNorm stays its own kernel (emsize 1024 by default: the wide fused kernels lose there) an fp16 model runs the same streams in fp16: the GEMM in
 // front takes its residual from the operand-precision copy of the LayerNorm output and stores the sum in fp16, layernorm_fwd reads that and writes the operand copy
@@ -179,13 +180,6 @@ static bool residual16_separate_ln(const pfn_model_desc& d, bool ln_fusable) {
   // (from emsize 1024 on: there the streams are the kernels' bound.  Narrow unfusable widths keep f32 -- nothing to gain, and here the ROUNDED sum is what the
   // LayerNorm normalises, so the rounding reaches the operands and not only the residual path: measured 1.3 x on the logits at emsize 1024, 4 x at 64)
   return d.precision == PFN_PREC_FP16 && !(d.schedule & PFN_SCHED_F32_RESIDUAL) && d.nlayers > 0 && d.dropout == 0.f && d.emsize >= 1024 && d.emsize % 8 == 0 && !ln_fusable;
-}
-// can out_proj / linear2 run as gemm_nt_ln_kernel at all (shapes, 16-byte alignment of every stream)?  The forward and the backward ask the same question.
-static bool ln_gemm_probe(const pfn_model_desc& d, const Ws& w, const float* params, const void* sh, int M) {
-  GemmLN probe; memset(&probe, 0, sizeof(probe));
-  probe.A = w.x0_t; probe.lda = d.emsize; probe.B = sh; probe.ldb = d.emsize; probe.M = M; probe.N = d.emsize; probe.K = d.emsize;
-  probe.bias = params; probe.gamma = params; probe.beta = params; probe.resid = w.x0; probe.y = w.x0; probe.x_t = w.x0_t;
-  return gemm_ln_supported(probe);
 }
 
 Ws carve(const pfn_model_desc& d, int B, int S, char* base) {
@@ -322,6 +316,272 @@ GemmTN tn(const void* A, long lda, const void* B, long ldb, float* C, long ldc, 
   return g;
 }
 
+// ---- what the schedules share: the training forward / backward and the predict forward / backward are built from the pieces below --------------------------------
+// A pass's constants: the descriptor, the f32 parameters, their operand-precision shadow (W) with its transposed half (WT), the layout, the launch stream
+struct Model { const pfn_model_desc* d; const float* params; const char* sh; const Layout* L; hipStream_t s; };
+inline const void* W(const Model& m, int64_t off) { return m.sh + off * esize(m.d->precision); }
+inline const void* WT(const Model& m, int64_t off) { return m.sh + (m.L->total + off) * esize(m.d->precision); }
+constexpr int NO_PROF = -PFN_PROF_SLOTS;      // profile-slot offset of a pass that records nothing (a predict pass): prof_begin ignores the negative slots it yields
+
+int check_context(const pfn_model_desc& d, int B, int sep, const void* context, int64_t context_bytes, Context* c) {
+  *c = context_layout(d, B, sep);
+  if (sep > 0 && d.nlayers > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context with sep=%d", sep);
+  if (context_bytes < c->bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)c->bytes);
+  return PFN_OK;
+}
+
+// can out_proj / linear2 run as gemm_nt_ln_kernel at all (shapes, 16-byte alignment of every stream)?  x0 / x0_t: the embedding output of the pass, f32 and operand precision
+bool ln_gemm_probe(const pfn_model_desc& d, float* x0, void* x0_t, const float* params, const void* sh, int M) {
+  GemmLN probe; memset(&probe, 0, sizeof(probe));
+  probe.A = x0_t; probe.lda = d.emsize; probe.B = sh; probe.ldb = d.emsize; probe.M = M; probe.N = d.emsize; probe.K = d.emsize;
+  probe.bias = params; probe.gamma = params; probe.beta = params; probe.resid = x0; probe.y = x0; probe.x_t = x0_t;
+  return gemm_ln_supported(probe);
+}
+
+// The decisions that fix the memory layout between a forward and its backward, taken once per pass from the descriptor, the pass's rows and the live dropout probability.
+struct Plan {
+  bool ln_ok;      // ln_gemm_probe
+  // out_proj and linear2 run fused with their residual add and LayerNorm (gemm_nt_ln_kernel) when the shape allows: the f32 LayerNorm output is then never
+  // stored -- the next residual add recomputes it from the pre-LN sum and the row statistics -- except after the last layer, whose f32 output feeds the decoder gather.
+  // (dropout sits between the bias and the residual add: it takes the unfused GEMM / LayerNorm kernels with an element-wise pass between)
+  // (emsize 1024: the 64-row fused kernels exist and are correct, but lose to GEMM + LayerNorm kernels -- PFN_SCHED_FUSE_LN_WIDE)
+  bool fuse_ln;
+  bool y16;        // the pre-LayerNorm sums in operand precision inside the fused GEMMs (residual16; implies fuse_ln: the descriptor's dropout is 0, so is the live one)
+  bool y16u;       // the same ahead of a separate LayerNorm (residual16_separate_ln; implies !fuse_ln)
+  bool y16_any;    // either: how a backward reads y1 / y2
+  // the two GEMMs whose output is the gradient w.r.t. a LayerNorm output may run that LayerNorm's backward in their epilogue, as far as the descriptor decides
+  // (lnbwd_fusable asks the kernel); dropout: masked and unmasked LayerNorm-input gradients both exist
+  bool lnb_eligible;
+};
+Plan make_plan(const pfn_model_desc& d, float* x0, void* x0_t, const float* params, const void* sh, int M, float pdrop) {
+  Plan pl;
+  const int E = d.emsize, sched = d.schedule;
+  const bool width_ok = (E <= 512 || (sched & PFN_SCHED_FUSE_LN_WIDE));
+  pl.ln_ok = ln_gemm_probe(d, x0, x0_t, params, sh, M);
+  const bool ln_fusable = pl.ln_ok && d.nhid % 32 == 0 && width_ok;
+  pl.fuse_ln = prec_is16(d.precision) && ln_fusable && pdrop == 0.f;
+  pl.y16 = residual16(d) && pl.ln_ok;
+  pl.y16u = residual16_separate_ln(d, ln_fusable);
+  pl.y16_any = pl.y16 || pl.y16u;
+  pl.lnb_eligible = !(sched & PFN_SCHED_DETERMINISTIC) && !(sched & PFN_SCHED_SEPARATE_LNBWD) && prec_is16(d.precision) && d.nlayers > 0 && pdrop == 0.f && width_ok;
+  return pl;
+}
+
+// The embedding's weight gradients d(src)^T . [x | masked y | train flag] are a (skinny) weight-gradient GEMM like the others: embed_fwd left the augmented inputs in
+// operand precision, the first layer's dx leaves in operand precision (gA_t, loss-scaled), and the split-K TN kernel does the rest (the register kernel it replaces
+// streamed d(src) at 0.7 TB/s).  Custom encoders (dsrc_sbe), the exact-f32 mode and wide encoders keep the f32 path (gA).  pfn_stack_input_grads reads d(src) by this rule.
+bool emb_gemm(const pfn_model_desc& d, bool custom_encoder) {
+  return !custom_encoder && prec_is16(d.precision) && d.nlayers > 0 && emb_aug_width(d.num_features) > 0 && d.emsize % 8 == 0;
+}
+// A predict backward computes no weight gradient, so its d(src) does not wait on the augmented-input operand: operand precision (gA_t) whenever a 16-bit chain produced it
+bool predict_dsrc_is_t(const pfn_model_desc& d) { return d.nlayers > 0 && prec_is16(d.precision); }
+
+// where a layer's input lives in f32: plain, or as the LayerNorm that produced it (pre-LN sum, row statistics, weight and bias -- GemmLN recomputes it)
+struct Resid { const float* plain; const void* y; const float* mean; const float* rstd; const float* gamma; const float* beta; };
+void set_resid(GemmLN& g, const Resid& r) { g.resid = r.plain; g.ry = r.y; g.rmean = r.mean; g.rrstd = r.rstd; g.rgamma = r.gamma; g.rbeta = r.beta; }
+// the buffers of one layer's forward: the layer input, q|k|v, ctx, what LN1 leaves, h, hpre and the output.  x2: the f32 output, read only after the last layer.
+struct LayerBufs { const float* xin; const char* xin_t; char *qkv, *ctx; float* lse; float *y1, *mean1, *rstd1, *x1; char *x1_t, *h, *hpre; float *y2, *mean2, *rstd2, *x2; char* x2_t; };
+
+// One encoder layer behind its attention: x1 = LN1(x + out_proj(ctx)), h = gelu(linear1(x1)), x2 = LN2(x1 + linear2(h)) on `rows` rows.
+// pdrop > 0: the three element-wise dropout sites are live, seed[site] their seeds.  prof: 0 / 1 (a top layer on the test rows) / NO_PROF.
+int layer_tail_forward(const Model& m, const LayerP& p, const LayerBufs& u, Resid& res, int rows, const Plan& pl, float pdrop, const unsigned* seed, bool last, int prof) {
+  const pfn_model_desc& d = *m.d;
+  const int prec = d.precision, E = d.emsize, F = d.nhid;
+  const float* params = m.params;
+  hipStream_t s = m.s;
+  const bool y16u = pl.y16u;
+  if (pl.fuse_ln) {  // x1 = LN1(x + out_proj(ctx))
+    ProfScope ps(PFN_PROF_GEMM_OUT_LN + prof, s);
+    GemmLN g; memset(&g, 0, sizeof(g));
+    g.A = u.ctx; g.lda = E; g.B = W(m, p.w_o); g.ldb = E; g.M = rows; g.N = E; g.K = E; g.bias = params + p.b_o;
+    set_resid(g, res);
+    g.gamma = params + p.g1; g.beta = params + p.be1; g.eps = d.ln_eps;
+    g.y = u.y1; g.mean = u.mean1; g.rstd = u.rstd1; g.x_t = u.x1_t; g.y16 = pl.y16;
+    PFN_TRY(launch_gemm_ln(g, prec, s));
+    res = Resid{nullptr, u.y1, u.mean1, u.rstd1, params + p.g1, params + p.be1};
+  } else {
+    {  // out_proj + residual  (dropout1: the product leaves alone and the element-wise pass adds the residual)
+      GemmNT g = nt(u.ctx, E, W(m, p.w_o), E, rows, E, E, EPI_BIAS | (pdrop > 0.f ? 0 : EPI_RESID) | EPI_OUT_F32);
+      g.bias = params + p.b_o; g.resid = u.xin; g.ld_resid = E; g.out_f32 = u.y1; g.ld_out_f32 = E;
+      // fp16 sums: the residual from the operand-precision layer input, the sum out in operand precision
+      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = u.xin_t; g.ld_aux = E; g.out_t = u.y1; g.ld_out_t = E; }
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+      if (pdrop > 0.f) PFN_TRY(launch_dropout_add(u.y1, u.xin, rows, E, seed[1], pdrop, s));
+    }
+    PFN_TRY(launch_layernorm_fwd(u.y1, params + p.g1, params + p.be1, y16u ? nullptr : u.x1, u.x1_t, u.mean1, u.rstd1, rows, E, d.ln_eps, prec, s, y16u));
+  }
+  {  // linear1 + GELU (the GELU derivative kept for the backward)
+    ProfScope ps(PFN_PROF_GEMM_LIN1 + prof, s);
+    GemmNT g = nt(u.x1_t, E, W(m, p.w1), E, rows, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
+    g.bias = params + p.b1; g.out_t = u.h; g.ld_out_t = F; g.out2_t = u.hpre; g.ld_out2 = F;
+    PFN_TRY(launch_gemm_nt(g, prec, s));
+    // FFN dropout: h and the stored GELU derivative take the same mask, so linear2, its weight gradient and d(hpre) need nothing more
+    if (pdrop > 0.f) PFN_TRY(launch_dropout_scale(u.h, u.h, u.hpre, u.hpre, rows, F, seed[2], pdrop, prec, s));
+  }
+  if (pl.fuse_ln) {  // x2 = LN2(x1 + linear2(h))
+    ProfScope ps(PFN_PROF_GEMM_LIN2_LN + prof, s);
+    GemmLN g; memset(&g, 0, sizeof(g));
+    g.A = u.h; g.lda = F; g.B = W(m, p.w2); g.ldb = F; g.M = rows; g.N = E; g.K = F; g.bias = params + p.b2;
+    set_resid(g, res);
+    g.gamma = params + p.g2; g.beta = params + p.be2; g.eps = d.ln_eps;
+    g.y = u.y2; g.mean = u.mean2; g.rstd = u.rstd2; g.x_t = u.x2_t; g.y16 = pl.y16;
+    g.x_f32 = last ? u.x2 : nullptr;
+    PFN_TRY(launch_gemm_ln(g, prec, s));
+    res = Resid{nullptr, u.y2, u.mean2, u.rstd2, params + p.g2, params + p.be2};
+  } else {
+    {  // linear2 + residual  (dropout2 as above)
+      GemmNT g = nt(u.h, F, W(m, p.w2), F, rows, E, F, EPI_BIAS | (pdrop > 0.f ? 0 : EPI_RESID) | EPI_OUT_F32);
+      g.bias = params + p.b2; g.resid = u.x1; g.ld_resid = E; g.out_f32 = u.y2; g.ld_out_f32 = E;
+      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = u.x1_t; g.ld_aux = E; g.out_t = u.y2; g.ld_out_t = E; }
+      PFN_TRY(launch_gemm_nt(g, prec, s));
+      if (pdrop > 0.f) PFN_TRY(launch_dropout_add(u.y2, u.x1, rows, E, seed[3], pdrop, s));
+    }
+    // (fp16 sums: only the last layer's f32 output has a reader -- the decoder gather, or the caller when there is no decoder)
+    PFN_TRY(launch_layernorm_fwd(u.y2, params + p.g2, params + p.be2, (y16u && !last) ? nullptr : u.x2, u.x2_t, u.mean2, u.rstd2, rows, E, d.ln_eps, prec, s, y16u));
+  }
+  return PFN_OK;
+}
+
+// The decoder on `rows` compact test rows: dt = gelu(dec0(xt)) with the GELU derivative (dpre) kept for the backward, logits = dec2(dt) in f32
+int decoder_forward(const Model& m, const void* xt_t, char* dt, char* dpre, float* logits, int rows) {
+  const int prec = m.d->precision, E = m.d->emsize, F = m.d->nhid, O = m.d->n_out;
+  {
+    GemmNT g = nt(xt_t, E, W(m, m.L->dec0_w), E, rows, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
+    g.bias = m.params + m.L->dec0_b; g.out_t = dt; g.ld_out_t = F; g.out2_t = dpre; g.ld_out2 = F;
+    PFN_TRY(launch_gemm_nt(g, prec, m.s));
+  }
+  GemmNT g = nt(dt, F, W(m, m.L->dec2_w), F, rows, O, F, EPI_BIAS | EPI_OUT_F32);
+  g.bias = m.params + m.L->dec2_b; g.out_f32 = logits; g.ld_out_f32 = O;
+  return launch_gemm_nt(g, prec, m.s);
+}
+// ... and its data gradients: dlog_t [rows, n_out_pad] (dlogits in operand precision, zero padded) -> dd_t = (dlog . W_dec2) * gelu'(dpre) -> dxt = dd . W_dec0 (f32)
+int decoder_backward_data(const Model& m, const void* dlog_t, const void* dpre, char* dd_t, float* dxt, int rows) {
+  const int prec = m.d->precision, E = m.d->emsize, F = m.d->nhid, O = m.d->n_out, npad = m.L->n_out_pad;
+  {
+    // (contraction over the zero-padded width when that is whole 64-deep stages: the LDS-DMA kernel then takes it)
+    GemmNT g = nt(dlog_t, npad, WT(m, m.L->dec2_wt), npad, rows, F, npad % 64 == 0 ? npad : O, EPI_GELU_BWD | EPI_OUT_T);
+    g.aux = dpre; g.ld_aux = F; g.out_t = dd_t; g.ld_out_t = F;
+    PFN_TRY(launch_gemm_nt(g, prec, m.s));
+  }
+  GemmNT g = nt(dd_t, F, WT(m, m.L->dec0_wt), F, rows, E, F, EPI_OUT_F32);
+  g.out_f32 = dxt; g.ld_out_f32 = E;
+  return launch_gemm_nt(g, prec, m.s);
+}
+
+// Weight-gradient problems contracted over `rows` rows: grouped launches of 256 x 256 tiles (TN_GROUP_MAX problems each) when every problem is supported, else --
+// exact-f32 parity mode and shapes outside the 256-tile kernel -- one split-K launch per gradient.  det: PFN_SCHED_DETERMINISTIC (no token splits).
+// allow_group = false: a part of a set that is launched one by one.
+bool tn_set_groupable(const std::vector<TnProblem>& probs, int prec) {
+  bool grouped = prec_is16(prec);
+  for (const TnProblem& t : probs) grouped = grouped && gemm_tn_group_supported(t);
+  return grouped;
+}
+int launch_tn_set(const std::vector<TnProblem>& probs, int rows, int prec, bool det, const float* lsc, int prof_slot, hipStream_t s, bool allow_group = true) {
+  if (!(allow_group && tn_set_groupable(probs, prec))) {
+    for (const TnProblem& t : probs) {
+      GemmTN g = tn(t.A, t.lda, t.B, t.ldb, t.C, t.ldc, rows, t.Pv ? t.Pv : t.P, t.Q, t.colsum);
+      if (det) g.max_splits = 1;
+      g.scale_amax = lsc;
+      PFN_TRY(launch_gemm_tn(g, prec, s));
+    }
+    return PFN_OK;
+  }
+  for (size_t i0 = 0; i0 < probs.size(); i0 += TN_GROUP_MAX) {
+    ProfScope ps(prof_slot, s);
+    GemmTNGroup g;
+    memset(&g, 0, sizeof(g));
+    g.n = (int)std::min<size_t>(TN_GROUP_MAX, probs.size() - i0);
+    g.M = rows;
+    g.splits = det ? 1 : 0;
+    g.scale_amax = lsc;
+    for (int i = 0; i < g.n; ++i) g.p[i] = probs[i0 + i];
+    PFN_TRY(launch_gemm_tn_group(g, prec, s));
+  }
+  return PFN_OK;
+}
+
+// where a LayerNorm backward adds its parameter sums.  dbias: the column sums of its input gradient (the bias gradient of the Linear in front) from the separate
+// kernel; nullptr when the weight-gradient GEMM that reads the same operand takes them.  The fused GEMM writes dgamma / dbeta only.
+struct LnSinks { float *dgamma, *dbeta, *dbias; };
+// One layer's part of a backward chain.  dout: the gradient w.r.t. the layer output (f32, or operand precision when dout_is_t), unread when the layer above ran this
+// layer's LN2 backward in its dx GEMM; y / mean / rstd / gamma: what the forward kept of the two LayerNorms; dx1_t: scratch of the unfused dx1.
+struct LayerGrads {
+  const void* dout; int dout_is_t;
+  const void* y2; const float *mean2, *rstd2, *gamma2; const void* y1; const float *mean1, *rstd1, *gamma1; const void* hpre;
+  char *dy2_t, *dy2m_t, *dh_t, *dy1_t, *dqkv_t, *dx1_t;      // dy2m_t: dy2 times the dropout2 mask (dropout > 0 only)
+  LnSinks ln2, ln1;
+  float* ln_part;      // PFN_SCHED_DETERMINISTIC: Ws::ln_part
+};
+// A data-gradient GEMM with a LayerNorm backward in its epilogue (gemm_nt_lnbwd_kernel): dx_t = LN'(A . Bw^T + aux) through (y, mean, rstd, gamma) on `rows` rows
+GemmLNB lnb(const Model& m, const Plan& pl, const float* lsc, const void* A, long lda, const void* Bw, long ldb, int K, const void* aux, const void* y,
+            const float* mean, const float* rstd, const float* gamma, void* dx_t, const LnSinks& sink, int rows) {
+  GemmLNB g; memset(&g, 0, sizeof(g));
+  g.A = A; g.lda = lda; g.B = Bw; g.ldb = ldb; g.M = rows; g.N = m.d->emsize; g.K = K; g.aux = aux;
+  g.y = y; g.mean = mean; g.rstd = rstd; g.gamma = gamma; g.dx_t = dx_t; g.dgamma = sink.dgamma; g.dbeta = sink.dbeta; g.scale_amax = lsc; g.y16 = pl.y16_any;
+  return g;
+}
+// dy1 = LN1 backward of (dh . W1 + dy2), and dy2 of the layer below = its LN2 backward of (dqkv . Win + dy1): the two fused launches of a chain
+GemmLNB lnb_dy1(const Model& m, const Plan& pl, const float* lsc, const LayerP& t, const LayerGrads& g, int rows) {
+  const int F = m.d->nhid;
+  return lnb(m, pl, lsc, g.dh_t, F, WT(m, t.w1), F, F, g.dy2_t, g.y1, g.mean1, g.rstd1, g.gamma1, g.dy1_t, g.ln1, rows);
+}
+GemmLNB lnb_dx(const Model& m, const Plan& pl, const float* lsc, const LayerP& t, const char* dqkv_t, const char* dy1_t, const LayerGrads& below, int rows) {
+  const int E = m.d->emsize;
+  return lnb(m, pl, lsc, dqkv_t, 3 * E, WT(m, t.w_in), 3 * E, 3 * E, dy1_t, below.y2, below.mean2, below.rstd2, below.gamma2, below.dy2_t, below.ln2, rows);
+}
+// do both fused launches exist for this pass?  g0: layer 0 (every layer has its shapes and alignment)
+bool lnbwd_fusable(const Model& m, const Plan& pl, const float* lsc, const LayerGrads& g0, int rows) {
+  const LayerP& t = m.L->layer_t[0];
+  return pl.lnb_eligible && gemm_lnbwd_supported(lnb_dy1(m, pl, lsc, t, g0, rows)) && gemm_lnbwd_supported(lnb_dx(m, pl, lsc, t, g0.dqkv_t, g0.dy1_t, g0, rows));
+}
+// From the gradient of the layer output to dy1, the gradient of LN1's input (the operand of d(ctx) and of out_proj's weight gradient).
+// LN2: the input gradient leaves only in operand precision (dy2_t); it is both the GEMM operand below and the residual-branch gradient that the dx1 GEMM adds back,
+// so no f32 copy is written or re-read.  ln2_done: the layer above already left dy2_t.
+// dropout (pdrop > 0, seed2 = the dropout2 site): the gradient entering linear2 is the LayerNorm-input gradient times that site's mask; the residual path keeps the
+// unmasked one, and the bias gradient becomes a column sum of the masked operand (the weight-gradient launch).
+int layer_backward_to_dy1(const Model& m, const LayerP& t, const LayerGrads& g, int rows, const Plan& pl, bool fuse_lnb, bool ln2_done, const float* lsc,
+                          float pdrop, unsigned seed2, int prof) {
+  const int prec = m.d->precision, E = m.d->emsize, F = m.d->nhid;
+  hipStream_t s = m.s;
+  if (!ln2_done)
+    PFN_TRY(launch_layernorm_bwd(g.dout, g.dout_is_t, g.y2, g.gamma2, g.mean2, g.rstd2, nullptr, g.dy2_t, g.ln2.dgamma, g.ln2.dbeta, g.ln2.dbias, rows, E, prec, s,
+                                 g.ln_part, lsc, pl.y16_any));
+  const char* dy2_op = g.dy2_t;
+  if (pdrop > 0.f) { PFN_TRY(launch_dropout_scale(g.dy2_t, g.dy2m_t, nullptr, nullptr, rows, E, seed2, pdrop, prec, s)); dy2_op = g.dy2m_t; }
+  {  // d(hpre) = (dy2 . W2) * gelu'(hpre)
+    ProfScope ps(PFN_PROF_GEMM_DHPRE + prof, s);
+    GemmNT gm = nt(dy2_op, E, WT(m, t.w2), E, rows, F, E, EPI_GELU_BWD | EPI_OUT_T);
+    gm.aux = g.hpre; gm.ld_aux = F; gm.out_t = g.dh_t; gm.ld_out_t = F;
+    PFN_TRY(launch_gemm_nt(gm, prec, s));
+  }
+  if (fuse_lnb) {  // dy1 = LN1 backward of (dh . W1 + dy2)
+    ProfScope ps(PFN_PROF_GEMM_DY1 + prof, s);
+    PFN_TRY(launch_gemm_lnbwd(lnb_dy1(m, pl, lsc, t, g, rows), prec, s));
+  } else {
+    {  // dx1 = dh . W1 + dy2
+      GemmNT gm = nt(g.dh_t, F, WT(m, t.w1), F, rows, E, F, EPI_RESID_T | EPI_OUT_T);
+      gm.aux = g.dy2_t; gm.ld_aux = E; gm.out_t = g.dx1_t; gm.ld_out_t = E;
+      PFN_TRY(launch_gemm_nt(gm, prec, s));
+    }
+    PFN_TRY(launch_layernorm_bwd(g.dx1_t, 1, g.y1, g.gamma1, g.mean1, g.rstd1, nullptr, g.dy1_t, g.ln1.dgamma, g.ln1.dbeta, g.ln1.dbias, rows, E, prec, s,
+                                 g.ln_part, lsc, pl.y16_any));
+  }
+  return PFN_OK;
+}
+// The gradient w.r.t. the layer input, dqkv . Win + dy1 on `rows` rows (token order).  below != nullptr: it leaves as dy2 of the layer below, through that layer's LN2
+// backward in the epilogue.  Else it stays in operand precision between layers (gA_t); out_f32: the embedding's gradient in f32 (gA) instead.
+int layer_backward_dx(const Model& m, const LayerP& t, const char* dqkv_t, const char* dy1_t, int rows, const Plan& pl, const float* lsc, const LayerGrads* below,
+                      float* gA, char* gA_t, bool out_f32, int prof) {
+  const int prec = m.d->precision, E = m.d->emsize;
+  if (below) {
+    ProfScope ps(PFN_PROF_GEMM_DX + prof, m.s);
+    return launch_gemm_lnbwd(lnb_dx(m, pl, lsc, t, dqkv_t, dy1_t, *below, rows), prec, m.s);
+  }
+  GemmNT g = nt(dqkv_t, 3 * E, WT(m, t.w_in), 3 * E, rows, E, 3 * E, EPI_RESID_T | (out_f32 ? EPI_OUT_F32 : EPI_OUT_T));
+  g.aux = dy1_t; g.ld_aux = E; g.out_f32 = gA; g.ld_out_f32 = E; g.out_t = gA_t; g.ld_out_t = E;
+  return launch_gemm_nt(g, prec, m.s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -343,7 +603,6 @@ static bool top_layer_on_test_rows(const pfn_model_desc& d, int S, int sep, floa
 static bool top_layer_on_test_rows_ragged(const pfn_model_desc& d, int S, const Ragged& rg, float pdrop) {
   return !(d.schedule & PFN_SCHED_TOP_LAYER_ALL_ROWS) && d.nlayers > 0 && pdrop == 0.f && d.dropout == 0.f && rg.test_rows > 0 && 4L * rg.sep_min >= S;
 }
-// emsize 1024: the 64-row fused kernels exist and are correct, but lose to GEMM + LayerNorm kernels (PFN_SCHED_FUSE_LN_WIDE)
 int pfn_abi_version(void) { return PFN_ABI_VERSION; }
 int pfn_default_schedule(void) { return g_default_schedule; }
 int pfn_profile_enable(int on) { g_prof_on.store(on < 0 ? 0 : on); return PFN_OK; }
@@ -484,7 +743,7 @@ static int stack_forward_impl(const pfn_model_desc* d, const float* params, cons
   if (!logits && sep < S) return fail(PFN_ERR_ARGUMENT, "null logits");
   hipStream_t s = (hipStream_t)stream;
   const int prec = d->precision, es = esize(prec);
-  const int E = d->emsize, F = d->nhid, H = d->nhead, O = d->n_out;
+  const int E = d->emsize, H = d->nhead, O = d->n_out;
   Layout L = make_layout(*d);
   Ws w = carve(*d, B, S, (char*)workspace);
   if (workspace_bytes < w.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)w.bytes);
@@ -496,7 +755,6 @@ static int stack_forward_impl(const pfn_model_desc* d, const float* params, cons
     return fail(PFN_ERR_ARGUMENT, "bad ragged-batch arguments");
   const int M = B * S, Mt = rg ? (int)rg->test_rows : (S - sep) * B;
   const char* sh = (const char*)shadow;
-  auto W = [&](int64_t off) { return (const void*)(sh + off * es); };
 
   if (src_sbe) {
     PFN_TRY(launch_sbe_to_bse(src_sbe, w.x0, w.x0_t, S, B, E, prec, s));
@@ -516,19 +774,9 @@ static int stack_forward_impl(const pfn_model_desc* d, const float* params, cons
   }
   const float* xin = w.x0;
   const char* xin_t = w.x0_t;
-  // out_proj and linear2 run fused with their residual add and LayerNorm (gemm_nt_ln_kernel) when the shape allows:
-  // the f32 LayerNorm output is then never stored -- the next residual add recomputes it from the pre-LN sum and the
-  // row statistics -- except after the last layer, whose f32 output feeds the decoder gather.
-  // (dropout sits between the bias and the residual add: it takes the unfused GEMM / LayerNorm kernels with an element-wise pass between)
-  const bool ln_ok = ln_gemm_probe(*d, w, params, sh, M);
-  const bool fuse_ln = prec_is16(prec) && ln_ok && F % 32 == 0 && pdrop == 0.f && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE));
-  const bool y16 = residual16(*d) && ln_ok;      // (implies fuse_ln: the descriptor's dropout is 0, so is pdrop)
-  const bool y16u = residual16_separate_ln(*d, ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE)));      // (implies !fuse_ln)
-  struct Resid { const float* plain; const void* y; const float* mean; const float* rstd; const float* gamma; const float* beta; };
-  Resid res = {w.x0, nullptr, nullptr, nullptr, nullptr, nullptr};   // where the layer input lives in f32
-  auto set_resid = [](GemmLN& g, const Resid& r) {
-    g.resid = r.plain; g.ry = r.y; g.rmean = r.mean; g.rrstd = r.rstd; g.rgamma = r.gamma; g.rbeta = r.beta;
-  };
+  const Model m = {d, params, sh, &L, s};
+  const Plan pl = make_plan(*d, w.x0, w.x0_t, params, sh, M, pdrop);
+  Resid res = {w.x0, nullptr, nullptr, nullptr, nullptr, nullptr};
   const bool top_mode = rg ? top_layer_on_test_rows_ragged(*d, S, *rg, pdrop) : top_layer_on_test_rows(*d, S, sep, pdrop);
   // north_star's "QKV projection + attention as one kernel", the half that can exist (PFN_SCHED_FUSE_Q_PROJECTION; measured, not the default: DESIGN.md section 3)
   const bool fuse_q = (d->schedule & PFN_SCHED_FUSE_Q_PROJECTION) && pdrop == 0.f && attn_fwd_can_fuse_q(E, H, prec);
@@ -543,15 +791,15 @@ static int stack_forward_impl(const pfn_model_desc* d, const float* params, cons
     const int Ml = top ? Mt : M;
     {  // packed q/k/v projection
       ProfScope ps(PFN_PROF_GEMM_QKV, s);
-      GemmNT g = nt(xin_t, E, W(p.w_in), E, M, 3 * E, E, EPI_BIAS | EPI_OUT_T);
+      GemmNT g = nt(xin_t, E, W(m, p.w_in), E, M, 3 * E, E, EPI_BIAS | EPI_OUT_T);
       g.bias = params + p.b_in; g.out_t = a.qkv; g.ld_out_t = 3 * E;
       if (fuse_q) {      // PFN_SCHED_FUSE_Q_PROJECTION: only k | v here, q inside the attention kernel (below)
-        g.B = W(p.w_in + (int64_t)E * E); g.N = 2 * E; g.bias = params + p.b_in + E; g.out_t = a.qkv + (int64_t)E * es;
+        g.B = W(m, p.w_in + (int64_t)E * E); g.N = 2 * E; g.bias = params + p.b_in + E; g.out_t = a.qkv + (int64_t)E * es;
       }
       // 16-bit operands: the keys leave centred per dataset, k' = k - W_k xbar (pfn_kernels.h launch_key_shift: the attention output and every gradient are those of
       // the uncentred keys, the operand rounding of K is 9 x smaller on a trained model).  The shift is taken in f32 inside this GEMM's epilogue.
       if (w.kshift && E % 64 == 0) {
-        PFN_TRY(launch_key_shift(xin_t, W(p.w_in + (int64_t)E * E), w.kshift, B, S, E, sep, sep_of, prec, s));
+        PFN_TRY(launch_key_shift(xin_t, W(m, p.w_in + (int64_t)E * E), w.kshift, B, S, E, sep, sep_of, prec, s));
         g.flags |= EPI_ROWSHIFT; g.rowshift = w.kshift; g.rs_ld = E; g.rs_S = S; g.rs_n0 = fuse_q ? 0 : E; g.rs_n1 = g.rs_n0 + E;
       }
       PFN_TRY(launch_gemm_nt(g, prec, s));
@@ -570,77 +818,28 @@ static int stack_forward_impl(const pfn_model_desc* d, const float* params, cons
       at.p_drop = pdrop; at.drop_seed = dseed(l, 0);
       at.q_begin = top ? (rg ? rg->sep_min : sep) : 0;
       at.q_from_sep = (top && rg) ? 1 : 0;
-      if (fuse_q) { at.xq = xin_t; at.wq = W(p.w_in); at.bq = params + p.b_in; at.q_store = 1; }      // (q_store: the backward reads Q from qkv)
+      if (fuse_q) { at.xq = xin_t; at.wq = W(m, p.w_in); at.bq = params + p.b_in; at.q_store = 1; }      // (q_store: the backward reads Q from qkv)
       PFN_TRY(launch_attn_fwd(at, prec, s));
     }
-    const char* ctx_in = a.ctx;
+    LayerBufs u = {xin, xin_t, a.qkv, a.ctx, a.lse, a.y1, a.mean1, a.rstd1, a.x1, a.x1_t, a.h, a.hpre, a.y2, a.mean2, a.rstd2, a.x2, a.x2_t};
     if (top) {      // the test rows of the attention output and of the layer input, gathered
       PFN_TRY(gather_top(a.ctx, w.top_ctx_t, (long)E * es));
-      ctx_in = w.top_ctx_t;
-      if (fuse_ln && !res.plain) {
-        PFN_TRY(gather_top(res.y, w.top_ry, (long)E * (y16 ? es : 4)));
+      u.ctx = w.top_ctx_t;
+      if (pl.fuse_ln && !res.plain) {
+        PFN_TRY(gather_top(res.y, w.top_ry, (long)E * (pl.y16 ? es : 4)));
         PFN_TRY(gather_top(res.mean, w.top_rmean, 4));
         PFN_TRY(gather_top(res.rstd, w.top_rrstd, 4));
         res = Resid{nullptr, w.top_ry, w.top_rmean, w.top_rrstd, res.gamma, res.beta};
       } else {
-        if (y16u) PFN_TRY(gather_top(xin_t, w.top_ry, (long)E * es));      // (the residual of this layer's out_proj is read in operand precision)
-        else PFN_TRY(gather_top(fuse_ln ? res.plain : xin, w.top_ry, (long)E * 4));
+        if (pl.y16u) PFN_TRY(gather_top(xin_t, w.top_ry, (long)E * es));      // (the residual of this layer's out_proj is read in operand precision)
+        else PFN_TRY(gather_top(pl.fuse_ln ? res.plain : xin, w.top_ry, (long)E * 4));
         res = Resid{w.top_ry, nullptr, nullptr, nullptr, nullptr, nullptr};
-        xin = w.top_ry;
+        u.xin = w.top_ry; u.xin_t = (const char*)w.top_ry;
       }
+      u.x2 = O == 0 ? logits : nullptr;     // the stack's f32 output rows: only what the caller reads (the decoder takes x2_t)
     }
-    float* x2_f32 = top ? (O == 0 ? logits : nullptr) : a.x2;     // the stack's f32 output rows: only what the decoder gather (or the caller) reads
-    if (fuse_ln) {  // x1 = LN1(x + out_proj(ctx))
-      ProfScope ps(PFN_PROF_GEMM_OUT_LN + (top ? 1 : 0), s);
-      GemmLN g; memset(&g, 0, sizeof(g));
-      g.A = ctx_in; g.lda = E; g.B = W(p.w_o); g.ldb = E; g.M = Ml; g.N = E; g.K = E; g.bias = params + p.b_o;
-      set_resid(g, res);
-      g.gamma = params + p.g1; g.beta = params + p.be1; g.eps = d->ln_eps;
-      g.y = a.y1; g.mean = a.mean1; g.rstd = a.rstd1; g.x_t = a.x1_t; g.y16 = y16;
-      PFN_TRY(launch_gemm_ln(g, prec, s));
-      res = Resid{nullptr, a.y1, a.mean1, a.rstd1, params + p.g1, params + p.be1};
-    } else {
-      {  // out_proj + residual  (dropout1: the product leaves alone and the element-wise pass adds the residual)
-        GemmNT g = nt(ctx_in, E, W(p.w_o), E, Ml, E, E, EPI_BIAS | (pdrop > 0.f ? 0 : EPI_RESID) | EPI_OUT_F32);
-        g.bias = params + p.b_o; g.resid = xin; g.ld_resid = E; g.out_f32 = a.y1; g.ld_out_f32 = E;
-        if (y16u) {      // residual from the operand-precision layer input (the gathered test rows in top mode), sum out in operand precision
-          g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = top ? (const void*)w.top_ry : (const void*)xin_t; g.ld_aux = E; g.out_t = a.y1; g.ld_out_t = E;
-        }
-        PFN_TRY(launch_gemm_nt(g, prec, s));
-        if (pdrop > 0.f) PFN_TRY(launch_dropout_add(a.y1, xin, M, E, dseed(l, 1), pdrop, s));
-      }
-      PFN_TRY(launch_layernorm_fwd(a.y1, params + p.g1, params + p.be1, y16u ? nullptr : a.x1, a.x1_t, a.mean1, a.rstd1, Ml, E, d->ln_eps, prec, s, y16u));
-    }
-    {  // linear1 + GELU (pre-activation kept for the backward)
-      ProfScope ps(PFN_PROF_GEMM_LIN1 + (top ? 1 : 0), s);
-      GemmNT g = nt(a.x1_t, E, W(p.w1), E, Ml, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
-      g.bias = params + p.b1; g.out_t = a.h; g.ld_out_t = F; g.out2_t = a.hpre; g.ld_out2 = F;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-      // FFN dropout: h and the stored GELU derivative take the same mask, so linear2, its weight gradient and d(hpre) need nothing more
-      if (pdrop > 0.f) PFN_TRY(launch_dropout_scale(a.h, a.h, a.hpre, a.hpre, M, F, dseed(l, 2), pdrop, prec, s));
-    }
-    if (fuse_ln) {  // x2 = LN2(x1 + linear2(h))
-      ProfScope ps(PFN_PROF_GEMM_LIN2_LN + (top ? 1 : 0), s);
-      GemmLN g; memset(&g, 0, sizeof(g));
-      g.A = a.h; g.lda = F; g.B = W(p.w2); g.ldb = F; g.M = Ml; g.N = E; g.K = F; g.bias = params + p.b2;
-      set_resid(g, res);
-      g.gamma = params + p.g2; g.beta = params + p.be2; g.eps = d->ln_eps;
-      g.y = a.y2; g.mean = a.mean2; g.rstd = a.rstd2; g.x_t = a.x2_t; g.y16 = y16;
-      g.x_f32 = (l == d->nlayers - 1) ? x2_f32 : nullptr;
-      PFN_TRY(launch_gemm_ln(g, prec, s));
-      res = Resid{nullptr, a.y2, a.mean2, a.rstd2, params + p.g2, params + p.be2};
-    } else {
-      {  // linear2 + residual  (dropout2 as above)
-        GemmNT g = nt(a.h, F, W(p.w2), F, Ml, E, F, EPI_BIAS | (pdrop > 0.f ? 0 : EPI_RESID) | EPI_OUT_F32);
-        g.bias = params + p.b2; g.resid = a.x1; g.ld_resid = E; g.out_f32 = a.y2; g.ld_out_f32 = E;
-        if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = a.x1_t; g.ld_aux = E; g.out_t = a.y2; g.ld_out_t = E; }
-        PFN_TRY(launch_gemm_nt(g, prec, s));
-        if (pdrop > 0.f) PFN_TRY(launch_dropout_add(a.y2, a.x1, M, E, dseed(l, 3), pdrop, s));
-      }
-      // (fp16 sums: only the last layer's f32 output has a reader -- the decoder gather, or the caller when there is no decoder)
-      float* x2_out = top ? x2_f32 : ((y16u && l < d->nlayers - 1) ? nullptr : a.x2);
-      PFN_TRY(launch_layernorm_fwd(a.y2, params + p.g2, params + p.be2, x2_out, a.x2_t, a.mean2, a.rstd2, Ml, E, d->ln_eps, prec, s, y16u));
-    }
+    const unsigned seeds[4] = {dseed(l, 0), dseed(l, 1), dseed(l, 2), dseed(l, 3)};
+    PFN_TRY(layer_tail_forward(m, p, u, res, Ml, pl, pdrop, seeds, l == d->nlayers - 1, top ? 1 : 0));
     xin = a.x2; xin_t = a.x2_t;
   }
   // decoder on the test rows only (the reference decodes all rows, then slices: transformer.py:85,91)
@@ -655,17 +854,7 @@ static int stack_forward_impl(const pfn_model_desc* d, const float* params, cons
     if (top_mode) {}
     else if (rg) PFN_TRY(launch_gather_test_rows_ragged(xin, w.xt_t, S, B, E, rg->sep_of, (const long*)rg->row_off, prec, s));
     else PFN_TRY(launch_gather_test_rows(xin, w.xt_t, S, B, E, sep, prec, s));
-    const char* xt_t = top_mode ? w.layer[d->nlayers - 1].x2_t : w.xt_t;
-    {
-      GemmNT g = nt(xt_t, E, W(L.dec0_w), E, Mt, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
-      g.bias = params + L.dec0_b; g.out_t = w.dt; g.ld_out_t = F; g.out2_t = w.dpre; g.ld_out2 = F;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
-    {
-      GemmNT g = nt(w.dt, F, W(L.dec2_w), F, Mt, O, F, EPI_BIAS | EPI_OUT_F32);
-      g.bias = params + L.dec2_b; g.out_f32 = logits; g.ld_out_f32 = O;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
+    PFN_TRY(decoder_forward(m, top_mode ? w.layer[d->nlayers - 1].x2_t : w.xt_t, w.dt, w.dpre, logits, Mt));
   }
   return PFN_OK;
 }
@@ -715,9 +904,9 @@ int pfn_stack_condition(const pfn_model_desc* d, const float* params, const void
                         int B, int sep, void* workspace, int64_t workspace_bytes, void* context, int64_t context_bytes, void* stream) {
   PFN_TRY(check_desc(d));
   if (B < 1 || sep < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d sep=%d", B, sep);
-  const KvSink sink = {(char*)context, context_layout(*d, B, sep)};
   if (sep > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context");
-  if (context_bytes < sink.c.bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)sink.c.bytes);
+  KvSink sink = {(char*)context, {}};
+  PFN_TRY(check_context(*d, B, sep, context, context_bytes, &sink.c));
   if (sep == 0 || d->nlayers == 0) return PFN_OK;
   if (!x || !y) return fail(PFN_ERR_ARGUMENT, "need x and y");
   return stack_forward_impl(d, params, shadow, x, x_st, x_sb, y, y_st, y_sb, nullptr, B, sep, sep, workspace, workspace_bytes, nullptr, stream, false, 0, nullptr, &sink);
@@ -733,9 +922,9 @@ int pfn_stack_condition_ragged(const pfn_model_desc* d, const float* params, con
   PFN_TRY(check_desc(d));
   if (B < 1 || sep_max < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d sep_max=%d", B, sep_max);
   if (!sep_of) return fail(PFN_ERR_ARGUMENT, "null sep_of");
-  const KvSink sink = {(char*)context, context_layout(*d, B, sep_max)};
   if (sep_max > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context");
-  if (context_bytes < sink.c.bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)sink.c.bytes);
+  KvSink sink = {(char*)context, {}};
+  PFN_TRY(check_context(*d, B, sep_max, context, context_bytes, &sink.c));
   if (sep_max == 0 || d->nlayers == 0) return PFN_OK;
   if (!x || !y || !params || !shadow || !workspace) return fail(PFN_ERR_ARGUMENT, "null pointer");
   const Ws w = carve(*d, B, sep_max, (char*)workspace);
@@ -761,9 +950,8 @@ static int stack_predict_impl(const pfn_model_desc* d, const float* params, cons
   PFN_TRY(check_desc(d));
   if (ragged && !sep_of) return fail(PFN_ERR_ARGUMENT, "null sep_of");
   if (B < 1 || n < 0 || sep < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d n=%d sep=%d", B, n, sep);
-  const Context c = context_layout(*d, B, sep);
-  if (sep > 0 && d->nlayers > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context with sep=%d", sep);
-  if (context_bytes < c.bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)c.bytes);
+  Context c;
+  PFN_TRY(check_context(*d, B, sep, context, context_bytes, &c));
   if (!params || !shadow || !workspace || (n > 0 && (!x || !logits))) return fail(PFN_ERR_ARGUMENT, "null pointer");
   PredictWs w;
   PredictGradWs sv;
@@ -776,13 +964,11 @@ static int stack_predict_impl(const pfn_model_desc* d, const float* params, cons
   }
   if (n == 0) return PFN_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int prec = d->precision, es = esize(prec);
-  const int E = d->emsize, F = d->nhid, H = d->nhead, O = d->n_out, M = B * n;
+  const int prec = d->precision;
+  const int E = d->emsize, H = d->nhead, O = d->n_out, M = B * n;
   Layout L = make_layout(*d);
-  const char* sh = (const char*)shadow;
-  auto W = [&](int64_t off) { return (const void*)(sh + off * es); };
+  const Model m = {d, params, (const char*)shadow, &L, s};
   // the buffers of layer l: the layer input (set 2 / the previous layer's output), q|k|v, ctx, set 1, h, hpre and the output (set 2 again / kept)
-  struct LayerBufs { float *xin; char* xin_t; char *qkv, *ctx; float* lse; float *y1, *mean1, *rstd1, *x1; char *x1_t, *h, *hpre; float *y2, *mean2, *rstd2, *x2; char* x2_t; };
   auto bufs = [&](int l) {
     LayerBufs u;
     if (!saved) {
@@ -803,23 +989,15 @@ static int stack_predict_impl(const pfn_model_desc* d, const float* params, cons
     e.out_f32 = x0; e.out_t = x0_t; e.S = n; e.B = B; e.nf = d->num_features; e.E = E; e.sep = 0;
     PFN_TRY(launch_embed_fwd(e, prec, s));
   }
-  // the forward's fusion rules (stack_forward_impl) for the same descriptor and these rows
-  Ws probe_ws; probe_ws.x0 = x0; probe_ws.x0_t = x0_t;
-  const bool ln_ok = ln_gemm_probe(*d, probe_ws, params, sh, M);
-  const bool fuse_ln = prec_is16(prec) && ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE));
-  const bool y16 = residual16(*d) && ln_ok;
-  const bool y16u = residual16_separate_ln(*d, ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE)));
-  struct Resid { const float* plain; const void* y; const float* mean; const float* rstd; const float* gamma; const float* beta; };
+  const Plan pl = make_plan(*d, x0, x0_t, params, shadow, M, 0.f);
   Resid res = {x0, nullptr, nullptr, nullptr, nullptr, nullptr};
-  auto set_resid = [](GemmLN& g, const Resid& r) { g.resid = r.plain; g.ry = r.y; g.rmean = r.mean; g.rrstd = r.rstd; g.rgamma = r.gamma; g.rbeta = r.beta; };
-  float* xout = x0;      // the last layer's f32 output
+  const float* xout = x0;      // the last layer's f32 output
   for (int l = 0; l < d->nlayers; ++l) {
     const LayerP& p = L.layer[l];
     const LayerBufs u = bufs(l);
-    const bool last = l == d->nlayers - 1;
     const char* kv = (const char*)context + l * c.layer_bytes;
     {  // packed q/k/v projection; the self keys shifted by the vector that centred the cached ones
-      GemmNT g = nt(u.xin_t, E, W(p.w_in), E, M, 3 * E, E, EPI_BIAS | EPI_OUT_T);
+      GemmNT g = nt(u.xin_t, E, W(m, p.w_in), E, M, 3 * E, E, EPI_BIAS | EPI_OUT_T);
       g.bias = params + p.b_in; g.out_t = u.qkv; g.ld_out_t = 3 * E;
       if (c.shift_bytes && sep > 0) {
         g.flags |= EPI_ROWSHIFT; g.rowshift = (const float*)(kv + c.kv_bytes); g.rs_ld = E; g.rs_S = n; g.rs_n0 = E; g.rs_n1 = 2 * E;
@@ -832,61 +1010,15 @@ static int stack_predict_impl(const pfn_model_desc* d, const float* params, cons
       at.kv = kv; at.kv_ld = 2L * E; at.kv_sb = (long)sep * 2 * E; at.part_o = saved ? sv.part_o : w.part_o; at.part_ml = saved ? sv.part_ml : w.part_ml;
       PFN_TRY(launch_attn_fwd_cache(at, prec, s));
     }
-    if (fuse_ln) {  // x1 = LN1(x + out_proj(ctx))
-      GemmLN g; memset(&g, 0, sizeof(g));
-      g.A = u.ctx; g.lda = E; g.B = W(p.w_o); g.ldb = E; g.M = M; g.N = E; g.K = E; g.bias = params + p.b_o;
-      set_resid(g, res);
-      g.gamma = params + p.g1; g.beta = params + p.be1; g.eps = d->ln_eps;
-      g.y = u.y1; g.mean = u.mean1; g.rstd = u.rstd1; g.x_t = u.x1_t; g.y16 = y16;
-      PFN_TRY(launch_gemm_ln(g, prec, s));
-      res = Resid{nullptr, u.y1, u.mean1, u.rstd1, params + p.g1, params + p.be1};
-    } else {
-      GemmNT g = nt(u.ctx, E, W(p.w_o), E, M, E, E, EPI_BIAS | EPI_RESID | EPI_OUT_F32);
-      g.bias = params + p.b_o; g.resid = u.xin; g.ld_resid = E; g.out_f32 = u.y1; g.ld_out_f32 = E;
-      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = u.xin_t; g.ld_aux = E; g.out_t = u.y1; g.ld_out_t = E; }
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-      PFN_TRY(launch_layernorm_fwd(u.y1, params + p.g1, params + p.be1, y16u ? nullptr : u.x1, u.x1_t, u.mean1, u.rstd1, M, E, d->ln_eps, prec, s, y16u));
-    }
-    {  // linear1 + GELU
-      GemmNT g = nt(u.x1_t, E, W(p.w1), E, M, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
-      g.bias = params + p.b1; g.out_t = u.h; g.ld_out_t = F; g.out2_t = u.hpre; g.ld_out2 = F;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
-    if (fuse_ln) {  // x2 = LN2(x1 + linear2(h)), over the layer input (read by out_proj only)
-      GemmLN g; memset(&g, 0, sizeof(g));
-      g.A = u.h; g.lda = F; g.B = W(p.w2); g.ldb = F; g.M = M; g.N = E; g.K = F; g.bias = params + p.b2;
-      set_resid(g, res);
-      g.gamma = params + p.g2; g.beta = params + p.be2; g.eps = d->ln_eps;
-      g.y = u.y2; g.mean = u.mean2; g.rstd = u.rstd2; g.x_t = u.x2_t; g.y16 = y16;
-      g.x_f32 = last ? u.x2 : nullptr;
-      PFN_TRY(launch_gemm_ln(g, prec, s));
-      res = Resid{nullptr, u.y2, u.mean2, u.rstd2, params + p.g2, params + p.be2};
-    } else {
-      GemmNT g = nt(u.h, F, W(p.w2), F, M, E, F, EPI_BIAS | EPI_RESID | EPI_OUT_F32);
-      g.bias = params + p.b2; g.resid = u.x1; g.ld_resid = E; g.out_f32 = u.y2; g.ld_out_f32 = E;
-      if (y16u) { g.flags = EPI_BIAS | EPI_RESID_T | EPI_OUT_T; g.aux = u.x1_t; g.ld_aux = E; g.out_t = u.y2; g.ld_out_t = E; }
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-      PFN_TRY(launch_layernorm_fwd(u.y2, params + p.g2, params + p.be2, (y16u && !last) ? nullptr : u.x2, u.x2_t, u.mean2, u.rstd2, M, E, d->ln_eps, prec, s, y16u));
-    }
+    // (x2 = LN2(...) lands over the layer input, which out_proj alone reads)
+    PFN_TRY(layer_tail_forward(m, p, u, res, M, pl, 0.f, nullptr, l == d->nlayers - 1, NO_PROF));
     xout = u.x2;
   }
   // [B, n] token order -> the caller's rows t B + b; then the decoder on them (set 1 and the q|k|v buffer are free now)
   if (O == 0) return launch_gather_test_rows(xout, logits, n, B, E, 0, PFN_PREC_F32, s);
   char* xt_t = saved ? sv.xt_t : w.x1_t;
-  char* dt = saved ? sv.dt : w.h;
-  char* dpre = saved ? sv.dpre : w.hpre;
   PFN_TRY(launch_gather_test_rows(xout, xt_t, n, B, E, 0, prec, s));
-  {
-    GemmNT g = nt(xt_t, E, W(L.dec0_w), E, M, F, E, EPI_BIAS | EPI_GELU | EPI_OUT_T | EPI_OUT2_T);
-    g.bias = params + L.dec0_b; g.out_t = dt; g.ld_out_t = F; g.out2_t = dpre; g.ld_out2 = F;
-    PFN_TRY(launch_gemm_nt(g, prec, s));
-  }
-  {
-    GemmNT g = nt(dt, F, W(L.dec2_w), F, M, O, F, EPI_BIAS | EPI_OUT_F32);
-    g.bias = params + L.dec2_b; g.out_f32 = logits; g.ld_out_f32 = O;
-    PFN_TRY(launch_gemm_nt(g, prec, s));
-  }
-  return PFN_OK;
+  return decoder_forward(m, xt_t, saved ? sv.dt : w.h, saved ? sv.dpre : w.hpre, logits, M);
 }
 int pfn_stack_predict(const pfn_model_desc* d, const float* params, const void* shadow, const void* context, int64_t context_bytes, int sep,
                       const float* x, int64_t x_st, int64_t x_sb, int B, int n, void* workspace, int64_t workspace_bytes, float* logits, void* stream) {
@@ -930,26 +1062,19 @@ static int stack_predict_backward_impl(const pfn_model_desc* d, const float* par
                                        int64_t dx_sb, void* stream) {
   PFN_TRY(check_desc(d));
   if (B < 1 || n < 0 || sep < 0) return fail(PFN_ERR_ARGUMENT, "bad B=%d n=%d sep=%d", B, n, sep);
-  const Context c = context_layout(*d, B, sep);
-  if (sep > 0 && d->nlayers > 0 && !context) return fail(PFN_ERR_ARGUMENT, "null context with sep=%d", sep);
-  if (context_bytes < c.bytes) return fail(PFN_ERR_ARGUMENT, "context too small: %lld < %lld", (long long)context_bytes, (long long)c.bytes);
+  Context c;
+  PFN_TRY(check_context(*d, B, sep, context, context_bytes, &c));
   if (!params || !shadow || !workspace || (n > 0 && (!dlogits || !dx))) return fail(PFN_ERR_ARGUMENT, "null pointer");
   PredictGradWs w = carve_predict_grad(*d, B, n, (char*)workspace);
   if (workspace_bytes < w.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)w.bytes);
   if (n == 0) return PFN_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int prec = d->precision, es = esize(prec);
-  const int E = d->emsize, F = d->nhid, H = d->nhead, O = d->n_out, M = B * n;
+  const int prec = d->precision;
+  const int E = d->emsize, H = d->nhead, O = d->n_out, M = B * n;
   Layout L = make_layout(*d);
-  const int npad = L.n_out_pad;
-  const char* sh = (const char*)shadow;
-  auto WT = [&](int64_t off) { return (const void*)(sh + (L.total + off) * es); };
-  // the forward's layout decisions (stack_predict_impl), and the training backward's for the LayerNorm backward
-  Ws probe_ws; probe_ws.x0 = w.x0; probe_ws.x0_t = w.x0_t;
-  const bool ln_ok = ln_gemm_probe(*d, probe_ws, params, sh, M);
-  const bool y16 = (residual16(*d) && ln_ok) || residual16_separate_ln(*d, ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE)));
-  float* sg = w.sink;                      // dgamma | dbeta | dbias sums nobody reads
-  float *sb = w.sink + E, *sx = w.sink + 2 * E;
+  const Model m = {d, params, (const char*)shadow, &L, s};
+  const Plan pl = make_plan(*d, w.x0, w.x0_t, params, shadow, M, 0.f);
+  const LnSinks sink = {w.sink, w.sink + E, w.sink + 2 * E};      // dgamma | dbeta | dbias sums nobody reads
   const float* lsc = nullptr;
   if (prec == PFN_PREC_FP16) {      // the training backward's loss scale: the chain runs on dlogits * 2^k, dx leaves without it
     PFN_TRY(launch_absmax(dlogits, (long)M * (O > 0 ? O : E), w.lscale, s));
@@ -960,60 +1085,29 @@ static int stack_predict_backward_impl(const pfn_model_desc* d, const float* par
   if (O == 0) {
     if (lsc) { PFN_TRY(launch_scale_copy(dlogits, w.dxt, (long)M * E, lsc, s)); dxt = w.dxt; }
   } else {
-    PFN_TRY(launch_cast_rows(dlogits, O, w.dlog_t, npad, M, O, prec, s, lsc));
-    {
-      GemmNT g = nt(w.dlog_t, npad, WT(L.dec2_wt), npad, M, F, npad % 64 == 0 ? npad : O, EPI_GELU_BWD | EPI_OUT_T);
-      g.aux = w.dpre; g.ld_aux = F; g.out_t = w.dd_t; g.ld_out_t = F;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
-    {
-      GemmNT g = nt(w.dd_t, F, WT(L.dec0_wt), F, M, E, F, EPI_OUT_F32);
-      g.out_f32 = w.dxt; g.ld_out_f32 = E;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
+    PFN_TRY(launch_cast_rows(dlogits, O, w.dlog_t, L.n_out_pad, M, O, prec, s, lsc));
+    PFN_TRY(decoder_backward_data(m, w.dlog_t, w.dpre, w.dd_t, w.dxt, M));
     dxt = w.dxt;
   }
   // -> [B, n] token order, f32 (the top layer's LN2 backward reads it as it is)
   PFN_TRY(launch_scatter_test_rows(dxt, w.gA, n, B, E, 0, PFN_PREC_F32, s));
-  auto lnb = [&](const void* A, long lda, const void* Bw, long ldb, int K, const void* aux, const void* y, const float* mean, const float* rstd,
-                 const float* gamma, void* dx_t) {
-    GemmLNB g; memset(&g, 0, sizeof(g));
-    g.A = A; g.lda = lda; g.B = Bw; g.ldb = ldb; g.M = M; g.N = E; g.K = K; g.aux = aux;
-    g.y = y; g.mean = mean; g.rstd = rstd; g.gamma = gamma; g.dx_t = dx_t; g.dgamma = sg; g.dbeta = sb; g.scale_amax = lsc; g.y16 = y16;
-    return g;
+  // layer l's view: one set of gradient rows for every layer; LN2 reads gA (f32, the top layer) or gA_t (operand precision, the layer above's dx)
+  auto view = [&](int l) {
+    const LayerP& p = L.layer[l];
+    const PredictLayerWs& a = w.layer[l];
+    const bool top = l == d->nlayers - 1;
+    return LayerGrads{top ? (const void*)w.gA : (const void*)w.gA_t, top ? 0 : 1, a.y2, a.mean2, a.rstd2, params + p.g2, a.y1, a.mean1, a.rstd1, params + p.g1, a.hpre,
+                      w.dy2_t, nullptr, w.dh_t, w.dy1_t, w.dqkv_t, w.gA_t, sink, sink, nullptr};
   };
-  bool fuse_lnb = !(d->schedule & PFN_SCHED_DETERMINISTIC) && !(d->schedule & PFN_SCHED_SEPARATE_LNBWD) && prec_is16(prec) && d->nlayers > 0 &&
-                  (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE));
-  if (fuse_lnb) {
-    const LayerP& p = L.layer[0]; const LayerP& t = L.layer_t[0]; const PredictLayerWs& a = w.layer[0];
-    fuse_lnb = gemm_lnbwd_supported(lnb(w.dh_t, F, WT(t.w1), F, F, w.dy2_t, a.y1, a.mean1, a.rstd1, params + p.g1, w.dy1_t)) &&
-               gemm_lnbwd_supported(lnb(w.dqkv_t, 3 * E, WT(t.w_in), 3 * E, 3 * E, w.dy1_t, a.y2, a.mean2, a.rstd2, params + p.g2, w.dy2_t));
-  }
-  const bool last_t = d->nlayers == 0 || prec_is16(prec);      // the embedding's gradient: operand precision from a 16-bit chain (gA_t), else f32 (gA)
+  const bool fuse_lnb = d->nlayers > 0 && lnbwd_fusable(m, pl, lsc, view(0), M);
+  const bool from_t = predict_dsrc_is_t(*d);
   for (int l = d->nlayers - 1; l >= 0; --l) {
-    const LayerP &p = L.layer[l], &t = L.layer_t[l];
+    const LayerP& t = L.layer_t[l];
     const PredictLayerWs& a = w.layer[l];
     const char* kv = (const char*)context + l * c.layer_bytes;
-    if (!fuse_lnb || l == d->nlayers - 1)      // LN2: from gA (f32, the top layer) or gA_t (operand precision, the layer above's dx)
-      PFN_TRY(launch_layernorm_bwd(l == d->nlayers - 1 ? (const void*)w.gA : (const void*)w.gA_t, l == d->nlayers - 1 ? 0 : 1, a.y2, params + p.g2, a.mean2, a.rstd2,
-                                   nullptr, w.dy2_t, sg, sb, sx, M, E, prec, s, nullptr, lsc, y16));
-    {  // d(hpre) = (dy2 . W2) * gelu'(hpre)
-      GemmNT g = nt(w.dy2_t, E, WT(t.w2), E, M, F, E, EPI_GELU_BWD | EPI_OUT_T);
-      g.aux = a.hpre; g.ld_aux = F; g.out_t = w.dh_t; g.ld_out_t = F;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
-    if (fuse_lnb) {  // dy1 = LN1 backward of (dh . W1 + dy2)
-      PFN_TRY(launch_gemm_lnbwd(lnb(w.dh_t, F, WT(t.w1), F, F, w.dy2_t, a.y1, a.mean1, a.rstd1, params + p.g1, w.dy1_t), prec, s));
-    } else {
-      {  // dx1 = dh . W1 + dy2
-        GemmNT g = nt(w.dh_t, F, WT(t.w1), F, M, E, F, EPI_RESID_T | EPI_OUT_T);
-        g.aux = w.dy2_t; g.ld_aux = E; g.out_t = w.gA_t; g.ld_out_t = E;
-        PFN_TRY(launch_gemm_nt(g, prec, s));
-      }
-      PFN_TRY(launch_layernorm_bwd(w.gA_t, 1, a.y1, params + p.g1, a.mean1, a.rstd1, nullptr, w.dy1_t, sg, sb, sx, M, E, prec, s, nullptr, lsc, y16));
-    }
+    PFN_TRY(layer_backward_to_dy1(m, t, view(l), M, pl, fuse_lnb, fuse_lnb && l < d->nlayers - 1, lsc, 0.f, 0, NO_PROF));
     {  // d(ctx) = dy1 . Wo
-      GemmNT g = nt(w.dy1_t, E, WT(t.w_o), E, M, E, E, EPI_OUT_T);
+      GemmNT g = nt(w.dy1_t, E, WT(m, t.w_o), E, M, E, E, EPI_OUT_T);
       g.out_t = w.dctx_t; g.ld_out_t = E;
       PFN_TRY(launch_gemm_nt(g, prec, s));
     }
@@ -1024,19 +1118,11 @@ static int stack_predict_backward_impl(const pfn_model_desc* d, const float* par
       at.B = B; at.S = n; at.E = E; at.H = H; at.sep = sep; at.sep_of = sep_of;
       PFN_TRY(launch_attn_bwd_cache(at, prec, s));
     }
-    if (fuse_lnb && l > 0) {  // dy2 of the layer below = its LN2 backward of (dqkv . Win + dy1)
-      const LayerP& pb = L.layer[l - 1];
-      const PredictLayerWs& ab = w.layer[l - 1];
-      PFN_TRY(launch_gemm_lnbwd(lnb(w.dqkv_t, 3 * E, WT(t.w_in), 3 * E, 3 * E, w.dy1_t, ab.y2, ab.mean2, ab.rstd2, params + pb.g2, w.dy2_t), prec, s));
-    } else {  // dx = dqkv . Win + dy1
-      GemmNT g = nt(w.dqkv_t, 3 * E, WT(t.w_in), 3 * E, M, E, 3 * E, EPI_RESID_T | (l == 0 && !last_t ? EPI_OUT_F32 : EPI_OUT_T));
-      g.aux = w.dy1_t; g.ld_aux = E; g.out_f32 = w.gA; g.ld_out_f32 = E; g.out_t = w.gA_t; g.ld_out_t = E;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
+    const LayerGrads below = l > 0 ? view(l - 1) : LayerGrads{};
+    PFN_TRY(layer_backward_dx(m, t, w.dqkv_t, w.dy1_t, M, pl, lsc, fuse_lnb && l > 0 ? &below : nullptr, w.gA, w.gA_t, l == 0 && !from_t, NO_PROF));
   }
   // ---- embedding: dx = d(src) . W_enc ----
   EmbedInGradArgs e; memset(&e, 0, sizeof(e));
-  const bool from_t = d->nlayers > 0 && last_t;
   e.dsrc = from_t ? (const void*)w.gA_t : (const void*)w.gA; e.dsrc_prec = from_t ? prec : PFN_PREC_F32;
   e.wx = params + L.enc_w; e.wy = params + L.yenc_w; e.dx = dx; e.dx_st = dx_st; e.dx_sb = dx_sb; e.dy = nullptr;
   e.S = n; e.B = B; e.nf = d->num_features; e.E = E; e.sep = 0; e.scale_amax = lsc;
@@ -1060,14 +1146,13 @@ static int stack_backward_impl(const pfn_model_desc* d, const float* params, con
                                int first_group_layers, pfn_host_callback on_first_group, void* user, int use_dropout, uint64_t dropout_seed, const Ragged* rg) {
   PFN_TRY(check_desc(d));
   const float pdrop = use_dropout ? d->dropout : 0.f;
-  const bool top_mode = rg ? top_layer_on_test_rows_ragged(*d, S, *rg, pdrop) : top_layer_on_test_rows(*d, S, sep, pdrop);       // (the forward took the same decision: same descriptor, shape, dropout)
+  const bool top_mode = rg ? top_layer_on_test_rows_ragged(*d, S, *rg, pdrop) : top_layer_on_test_rows(*d, S, sep, pdrop);
   const int* sep_of = rg ? rg->sep_of : nullptr;
   if (rg && (dsrc_sbe || rg->test_rows < 0 || rg->test_rows > (int64_t)B * S || !rg->sep_of || !rg->row_off)) return fail(PFN_ERR_ARGUMENT, "bad ragged-batch arguments");
   // PFN_SCHED_DETERMINISTIC: one writer per gradient element and launch -- no token splits in the weight-gradient GEMMs, the LayerNorm backward as its own
   // kernel with ordered partial sums, the embedding gradient from one workgroup per column block
   const bool det = (d->schedule & PFN_SCHED_DETERMINISTIC) != 0;
   const float* lsc = nullptr;      // fp16 operands: the device float the loss scale is derived from (set below, once the workspace is carved); else no scaling
-  auto tn_det = [&](GemmTN g) { if (det) g.max_splits = 1; g.scale_amax = lsc; return g; };
   auto dseed = [&](int layer, int site) { return dropout_site_seed(dropout_seed, layer, site); };
   if (!params || !shadow || !workspace || !grads) return fail(PFN_ERR_ARGUMENT, "null pointer");
   if (!dsrc_sbe && (!x || !y)) return fail(PFN_ERR_ARGUMENT, "need x and y (or dsrc_sbe)");
@@ -1080,11 +1165,8 @@ static int stack_backward_impl(const pfn_model_desc* d, const float* params, con
   if (workspace_bytes < w.bytes) return fail(PFN_ERR_ARGUMENT, "workspace too small");
   const int M = B * S, Mt = rg ? (int)rg->test_rows : (S - sep) * B, npad = L.n_out_pad;
   const char* sh = (const char*)shadow;
-  auto W = [&](int64_t off) { return (const void*)(sh + off * es); };
-  auto WT = [&](int64_t off) { return (const void*)(sh + (L.total + off) * es); };
-  const bool ln_ok = ln_gemm_probe(*d, w, params, sh, M);
-  // the forward stored the pre-LayerNorm sums in operand precision (same rules, same pointers): inside the LayerNorm-fused GEMMs, or from a GEMM ahead of layernorm_fwd
-  const bool y16 = (residual16(*d) && ln_ok) || residual16_separate_ln(*d, ln_ok && F % 32 == 0 && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE)));
+  const Model m = {d, params, sh, &L, s};
+  const Plan pl = make_plan(*d, w.x0, w.x0_t, params, sh, M, pdrop);
 
   // fp16 operands: the backward chain runs on dlogits * 2^k, k from max|dlogits| on the device; every kernel that writes a parameter gradient takes 2^k out again
   if (prec == PFN_PREC_FP16 && Mt > 0) {
@@ -1109,26 +1191,13 @@ static int stack_backward_impl(const pfn_model_desc* d, const float* params, con
     dp2.colsum = grads + L.dec2_b;
     TnProblem dp0; memset(&dp0, 0, sizeof(dp0));
     dp0.A = w.dd_t; dp0.lda = F; dp0.B = xt_t; dp0.ldb = E; dp0.C = grads + L.dec0_w; dp0.ldc = E; dp0.P = F; dp0.Q = E; dp0.colsum = grads + L.dec0_b;
-    const bool dec_grouped = prec_is16(prec) && gemm_tn_group_supported(dp2) && gemm_tn_group_supported(dp0);
-    if (!dec_grouped) PFN_TRY(launch_gemm_tn(tn_det(tn(w.dlog_t, npad, w.dt, F, grads + L.dec2_w, F, Mt, O, F, grads + L.dec2_b)), prec, s));
-    {
-      // (contraction over the zero-padded width when that is whole 64-deep stages: the LDS-DMA kernel then takes it)
-      GemmNT g = nt(w.dlog_t, npad, WT(L.dec2_wt), npad, Mt, F, npad % 64 == 0 ? npad : O, EPI_GELU_BWD | EPI_OUT_T);
-      g.aux = w.dpre; g.ld_aux = F; g.out_t = w.dd_t; g.ld_out_t = F;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
-    if (dec_grouped) {
-      GemmTNGroup g; memset(&g, 0, sizeof(g));
-      g.n = 2; g.M = Mt; g.p[0] = dp2; g.p[1] = dp0; g.splits = det ? 1 : 0; g.scale_amax = lsc;
-      PFN_TRY(launch_gemm_tn_group(g, prec, s));
-    } else {
-      PFN_TRY(launch_gemm_tn(tn_det(tn(w.dd_t, F, xt_t, E, grads + L.dec0_w, E, Mt, F, E, grads + L.dec0_b)), prec, s));
-    }
-    {
-      GemmNT g = nt(w.dd_t, F, WT(L.dec0_wt), F, Mt, E, F, EPI_OUT_F32);
-      g.out_f32 = w.dxt; g.ld_out_f32 = E;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
+    // (one launch each: dec2's goes first, as it always did -- it is the reader of dlog_t that must not wait for the data chain: carve() gives dlog_t
+    // align_up(n_out, 8) columns, so with n_out >= 64 and not a multiple of 64 its last rows can reach into dd_t, which the chain writes)
+    const std::vector<TnProblem> dec = {dp2, dp0};
+    const bool dec_grouped = tn_set_groupable(dec, prec);
+    if (!dec_grouped) PFN_TRY(launch_tn_set({dp2}, Mt, prec, det, lsc, NO_PROF, s, false));
+    PFN_TRY(decoder_backward_data(m, w.dlog_t, w.dpre, w.dd_t, w.dxt, Mt));
+    PFN_TRY(launch_tn_set(dec_grouped ? dec : std::vector<TnProblem>{dp0}, Mt, prec, det, lsc, NO_PROF, s, dec_grouped));
   }
   // (top_mode: the top layer's backward runs on the compact test rows and takes dxt as it is)
   if (top_mode) {}
@@ -1143,25 +1212,18 @@ static int stack_backward_impl(const pfn_model_desc* d, const float* params, con
   // The two GEMMs whose output is the gradient w.r.t. a LayerNorm output (dx1 -> LN1, dx -> the previous layer's LN2) run that
   // LayerNorm's backward in their epilogue (gemm_nt_lnbwd_kernel) when the shape allows: the sum never reaches HBM, and the
   // bias gradient of the Linear in front of the LayerNorm moves to the weight-gradient GEMM that reads the same operand.
-  auto lnb = [&](const void* A, long lda, const void* Bw, long ldb, int K, const void* aux, const void* y, const float* mean, const float* rstd,
-                 const float* gamma, void* dx_t, float* dgamma, float* dbeta, int rows) {
-    GemmLNB g; memset(&g, 0, sizeof(g));
-    g.A = A; g.lda = lda; g.B = Bw; g.ldb = ldb; g.M = rows; g.N = E; g.K = K; g.aux = aux;
-    g.y = y; g.mean = mean; g.rstd = rstd; g.gamma = gamma; g.dx_t = dx_t; g.dgamma = dgamma; g.dbeta = dbeta; g.scale_amax = lsc; g.y16 = y16;
-    return g;
+  // layer l's view for the chain; compact: the top layer on the test rows (its gradient arrives as dxt, f32, and dy1 leaves in compact order)
+  auto view = [&](int l, bool compact) {
+    const LayerP& p = L.layer[l];
+    LayerWs& a = w.layer[l];
+    // (dropout: the two bias gradients come from the masked operands of the weight-gradient launch, not from the LayerNorm backward)
+    float *db2 = pdrop > 0.f ? nullptr : grads + p.b2, *dbo = pdrop > 0.f ? nullptr : grads + p.b_o;
+    return LayerGrads{compact ? (const void*)dxt : (const void*)w.gA_t, compact ? 0 : 1, a.y2, a.mean2, a.rstd2, params + p.g2, a.y1, a.mean1, a.rstd1, params + p.g1, a.hpre,
+                      a.dy2_t, a.dy2m_t, a.dh_t, compact ? w.top_dy1_t : a.dy1_t, a.dqkv_t, w.gA_t,
+                      LnSinks{grads + p.g2, grads + p.be2, db2}, LnSinks{grads + p.g1, grads + p.be1, dbo}, w.ln_part};
   };
-  // The embedding's weight gradients d(src)^T . [x | masked y | train flag] are a (skinny) weight-gradient GEMM like the others:
-  // embed_fwd left the augmented inputs in operand precision, the first layer's dx leaves in operand precision, and the
-  // split-K TN kernel does the rest (the register kernel it replaces streamed d(src) at 0.7 TB/s).  Custom encoders
-  // (dsrc_sbe), the exact-f32 mode and wide encoders keep the f32 path.
-  const int aug = emb_aug_width(d->num_features);
-  const bool emb_gemm = !dsrc_sbe && prec_is16(prec) && d->nlayers > 0 && aug > 0 && E % 8 == 0;
-  bool fuse_lnb = !det && !(d->schedule & PFN_SCHED_SEPARATE_LNBWD) && prec_is16(prec) && d->nlayers > 0 && pdrop == 0.f && (E <= 512 || (d->schedule & PFN_SCHED_FUSE_LN_WIDE));   // (dropout: masked and unmasked LayerNorm-input gradients both exist)
-  if (fuse_lnb) {
-    const LayerP& p = L.layer[0]; const LayerP& t = L.layer_t[0]; LayerWs& a = w.layer[0];
-    fuse_lnb = gemm_lnbwd_supported(lnb(a.dh_t, F, WT(t.w1), F, F, a.dy2_t, a.y1, a.mean1, a.rstd1, params + p.g1, a.dy1_t, grads + p.g1, grads + p.be1, M)) &&
-               gemm_lnbwd_supported(lnb(a.dqkv_t, 3 * E, WT(t.w_in), 3 * E, 3 * E, a.dy1_t, a.y2, a.mean2, a.rstd2, params + p.g2, a.dy2_t, grads + p.g2, grads + p.be2, M));
-  }
+  const bool emb_t = emb_gemm(*d, dsrc_sbe != nullptr);
+  const bool fuse_lnb = d->nlayers > 0 && lnbwd_fusable(m, pl, lsc, view(0, false), M);
   // ---- weight gradients of the layers [l_lo, l_hi] as one grouped launch (called once after the chain, or -- data-parallel runs,
   // pfn_stack_backward_split -- once for the top layers in the middle of the chain and once for the rest) ----
   auto launch_weight_gradients = [&](int l_hi, int l_lo) -> int {
@@ -1182,86 +1244,26 @@ static int stack_backward_impl(const pfn_model_desc* d, const float* params, con
       add(drop ? a.dy1m_t : (top ? w.top_dy1_t : a.dy1_t), E, top ? w.top_ctx_t : a.ctx, E, grads + p.w_o, E, E, E, (drop || fuse_lnb) ? grads + p.b_o : nullptr, top);
       add(a.dqkv_t, 3 * E, xin_t, E, grads + p.w_in, E, 3 * E, E, grads + p.b_in);
     }
-    if (!probs_top.empty()) {
-      bool grouped_top = prec_is16(prec);
-      for (const TnProblem& t : probs_top) grouped_top = grouped_top && gemm_tn_group_supported(t);
-      if (grouped_top) {
-        ProfScope ps(PFN_PROF_WGRAD + 1, s);
-        GemmTNGroup g;
-        memset(&g, 0, sizeof(g));
-        g.n = (int)probs_top.size();
-        g.M = Mt;
-        g.splits = det ? 1 : 0;
-        g.scale_amax = lsc;
-        for (int i = 0; i < g.n; ++i) g.p[i] = probs_top[i];
-        PFN_TRY(launch_gemm_tn_group(g, prec, s));
-      } else {
-        for (const TnProblem& t : probs_top)
-          PFN_TRY(launch_gemm_tn(tn_det(tn(t.A, t.lda, t.B, t.ldb, t.C, t.ldc, Mt, t.P, t.Q, t.colsum)), prec, s));
-      }
-    }
-    bool grouped = prec_is16(prec);
-    for (const TnProblem& t : probs) grouped = grouped && gemm_tn_group_supported(t);
-    if (grouped) {
-      for (size_t i0 = 0; i0 < probs.size(); i0 += TN_GROUP_MAX) {
-        ProfScope ps(PFN_PROF_WGRAD, s);
-        GemmTNGroup g;
-        memset(&g, 0, sizeof(g));
-        g.n = (int)std::min<size_t>(TN_GROUP_MAX, probs.size() - i0);
-        g.M = M;
-        g.splits = det ? 1 : 0;
-        g.scale_amax = lsc;
-        for (int i = 0; i < g.n; ++i) g.p[i] = probs[i0 + i];
-        PFN_TRY(launch_gemm_tn_group(g, prec, s));
-      }
-    } else {  // exact-f32 parity mode and shapes outside the 256-tile kernel: one split-K launch per gradient
-      for (const TnProblem& t : probs)
-        PFN_TRY(launch_gemm_tn(tn_det(tn(t.A, t.lda, t.B, t.ldb, t.C, t.ldc, M, t.P, t.Q, t.colsum)), prec, s));
-    }
+    PFN_TRY(launch_tn_set(probs_top, Mt, prec, det, lsc, PFN_PROF_WGRAD + 1, s));
+    PFN_TRY(launch_tn_set(probs, M, prec, det, lsc, PFN_PROF_WGRAD, s));
     return PFN_OK;
   };
   const int split_at = (on_first_group && first_group_layers > 0 && first_group_layers < d->nlayers) ? d->nlayers - first_group_layers : -1;
   bool delta_zeroed = false;      // the delta scratch holds zeros for the next EPI_ROWDOT epilogue (d(ctx) below)
   for (int l = d->nlayers - 1; l >= 0; --l) {
-    const LayerP &p = L.layer[l], &t = L.layer_t[l];
+    const LayerP& t = L.layer_t[l];
     LayerWs& a = w.layer[l];
     const bool top = top_mode && l == d->nlayers - 1;      // the chain of this layer down to d(attention output) runs on the test rows (compact order)
     const int Ml = top ? Mt : M;
     char* dy1_t = top ? w.top_dy1_t : a.dy1_t;
-    // LN2: the input gradient leaves only in operand precision (dy2_t); it is both the GEMM operand below and the
-    // residual-branch gradient that the dx1 GEMM adds back, so no f32 copy is written or re-read.  (Fused: the layer above
-    // already left dy2_t.)
-    // dropout: the gradient entering linear2 (dropout2) / out_proj (dropout1) is the LayerNorm-input gradient times that site's mask;
-    // the residual path keeps the unmasked one, and the two bias gradients become column sums of the masked operands (weight-gradient launch)
-    if (!fuse_lnb || l == d->nlayers - 1)
-      PFN_TRY(launch_layernorm_bwd(top ? (const void*)dxt : (const void*)w.gA_t, top ? 0 : 1, a.y2, params + p.g2, a.mean2, a.rstd2, nullptr, a.dy2_t,
-                                   grads + p.g2, grads + p.be2, pdrop > 0.f ? nullptr : grads + p.b2, Ml, E, prec, s, w.ln_part, lsc, y16));
-    const char* dy2_op = a.dy2_t;
-    if (pdrop > 0.f) { PFN_TRY(launch_dropout_scale(a.dy2_t, a.dy2m_t, nullptr, nullptr, M, E, dseed(l, 3), pdrop, prec, s)); dy2_op = a.dy2m_t; }
-    {  // d(hpre) = (dy2 . W2) * gelu'(hpre)
-      ProfScope ps(PFN_PROF_GEMM_DHPRE + (top ? 1 : 0), s);
-      GemmNT g = nt(dy2_op, E, WT(t.w2), E, Ml, F, E, EPI_GELU_BWD | EPI_OUT_T);
-      g.aux = a.hpre; g.ld_aux = F; g.out_t = a.dh_t; g.ld_out_t = F;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
-    if (fuse_lnb) {  // dy1 = LN1 backward of (dh . W1 + dy2)
-      ProfScope ps(PFN_PROF_GEMM_DY1 + (top ? 1 : 0), s);
-      PFN_TRY(launch_gemm_lnbwd(lnb(a.dh_t, F, WT(t.w1), F, F, a.dy2_t, a.y1, a.mean1, a.rstd1, params + p.g1, dy1_t, grads + p.g1, grads + p.be1, Ml), prec, s));
-    } else {
-      {  // dx1 = dh . W1 + dy2
-        GemmNT g = nt(a.dh_t, F, WT(t.w1), F, Ml, E, F, EPI_RESID_T | EPI_OUT_T);
-        g.aux = a.dy2_t; g.ld_aux = E; g.out_t = w.gA_t; g.ld_out_t = E;
-        PFN_TRY(launch_gemm_nt(g, prec, s));
-      }
-      PFN_TRY(launch_layernorm_bwd(w.gA_t, 1, a.y1, params + p.g1, a.mean1, a.rstd1, nullptr, dy1_t, grads + p.g1, grads + p.be1,
-                                   pdrop > 0.f ? nullptr : grads + p.b_o, Ml, E, prec, s, w.ln_part, lsc, y16));
-    }
+    PFN_TRY(layer_backward_to_dy1(m, t, view(l, top), Ml, pl, fuse_lnb, fuse_lnb && l < d->nlayers - 1, lsc, pdrop, dseed(l, 3), top ? 1 : 0));
+    // dropout1: d(ctx) and out_proj's weight gradient take dy1 times that site's mask, the residual path keeps the unmasked one
     const char* dy1_op = dy1_t;
     bool delta_fused = false;
     if (pdrop > 0.f) { PFN_TRY(launch_dropout_scale(a.dy1_t, a.dy1m_t, nullptr, nullptr, M, E, dseed(l, 1), pdrop, prec, s)); dy1_op = a.dy1m_t; }
     {  // d(ctx) = dy1 . Wo
       ProfScope ps(PFN_PROF_GEMM_DCTX + (top ? 1 : 0), s);
-      GemmNT g = nt(dy1_op, E, WT(t.w_o), E, Ml, E, E, EPI_OUT_T);
+      GemmNT g = nt(dy1_op, E, WT(m, t.w_o), E, Ml, E, E, EPI_OUT_T);
       g.out_t = top ? w.top_dctx_t : w.dctx_t; g.ld_out_t = E;
       // The attention backward's delta = rowsum(dO . O) leaves with d(ctx) from this GEMM's epilogue (EPI_ROWDOT) instead of a pass of its own over dO and O
       // (attn_delta_kernel: 1.4 % of the step's kernel time) -- on the full-sequence layers of the default schedule; the test-row top layer (compact rows), the
@@ -1302,19 +1304,9 @@ static int stack_backward_impl(const pfn_model_desc* d, const float* params, con
       at.zero_delta = delta_zeroed ? 1 : 0;
       PFN_TRY(launch_attn_bwd(at, prec, s));
     }
-    if (fuse_lnb && l > 0) {  // dy2 of the layer below = its LN2 backward of (dqkv . Win + dy1)
-      ProfScope ps(PFN_PROF_GEMM_DX, s);
-      const LayerP& pb = L.layer[l - 1];
-      LayerWs& ab = w.layer[l - 1];
-      PFN_TRY(launch_gemm_lnbwd(lnb(a.dqkv_t, 3 * E, WT(t.w_in), 3 * E, 3 * E, a.dy1_t, ab.y2, ab.mean2, ab.rstd2, params + pb.g2, ab.dy2_t,
-                                    grads + pb.g2, grads + pb.be2, M), prec, s));
-    } else {  // dx = dqkv . Win + dy1
-      // the gradient stays in operand precision between layers; the embedding's gradient (layer 0) too when its weight
-      // gradients are computed as a GEMM (emb_gemm below), else it leaves in f32
-      GemmNT g = nt(a.dqkv_t, 3 * E, WT(t.w_in), 3 * E, M, E, 3 * E, EPI_RESID_T | (l == 0 && !emb_gemm ? EPI_OUT_F32 : EPI_OUT_T));
-      g.aux = a.dy1_t; g.ld_aux = E; g.out_f32 = w.gA; g.ld_out_f32 = E; g.out_t = w.gA_t; g.ld_out_t = E;
-      PFN_TRY(launch_gemm_nt(g, prec, s));
-    }
+    // (layer 0: the embedding's gradient stays in operand precision too when its weight gradients are computed as a GEMM, else it leaves in f32)
+    const LayerGrads below = l > 0 ? view(l - 1, false) : LayerGrads{};
+    PFN_TRY(layer_backward_dx(m, t, a.dqkv_t, a.dy1_t, M, pl, lsc, fuse_lnb && l > 0 ? &below : nullptr, w.gA, w.gA_t, l == 0 && !emb_t, 0));
     if (l == split_at) {
       // the chain has left the top layers: their four operand sets are complete, and so is every LayerNorm / bias gradient of theirs
       PFN_TRY(launch_weight_gradients(d->nlayers - 1, split_at));
@@ -1324,9 +1316,10 @@ static int stack_backward_impl(const pfn_model_desc* d, const float* params, con
   // ---- weight gradients of every layer not launched yet ----
   if (d->nlayers > 0) PFN_TRY(launch_weight_gradients(split_at >= 0 ? split_at - 1 : d->nlayers - 1, 0));
   // ---- embedding ----
+  const int aug = emb_aug_width(d->num_features);
   if (dsrc_sbe) {
     PFN_TRY(launch_bse_to_sbe(w.gA, dsrc_sbe, S, B, E, s, lsc));
-  } else if (emb_gemm) {
+  } else if (emb_t) {
     if (hipMemsetAsync(w.embacc, 0, sizeof(float) * E * aug, s) != hipSuccess) return fail(PFN_ERR_LAUNCH, "memset");
     GemmTN g = tn(w.gA_t, E, w.xaug_t, aug, w.embacc, aug, M, E, aug, grads + L.enc_b);
     g.scale_amax = lsc;
@@ -1355,9 +1348,9 @@ int pfn_stack_input_grads(const pfn_model_desc* d, const float* params, int B, i
   const int prec = d->precision, E = d->emsize;
   const Layout L = make_layout(*d);
   hipStream_t s = (hipStream_t)stream;
-  const bool emb_gemm = prec_is16(prec) && d->nlayers > 0 && emb_aug_width(d->num_features) > 0 && E % 8 == 0;      // (stack_backward_impl, fused embedding)
+  const bool emb_t = emb_gemm(*d, false);
   EmbedInGradArgs e; memset(&e, 0, sizeof(e));
-  e.dsrc = emb_gemm ? (const void*)w.gA_t : (const void*)w.gA; e.dsrc_prec = emb_gemm ? prec : PFN_PREC_F32;
+  e.dsrc = emb_t ? (const void*)w.gA_t : (const void*)w.gA; e.dsrc_prec = emb_t ? prec : PFN_PREC_F32;
   e.wx = params + L.enc_w; e.wy = params + L.yenc_w;
   e.dx = dx; e.dx_st = dx_st; e.dx_sb = dx_sb; e.dy = dy; e.dy_st = dy_st; e.dy_sb = dy_sb;
   e.S = S; e.B = B; e.nf = d->num_features; e.E = E; e.sep = sep;

@@ -448,6 +448,40 @@ int pfn_gp_fit_predict(const float* x, const float* y, const int32_t* n_of, cons
                        int P, int S, int nf, int kernel, const float* x_test, int m, void* ws, int64_t ws_bytes,
                        float* mean, float* var, int32_t* info, void* stream);
 
+/* ---- batched NUTS (ABI 10, additive; csrc/gp_mcmc.hip): the No-U-Turn sampler as a state machine that advances C independent chains by exactly ONE
+ * evaluation of the potential per call.  The caller owns the target: it evaluates value [C] and grad [C, ld] at trial [C, ld] (e.g. with pfn_gp_mll_grad) and
+ * calls advance, which finishes the pending leapfrog of every chain, does the leaf's bookkeeping (multinomial NUTS, iterative tree with per-leaf progressive
+ * sampling inside a subtree and biased progressive sampling between subtrees, diagonal mass, divergence at an energy error above 1000), ends / begins
+ * transitions as needed and writes the next trial point.  The potential is U_c = scale[c] value[c] - sum_k shift[k] theta_ck with gradient scale[c] grad - shift
+ * (scale [C], shift [D] nullable: 1 and 0); only columns < D of the rows of trial / grad (row stride ld >= D) are ever touched.  A non-finite value, or
+ * info[c] != 0 (info nullable), makes the leaf divergent.  1 <= D <= 128, 1 <= max_tree_depth <= 10, num_samples >= 1, num_warmup >= 0; else PFN_ERR_ARGUMENT.
+ *   init: lays out the workspace, copies theta0 [C, ld] to trial (the first advance consumes the potential AT the start point), zeroes *done_count.
+ *         chain_ids [C] int64 (NULL: 0 .. C-1) select the chain's Philox stream: chain c's whole history is a function of (seed, chain_ids[c], its own inputs).
+ *         inv_mass0 [C, D] (NULL: ones).  window_ends: HOST array of n_windows <= PFN_NUTS_MAX_WINDOWS increasing transition counts at which a slow
+ *         (mass) adaptation window ends, the first window starting at transition window_start; every end lies below num_warmup (dual averaging restarts
+ *         at a window end); used with PFN_NUTS_ADAPT_MASS.  During the num_warmup
+ *         transitions the step size follows dual averaging (gamma .05, t0 10, kappa .75, mu = log(10 step_size)) towards target_accept; afterwards it is
+ *         the averaged one.
+ *   advance: outputs per finished transition t of chain c: stats [C, W+N, 8] = (step size used, mean accept probability, tree depth, leapfrogs, diverging,
+ *         potential of the kept point, 0, 0); the kept point into samples [C, N, D] (t >= W) or, with PFN_NUTS_KEEP_WARMUP and warm != NULL, warm [C, W, D].
+ *         A chain that has finished W+N transitions adds 1 to *done_count, rests at its last sample in trial and is never written again.
+ *         W = num_warmup and N = num_samples size these buffers and must be the values given to init.  The kernel compares (C, D, max_tree_depth, W, N)
+ *         with what init recorded in the workspace; on a mismatch it touches NOTHING -- no output, no trial point, no done_count -- while the call, which
+ *         cannot read device memory without synchronising, still returns PFN_OK: a caller that passes other sizes than it initialised sees no progress.
+ * Workspace: pfn_nuts_workspace_bytes(C, D, max_tree_depth) bytes (negative on bad arguments); the current inverse mass [C, D] f32 sits at byte offset
+ * PFN_NUTS_INV_MASS_OFFSET.  Stream-ordered; nothing is allocated and nothing synchronises. */
+#define PFN_NUTS_ADAPT_MASS 1
+#define PFN_NUTS_KEEP_WARMUP 2
+#define PFN_NUTS_MAX_WINDOWS 16
+#define PFN_NUTS_INV_MASS_OFFSET 256
+int64_t pfn_nuts_workspace_bytes(int C, int D, int max_tree_depth);
+int pfn_nuts_init(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int max_tree_depth, int num_warmup, int num_samples, int flags,
+                  const int32_t* window_ends, int n_windows, int window_start, float step_size, float target_accept, uint64_t seed,
+                  const int64_t* chain_ids, const float* theta0, const float* inv_mass0, float* trial, int32_t* done_count, void* stream);
+int pfn_nuts_advance(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int max_tree_depth, int num_warmup, int num_samples,
+                     const float* value, const float* grad, const int32_t* info, const float* scale, const float* shift, float* trial,
+                     float* samples, float* stats, float* warm, int32_t* done_count, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

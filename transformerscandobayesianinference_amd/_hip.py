@@ -21,6 +21,7 @@ PREC_F32 = 1
 PREC_FP16 = 2      # fp16 MFMA operands under a device-side loss scale (include/pfn_hip.h): the timed path that holds the north star's 1e-3
 PRECISIONS = {'bf16': PREC_BF16, 'f32': PREC_F32, 'fp32': PREC_F32, 'fp16': PREC_FP16, 'f16': PREC_FP16}
 SCHED_TOP_LAYER_ALL_ROWS, SCHED_FUSE_LN_WIDE, SCHED_SEPARATE_LNBWD, SCHED_DETERMINISTIC, SCHED_NO_KEY_CENTERING, SCHED_FUSE_Q_PROJECTION, SCHED_KEY_CENTERING, SCHED_F32_RESIDUAL = 1, 2, 4, 8, 16, 32, 64, 128     # pfn_model_desc.schedule bits (include/pfn_hip.h)
+NUTS_ADAPT_MASS, NUTS_KEEP_WARMUP, NUTS_MAX_WINDOWS, NUTS_INV_MASS_OFFSET = 1, 2, 16, 256      # PFN_NUTS_* (include/pfn_hip.h)
 
 # GEMM epilogue flags (csrc/pfn_kernels.h)
 EPI_BIAS, EPI_GELU, EPI_GELU_BWD, EPI_RESID, EPI_OUT_F32, EPI_OUT_T, EPI_OUT2_T, EPI_ACCUM, EPI_RESID_T = 1, 2, 4, 8, 16, 32, 64, 128, 256
@@ -111,6 +112,12 @@ SIGNATURES = {
     'pfn_gp_mll_grad': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P]),
     # (x, y, n_of, theta, prior, P, S, nf, kernel, x_test, m, ws, ws_bytes, mean, var, info, stream)
     'pfn_gp_fit_predict': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P]),
+    # batched NUTS (ABI 10, additive).  (ws, ws_bytes, C, D, ld, max_tree_depth, num_warmup, num_samples, flags, window_ends [host int32], n_windows, window_start,
+    #  step_size, target_accept, seed, chain_ids, theta0, inv_mass0, trial, done_count, stream)
+    'pfn_nuts_workspace_bytes': (_L, [_I, _I, _I]),
+    'pfn_nuts_init': (_I, [_P, _L, _I, _I, _L, _I, _I, _I, _I, _P, _I, _I, _F, _F, _U64, _P, _P, _P, _P, _P, _P]),
+    # (ws, ws_bytes, C, D, ld, max_tree_depth, num_warmup, num_samples, value, grad, info, scale, shift, trial, samples, stats, warm, done_count, stream)
+    'pfn_nuts_advance': (_I, [_P, _L, _I, _I, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

@@ -1535,6 +1535,44 @@ int pfn_gp_fit_predict(const float* x, const float* y, const int32_t* n_of, cons
   return PFN_OK;
 }
 
+int64_t pfn_nuts_workspace_bytes(int C, int D, int max_tree_depth) {
+  if (C < 1 || D < 1 || D > 128 || max_tree_depth < 1 || max_tree_depth > 10) return -1;
+  return nuts_workspace_bytes(C, D, max_tree_depth);
+}
+static int nuts_check(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int depth) {
+  if (C < 1 || D < 1 || D > 128 || depth < 1 || depth > 10 || ld < D || !ws) return fail(PFN_ERR_ARGUMENT, "bad nuts arguments (C %d, D %d in 1..128, ld %lld >= D, max_tree_depth %d in 1..10)", C, D, (long long)ld, depth);
+  if (ws_bytes < nuts_workspace_bytes(C, D, depth)) return fail(PFN_ERR_ARGUMENT, "ws_bytes %lld < pfn_nuts_workspace_bytes = %lld", (long long)ws_bytes, (long long)nuts_workspace_bytes(C, D, depth));
+  return PFN_OK;
+}
+int pfn_nuts_init(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int max_tree_depth, int num_warmup, int num_samples, int flags, const int32_t* window_ends,
+                  int n_windows, int window_start, float step_size, float target_accept, uint64_t seed, const int64_t* chain_ids, const float* theta0,
+                  const float* inv_mass0, float* trial, int32_t* done_count, void* stream) {
+  if (int rc = nuts_check(ws, ws_bytes, C, D, ld, max_tree_depth)) return rc;
+  if (!theta0 || !trial || !done_count || num_warmup < 0 || num_samples < 1 || !(step_size > 0.f) || !(target_accept > 0.f && target_accept < 1.f))
+    return fail(PFN_ERR_ARGUMENT, "bad nuts_init arguments");
+  if (flags & ~(PFN_NUTS_ADAPT_MASS | PFN_NUTS_KEEP_WARMUP)) return fail(PFN_ERR_ARGUMENT, "unknown nuts flags 0x%x", flags);
+  if (n_windows < 0 || n_windows > PFN_NUTS_MAX_WINDOWS || (n_windows > 0 && !window_ends) || window_start < 0) return fail(PFN_ERR_ARGUMENT, "bad adaptation windows");
+  for (int i = 0; i < n_windows; ++i)
+    if (window_ends[i] <= (i ? window_ends[i - 1] : window_start) || window_ends[i] >= num_warmup)
+      return fail(PFN_ERR_ARGUMENT, "adaptation window ends must increase and lie below num_warmup (dual averaging restarts at a window end and needs transitions after it)");
+  NutsInit a{};
+  a.ws = ws; a.C = C; a.D = D; a.depth = max_tree_depth; a.ld = ld; a.W = num_warmup; a.N = num_samples; a.flags = flags; a.window_ends = window_ends; a.n_windows = n_windows;
+  a.window_start = window_start; a.step_size = step_size; a.target = target_accept; a.seed = seed; a.chain_ids = chain_ids; a.theta0 = theta0; a.inv_mass0 = inv_mass0;
+  a.trial = trial; a.done_count = done_count;
+  PFN_TRY(launch_nuts_init(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_nuts_advance(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int max_tree_depth, int num_warmup, int num_samples, const float* value, const float* grad,
+                     const int32_t* info, const float* scale, const float* shift, float* trial, float* samples, float* stats, float* warm, int32_t* done_count, void* stream) {
+  if (int rc = nuts_check(ws, ws_bytes, C, D, ld, max_tree_depth)) return rc;
+  if (!value || !grad || !trial || !samples || !stats || !done_count || num_warmup < 0 || num_samples < 1) return fail(PFN_ERR_ARGUMENT, "bad nuts_advance arguments");
+  NutsAdvance a{};
+  a.ws = ws; a.C = C; a.D = D; a.depth = max_tree_depth; a.W = num_warmup; a.N = num_samples; a.ld = ld; a.value = value; a.grad = grad; a.info = info; a.scale = scale; a.shift = shift;
+  a.trial = trial; a.samples = samples; a.stats = stats; a.warm = warm; a.done_count = done_count;
+  PFN_TRY(launch_nuts_advance(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
 int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
                           float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
                           uint64_t seed, uint64_t offset, void* stream) {

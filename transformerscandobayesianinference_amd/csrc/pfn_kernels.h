@@ -492,6 +492,27 @@ int64_t gp_fit_workspace_bytes(int P, int S);
 int launch_gp_mll_grad(const GpFitArgs& a, hipStream_t s);
 int launch_gp_fit_predict(const GpFitArgs& a, hipStream_t s);
 
+// ---- batched NUTS (gp_mcmc.hip): one gradient evaluation of every chain per launch -----------------
+struct NutsInit {
+  void* ws; int C, D, depth; long ld; int W, N, flags;
+  const int32_t* window_ends;   // HOST array [n_windows]
+  int n_windows, window_start;
+  float step_size, target; unsigned long long seed;
+  const int64_t* chain_ids;     // [C] or null (the chain's index)
+  const float* theta0;          // [C, ld]
+  const float* inv_mass0;       // [C, D] or null (ones)
+  float* trial;                 // [C, ld]
+  int32_t* done_count;
+};
+struct NutsAdvance {
+  void* ws; int C, D, depth, W, N; long ld;
+  const float* value; const float* grad; const int32_t* info; const float* scale; const float* shift;
+  float* trial; float* samples; float* stats; float* warm; int32_t* done_count;
+};
+int64_t nuts_workspace_bytes(int C, int D, int depth);
+int launch_nuts_init(const NutsInit& a, hipStream_t s);
+int launch_nuts_advance(const NutsAdvance& a, hipStream_t s);
+
 // ---- BNN prior sampler (mlp_prior.hip) -----------------------------------------------------------
 struct MlpPriorArgs {
   const float* weights;   // [num_models][Lmax][HP][HP]: layer l transposed ([in][out]), zero padded

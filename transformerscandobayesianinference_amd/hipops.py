@@ -1,5 +1,7 @@
 """Tensor-level wrappers around the single-op C-ABI entry points (`pfn_op_*`, include/pfn_hip.h): one kernel launch per call on the
 current stream.  Used by the per-kernel parity tests (tests/test_gpu_ops.py), by bench.py's kernel table and by tools/."""
+import ctypes
+
 import torch
 
 from transformerscandobayesianinference_amd import _hip
@@ -239,3 +241,66 @@ def gp_fit_predict(x, y, theta, prior, kernel, x_test, n_of=None, ws=None):
     _hip.check(_hip.lib().pfn_gp_fit_predict(x.data_ptr(), y.data_ptr(), _hip.ptr(n_of), theta.data_ptr(), prior.data_ptr(), P, S, F, int(kernel), x_test.data_ptr(), m,
                                              ws.data_ptr(), ws.numel(), mean.data_ptr(), var.data_ptr(), info.data_ptr(), _hip.stream_ptr(x.device)), 'pfn_gp_fit_predict')
     return mean, var, info
+
+
+# ---- batched NUTS (csrc/gp_mcmc.hip; include/pfn_hip.h "batched NUTS") ----
+def nuts_workspace(C, D, max_tree_depth, device):
+    """The caller-owned workspace of pfn_nuts_init / pfn_nuts_advance for C chains of D coordinates."""
+    nbytes = int(_hip.lib().pfn_nuts_workspace_bytes(C, D, max_tree_depth))
+    if nbytes < 0:
+        raise _hip.HipExtensionError(f'pfn_nuts_workspace_bytes({C}, {D}, {max_tree_depth}): need C >= 1, 1 <= D <= 128, 1 <= max_tree_depth <= 10')
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _nuts_f32(t, shape, name, device):
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.device == device and tuple(t.shape) == tuple(shape), f'{name}: want contiguous f32 {tuple(shape)} on {device}'
+
+
+def nuts_init(ws, theta0, D, max_tree_depth, num_warmup, num_samples, seed, trial, done_count, flags=0, window_start=0, window_ends=(), step_size=0.1, target_accept=0.8,
+              chain_ids=None, inv_mass=None):
+    """pfn_nuts_init: lays the state of C = theta0.shape[0] chains out in `ws` and writes the start points to trial [C, ld] (ld = theta0.shape[1] >= D)."""
+    _hip.require_gpu_tensor(theta0, 'theta0')
+    C, ld = theta0.shape
+    dev = theta0.device
+    _nuts_f32(theta0, (C, ld), 'theta0', dev)
+    _nuts_f32(trial, (C, ld), 'trial', dev)
+    assert done_count.dtype == torch.int32 and done_count.numel() == 1 and done_count.device == dev
+    if chain_ids is not None:
+        assert chain_ids.dtype == torch.int64 and chain_ids.shape == (C,) and chain_ids.is_contiguous() and chain_ids.device == dev
+    if inv_mass is not None:
+        _nuts_f32(inv_mass, (C, D), 'inv_mass', dev)
+    ends = (ctypes.c_int32 * max(1, len(window_ends)))(*[int(e) for e in window_ends])
+    _hip.check(_hip.lib().pfn_nuts_init(ws.data_ptr(), ws.numel(), C, int(D), ld, int(max_tree_depth), int(num_warmup), int(num_samples), int(flags),
+                                        ctypes.cast(ends, ctypes.c_void_p), len(window_ends), int(window_start), float(step_size), float(target_accept), int(seed) & (2 ** 64 - 1),
+                                        _hip.ptr(chain_ids), theta0.data_ptr(), _hip.ptr(inv_mass), trial.data_ptr(), done_count.data_ptr(), _hip.stream_ptr(dev)), 'pfn_nuts_init')
+
+
+def nuts_advance(ws, D, max_tree_depth, value, grad, trial, samples, stats, done_count, info=None, scale=None, shift=None, warm=None):
+    """pfn_nuts_advance: consumes value [C], grad [C, ld] (and info [C] int32) at `trial`, advances every chain by one leapfrog and writes the next trial points;
+    samples [C, N, D], stats [C, W+N, 8], warm [C, W, D] receive the rows of the transitions that finished in this call.  N and W are read off the shapes of
+    `samples` and `stats` and handed to the kernel, which does nothing unless they are the ones `nuts_init` was given: buffers of another size are never written."""
+    C, ld = trial.shape
+    dev = trial.device
+    _nuts_f32(value, (C,), 'value', dev)
+    _nuts_f32(grad, (C, ld), 'grad', dev)
+    N = samples.shape[1]
+    W = stats.shape[1] - N
+    assert N >= 1 and W >= 0, 'samples [C, N, D] and stats [C, W+N, 8]'
+    _nuts_f32(samples, (C, N, D), 'samples', dev)
+    _nuts_f32(stats, (C, W + N, 8), 'stats', dev)
+    if info is not None:
+        assert info.dtype == torch.int32 and info.shape == (C,) and info.is_contiguous() and info.device == dev
+    if scale is not None:
+        _nuts_f32(scale, (C,), 'scale', dev)
+    if shift is not None:
+        _nuts_f32(shift, (D,), 'shift', dev)
+    if warm is not None:
+        _nuts_f32(warm, (C, W, D), 'warm', dev)
+    _hip.check(_hip.lib().pfn_nuts_advance(ws.data_ptr(), ws.numel(), C, int(D), ld, int(max_tree_depth), W, N, value.data_ptr(), grad.data_ptr(), _hip.ptr(info),
+                                           _hip.ptr(scale), _hip.ptr(shift), trial.data_ptr(), samples.data_ptr(), stats.data_ptr(), _hip.ptr(warm), done_count.data_ptr(),
+                                           _hip.stream_ptr(dev)), 'pfn_nuts_advance')
+
+
+def nuts_inv_mass(ws, C, D):
+    """The chains' current inverse mass [C, D]: a view of the workspace at PFN_NUTS_INV_MASS_OFFSET."""
+    return ws[_hip.NUTS_INV_MASS_OFFSET:_hip.NUTS_INV_MASS_OFFSET + 4 * C * D].view(torch.float32).view(C, D)

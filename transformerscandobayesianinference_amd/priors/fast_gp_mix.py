@@ -27,14 +27,17 @@ no minimum there (J -> -inf with the data explained by noise alone).  L-BFGS sta
 there is one, as botorch does; `FittedGP.converged` and `.outputscale` show when it did not (a run-away outputscale ends at max_iter with
 converged False).  The tests fit with outputscale_concentration = 2.
 
-The MCMC comparison code of the reference file (get_mcmc_model, evaluate_, :172-287: pyro NUTS) is out of scope.
+The MCMC baseline of the reference (get_mcmc_model, get_mean_logdensity, evaluate_, :171-268: pyro NUTS over the kernel hyper-parameters, one (t, b) problem at a
+time) is `sample_hyperparameter_posterior` / `MCMCGP` / `get_mcmc_model` / `get_mean_logdensity` / `evaluate_` below: the potential and its gradient are the
+same device call as MAP-II (`pfn_gp_mll_grad`), the sampler is the batched NUTS of mcmc.py (`pfn_nuts_advance`, csrc/gp_mcmc.hip: every chain of every problem
+advances by one leapfrog per pass), and the per-sample predictive distributions come from `pfn_gp_fit_predict`.  INTEGRATION.md lists the deviations from pyro.
 """
 import math
 
 import torch
 from torch import nn
 
-from transformerscandobayesianinference_amd import _hip, hipops
+from transformerscandobayesianinference_amd import _hip, hipops, mcmc
 from transformerscandobayesianinference_amd.bar_distribution import BarDistribution
 from transformerscandobayesianinference_amd.priors import fast_gp
 from transformerscandobayesianinference_amd.priors.utils import get_batch_to_dataloader
@@ -452,3 +455,175 @@ def evaluate(x, y, y_non_noisy, use_mse=False, hyperparameters={}, device=defaul
         per_t = torch.cat([per_t.new_zeros(1), per_t])
     torch.cuda.synchronize(dev)
     return losses.to('cpu'), per_t.to('cpu'), time.time() - start_time
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# NUTS over the hyper-parameters (reference :171-268)
+# ---------------------------------------------------------------------------------------------------------------------
+def _memory_cap(dev, S, F):
+    per_problem = max(1, int(_hip.lib().pfn_gp_fit_workspace_bytes(1, S)) + 8 * S * (F + 1))
+    return max(1, min(EVALUATE_MAX_GROUP, int(EVALUATE_MEMORY_SHARE * torch.cuda.mem_get_info(dev)[0]) // per_problem))
+
+
+class MCMCGP:
+    """The GP under posterior samples of its hyper-parameters, P independent problems: `theta [P, N_tot, F+3]` (log lengthscale_d, log outputscale,
+    log(noise - floor), mean 0; N_tot = chains x samples, chain-major), `lengthscale [P,N_tot,F]`, `outputscale [P,N_tot]`, `noise [P,N_tot]`, `stats
+    [P, chains, W+N, 8]` (mcmc.batched_nuts), `divergences [P]` (diverging sampling transitions), `evaluations` (passes of the sampler).  Stands for both the
+    model and the likelihood of the reference's `get_mcmc_model`."""
+
+    def __init__(self, x, y, n_of, theta, prior, kernel, nu, stats, num_samples, evaluations):
+        F = x.shape[-1]
+        self._x, self._y, self._n_of, self.theta, self._prior = x, y, n_of, theta, prior
+        self.kernel, self.nu = kernel, nu
+        self.lengthscale = theta[..., :F].exp()
+        self.outputscale = theta[..., F].exp()
+        self.noise = theta[..., F + 1].exp() + MIN_INFERRED_NOISE_LEVEL
+        self.stats, self.evaluations = stats, evaluations
+        self.divergences = stats[:, :, stats.shape[2] - num_samples:, 4].sum((1, 2)).to(torch.int64)
+        self.likelihood = self
+
+    @torch.no_grad()
+    def posterior(self, x_test, use_likelihood=True):
+        """Per-sample predictive (mean, var) [P, N_tot, m] at x_test [P,m,F] through pfn_gp_fit_predict: the rows of (x, y) are gathered per sample and the
+        batch is cut to EVALUATE_MEMORY_SHARE of the free device memory.  use_likelihood=False gives the latent function: the sample's noise is subtracted
+        and the variance floored at 1e-6."""
+        dev = self._x.device
+        x_test = x_test.to(dev).float()
+        if x_test.dim() == 2:
+            x_test = x_test.unsqueeze(0)
+        P, n_tot, _ = self.theta.shape
+        m = x_test.shape[1]
+        mean = torch.empty(P, n_tot, m, dtype=torch.float32, device=dev)
+        var = torch.empty_like(mean)
+        pp = torch.arange(P, device=dev).repeat_interleave(n_tot)
+        ss = torch.arange(n_tot, device=dev).repeat(P)
+        cap = _memory_cap(dev, self._x.shape[1], self._x.shape[2])
+        for lo in range(0, P * n_tot, cap):
+            p_, s_ = pp[lo:lo + cap], ss[lo:lo + cap]
+            mu, v, _ = hipops.gp_fit_predict(self._x[p_].contiguous(), self._y[p_].contiguous(), self.theta[p_, s_].contiguous(), self._prior, self.kernel,
+                                             x_test[p_].contiguous(), n_of=self._n_of[p_].contiguous())
+            mean[p_, s_], var[p_, s_] = mu, v
+        if not use_likelihood:
+            var = (var - self.noise.unsqueeze(-1)).clamp_min(1e-6)
+        return mean, var
+
+    @torch.no_grad()
+    def log_density(self, x_test, y_test, full_range=None, use_likelihood=True):
+        """log of the posterior-predictive mixture density at y_test [P,m]: logsumexp over the samples of the normal log densities minus log N_tot, every
+        component renormalised to `full_range` when given (reference get_mean_logdensity, :203-217).  Returns [P,m]."""
+        mean, var = self.posterior(x_test, use_likelihood)
+        y_test = y_test.to(mean.device).float().reshape(mean.shape[0], 1, -1)
+        return _mixture_logdensity(mean, var, y_test, full_range, dim=1)
+
+
+def _mixture_logdensity(mean, var, y, full_range, dim):
+    sd = var.sqrt()
+    logp = -0.5 * math.log(2 * math.pi) - sd.log() - 0.5 * ((y - mean) / sd) ** 2
+    if full_range is not None:
+        cdf = lambda v: 0.5 * (1. + torch.erf((float(v) - mean) / (sd * math.sqrt(2.))))
+        logp = logp - torch.log(1. - (cdf(full_range[0]) + (1. - cdf(full_range[1]))))
+    return torch.logsumexp(logp, dim) - math.log(mean.shape[dim])
+
+
+@torch.no_grad()
+def sample_hyperparameter_posterior(x, y, hyperparameters=None, n_of=None, num_samples=100, warmup_steps=300, num_chains=1, seed=0, kernel=None, init=None,
+                                    chain_id_base=0, **nuts_kwargs):
+    """NUTS over the log hyper-parameters of P independent GPs: x [P,S,F], y [P,S] on the GPU; problem p uses its first n_of[p] rows.  The potential is
+    U(theta) = n J(theta) - sum_{k < F+2} theta_k: the negative unnormalised log posterior of the natural values (J is the MAP-II objective per point,
+    `pfn_gp_mll_grad`) plus the Jacobian of the exp transform -- pyro samples in the same unconstrained space -- with the noise prior on
+    noise = exp(eta) + floor; the constant mean stays at 0 as in the reference, whose NUTS samples only the parameters that have priors.  The chains of a
+    problem are extra rows of the batch; chain j of problem p draws from Philox stream chain_id_base + p num_chains + j, so a sub-batch with the
+    matching base reproduces its part of the full batch bit for bit.  init: theta [P,F+3] replacing `default_theta`.  nuts_kwargs go to
+    mcmc.batched_nuts (step_size, target_accept, max_tree_depth, adapt_mass, sync_every).  Returns an `MCMCGP`."""
+    if x.device.type != 'cuda':
+        raise _hip.HipExtensionError(f'NUTS over the GP hyper-parameters runs on the GPU only (got device {x.device}); no CPU fallback')
+    kernel, nu = _kernel_of(hyperparameters, kernel)
+    dev = x.device
+    P, S, F = x.shape
+    K = int(num_chains)
+    xp, yp = x.float(), y.float().reshape(P, S)
+    n_of = torch.full((P,), S, dtype=torch.int32, device=dev) if n_of is None else torch.as_tensor(n_of, device=dev).to(torch.int32).clamp(1, S).contiguous()
+    Sp = (S + 3) // 4 * 4
+    if Sp != S:      # padded rows are masked through n_of: nothing in them is read
+        xp = torch.cat([xp, xp.new_zeros(P, Sp - S, F)], 1)
+        yp = torch.cat([yp, yp.new_zeros(P, Sp - S)], 1)
+    xp, yp = xp.contiguous(), yp.contiguous()
+    prior = hyperprior_vector(hyperparameters, dev)
+    theta0 = default_theta(P, F, hyperparameters, dev) if init is None else torch.as_tensor(init, dtype=torch.float32, device=dev).reshape(P, F + 3).clone()
+    theta0[:, F + 2] = 0.
+    xc, yc, nc = xp.repeat_interleave(K, 0), yp.repeat_interleave(K, 0), n_of.repeat_interleave(K)
+    ws = hipops.gp_fit_workspace(P * K, Sp, dev)
+
+    def fun(theta):
+        return hipops.gp_mll_grad(xc, yc, theta, prior, kernel, n_of=nc, flags=1, ws=ws)
+
+    ids = int(chain_id_base) + torch.arange(P * K, dtype=torch.int64, device=dev)
+    res = mcmc.batched_nuts(fun, theta0.repeat_interleave(K, 0), num_samples, warmup_steps, seed=seed, chain_ids=ids, scale=nc.float(),
+                            shift=torch.ones(F + 2, device=dev), D=F + 2, **nuts_kwargs)
+    theta = torch.zeros(P * K, num_samples, F + 3, dtype=torch.float32, device=dev)
+    theta[..., :F + 2] = res['samples']
+    return MCMCGP(xp, yp, n_of, theta.reshape(P, K * num_samples, F + 3), prior, kernel, nu, res['stats'].reshape(P, K, -1, 8), num_samples, res['evaluations'])
+
+
+def get_mcmc_model(x, y, hyperparameters, device, num_samples, warmup_steps):
+    """Reference :171-196: the model under `num_samples` NUTS draws of its hyper-parameters after `warmup_steps`, and its likelihood -- one object plays both
+    parts, as in `get_fitted_model`.  x [n,F] or [P,n,F], y [n], [n,1] or [P,n]."""
+    _reject_output_warping(hyperparameters)
+    if torch.device(device).type != 'cuda':
+        raise _hip.HipExtensionError(f'NUTS over the GP hyper-parameters runs on the GPU only (got device {device}); no CPU fallback')
+    x = torch.as_tensor(x).to(device).float()
+    x = x if x.dim() == 3 else x.unsqueeze(0)
+    y = torch.as_tensor(y).to(device).float().reshape(x.shape[0], x.shape[1])
+    model = sample_hyperparameter_posterior(x, y, hyperparameters, num_samples=num_samples, warmup_steps=warmup_steps)
+    return model, model.likelihood
+
+
+def get_mean_logdensity(dists, x, full_range=None):
+    """Reference :203-217: the log of the equally weighted mixture of normals N(d.mean, d.variance) over every component of every object of `dists`, at the
+    scalar x; with full_range = (lo, hi) every component is first renormalised to its mass inside the range."""
+    means = torch.cat([d.mean.reshape(-1) for d in dists], 0)
+    variances = torch.cat([d.variance.reshape(-1) for d in dists], 0)
+    return _mixture_logdensity(means, variances, torch.as_tensor(x, dtype=means.dtype, device=means.device), full_range, dim=0)
+
+
+@torch.no_grad()
+def evaluate_(x, y, y_non_noisy, hyperparameters=None, device=default_device, num_samples=100, warmup_steps=300, full_range=None, min_seq_len=0,
+              use_likelihood=False, seed=0):
+    """The NUTS baseline (reference :220-268): for every t in range(max(min_seq_len, 1), T) and every dataset b, the hyper-parameters are sampled given rows
+    [:t] of (x[:, b], y[:, b]) and the loss is minus the log of the mixture density of y[t, b] under the per-sample predictives (of the latent function
+    unless use_likelihood).  x [T,B,F], y [T,B].  Returns the reference's triple: (mean loss per t as a tensor, with a leading 0. when min_seq_len == 0;
+    seconds; the losses per t as a list of lists over b).  All (t, b) problems are batched in the 64-row buckets of `evaluate`; problem (t, b) draws from
+    Philox stream index(t) B + b whatever the grouping."""
+    import time
+    start_time = time.time()
+    _reject_output_warping(hyperparameters)
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _hip.HipExtensionError(f'NUTS over the GP hyper-parameters runs on the GPU only (got device {dev}); no CPU fallback')
+    T, B, F = x.shape
+    xb = x.to(dev).float().transpose(0, 1).contiguous()
+    yb = y.to(dev).float().reshape(T, B).transpose(0, 1).contiguous()
+    ts = list(range(max(min_seq_len, 1), T))
+    losses = torch.zeros(len(ts), B, dtype=torch.float32, device=dev)
+    buckets = {}
+    for i, t in enumerate(ts):
+        buckets.setdefault((t + 63) // 64 * 64, []).append(i)
+    for Sb, members in sorted(buckets.items()):
+        xs, ys = xb[:, :Sb], yb[:, :Sb]
+        if Sb > T:
+            xs = torch.cat([xs, xs.new_zeros(B, Sb - T, F)], 1)
+            ys = torch.cat([ys, ys.new_zeros(B, Sb - T)], 1)
+        cap = _memory_cap(dev, Sb, F)
+        ii = torch.as_tensor([i for i in members for _ in range(B)], dtype=torch.long, device=dev)
+        tt = torch.as_tensor([ts[i] for i in members for _ in range(B)], dtype=torch.long, device=dev)
+        bb = torch.arange(B, device=dev).repeat(len(members))
+        for lo in range(0, len(tt), cap):      # (a bucket's positions are consecutive, so its problems' stream indices are too)
+            i_, t_, b_ = ii[lo:lo + cap], tt[lo:lo + cap], bb[lo:lo + cap]
+            model = sample_hyperparameter_posterior(xs[b_], ys[b_], hyperparameters, n_of=t_, num_samples=num_samples, warmup_steps=warmup_steps, seed=seed,
+                                                    chain_id_base=members[0] * B + lo)
+            losses[i_, b_] = -model.log_density(xb[b_, t_].unsqueeze(1), yb[b_, t_].unsqueeze(1), full_range, use_likelihood)[:, 0]
+    per_t = losses.mean(1)
+    if min_seq_len == 0:
+        per_t = torch.cat([per_t.new_zeros(1), per_t])
+    torch.cuda.synchronize(dev)
+    return per_t.to('cpu'), time.time() - start_time, losses.to('cpu').tolist()

@@ -14,7 +14,7 @@ EXTRA=""
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
   objs=""
-  for o in pfn_api gemm attention rowwise bar optim gp_prior mlp_prior; do
+  for o in pfn_api gemm gemm_tn attention rowwise bar optim gp_prior gp_fit gp_mcmc mlp_prior; do
     if [ $o = $STEM ]; then objs="$objs ../_variants/${STEM}_$name.o"; else objs="$objs ../_build/$o.o"; fi
   done
   ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result $EXTRA $flags -c $SRC -o ../_variants/${STEM}_$name.o &&

@@ -154,17 +154,33 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmTN g) {
 //   * 256 x 256 tile, 64-token stages, 8 waves as 2 (P) x 4 (Q), each 128 x 64;
 //   * both operands are token-major, so their LDS images are [token][256 columns] (512-byte rows)
 //     filled by LDS-DMA and read through ds_read_b64_tr_b16; the 64-byte-unit XOR swizzle of
-//     load_frag_tr is applied to the per-lane DMA source address;
+//     load_frag_tr is applied to the per-lane DMA source offset;
+//   * operand staging (TnStager, shared with gemm_tn_wide_kernel): one buffer descriptor per operand and workgroup whose base is
+//     the first token row of the stage requested next and whose num_records ends at the LAST ROW OF THE TOKEN SPLIT.  A lane's
+//     byte offsets (token row of its piece x row pitch + swizzled column) are computed once in front of the loop; per stage only
+//     the descriptor moves, in scalar registers (pfn_device.h dma_rsrc_advance).  Rows past the end of the split fail the range
+//     check and arrive in LDS as zeros, for A and for B: a ragged last stage needs no clamp, no branch and no clearing pass.
+//     The stage loop reads nothing from the problem table and multiplies no addresses (it used to: a scalar load with its wait,
+//     sixteen 64-bit multiply-adds and the clamps per wave and stage, then a zero-fill loop with a second barrier for the tail);
 //   * bias gradients (column sums of A) ride along as one extra MFMA against a constant ones
 //     fragment in the workgroups of the first Q tile, split over the four Q waves.
-// Requirements: P % 256 == 0, Q % 256 == 0, 16-byte aligned rows.
+// Requirements: P % 256 == 0, Q % 256 == 0, 16-byte aligned rows, row pitches of at least 256 elements, and -- the lane offsets and
+// the descriptor's num_records are 32-bit -- token split rows x row pitch x 2 bytes <= 0x7ffffff0 for both operands
+// (launch_gemm_tn_group answers PFN_ERR_UNSUPPORTED otherwise).
 // ---------------------------------------------------------------------------------------------
 // Stage depth / ring length (experiment builds: tools/build_variants.sh with -DPFN_TNB_KT= -DPFN_TNB_NS=).  Measured at the north
-// star (tools/bench_wgrad.py): 64 x 2 950 us, 32 x 3 952, 32 x 4 965, 32 x 5 965 -- up to four stages in flight instead of one change
-// nothing, i.e. the operand stream is bound by its rate (6.9 TB/s of LDS-DMA traffic, 2.6 TB/s of it from HBM), not by latency.
+// star (tools/bench_wgrad.py --batch 16) with the per-stage address arithmetic still in the loop: 64 x 2 950 us, 32 x 3 952, 32 x 4 965,
+// 32 x 5 965; and again without it (--batch 32, profiles/wgrad_stage_issue.txt): 64 x 2 1566-1621 us, 32 x 3 1706-1716, 32 x 4 1743,
+// 32 x 5 1730-1748 -- up to four stages in flight instead of one buy nothing either way: the operand stream is not bound by latency.
+// The address arithmetic itself was 130 us of the 1734-1767 us the launch took with it, its position another 30: requested right behind
+// the stage barrier the issue block (8 DMA instructions and 70 scalar ones) holds up the first fragment reads of all eight waves at once;
+// behind the first 16-token step's MFMAs (PFN_TNB_LATE_ISSUE, the slot it fills is free from the barrier on) it runs under them.
 #ifndef PFN_TNB_KT
 #define PFN_TNB_KT 64
 #define PFN_TNB_NS 2
+#endif
+#ifndef PFN_TNB_LATE_ISSUE
+#define PFN_TNB_LATE_ISSUE 1      // 1: the next stage's DMA is issued behind the first 16-token step's MFMAs (measured faster); 0: right behind the stage barrier
 #endif
 constexpr int TNB_KT = PFN_TNB_KT;               // tokens per stage
 constexpr int TNB_NS = PFN_TNB_NS;               // stages in the LDS ring: TNB_NS - 1 of them in flight under the one being multiplied
@@ -172,6 +188,53 @@ constexpr int TNB_TILE = TNB_KT * 512;           // bytes per operand per stage
 constexpr int TNB_PW = TNB_KT / 16;              // 1-KiB DMA pieces per wave per operand per stage (a piece = 2 token rows x 512 B)
 constexpr int TNB_LDS = TNB_NS * 2 * TNB_TILE;
 static_assert(TNB_LDS <= 160 * 1024 && TNB_KT % 16 == 0 && TNB_NS >= 2 && (TNB_NS - 2) * 2 * TNB_PW < 64, "weight-gradient ring does not fit");
+constexpr long TN_GROUP_MAX_SPLIT_BYTES = 0x7ffffff0L;      // token split rows x row pitch x 2 (TnStager's 32-bit byte range)
+
+// Operand staging of the grouped kernels (NW waves; a 1-KiB DMA piece is 2 token rows x 512 B, wave w moves pieces w, w + NW, ... of each
+// operand's stage).  16-bit operands.
+template <int NW> struct TnStager {
+  static constexpr int NP = TNB_KT / 2 / NW;      // pieces per wave per operand per stage
+  DmaRsrc ra, rb;                                 // base: first row of the stage requested next; num_records: from there to the end of the split's last row
+  unsigned a_lo, a_hi, b_lo, b_hi;                // the split's first row (where the profiling wrap goes back to)
+  unsigned step_a, step_b;                        // bytes per stage
+  int va[NP], vb[NP];                             // the lane's byte offset for each of its pieces
+  int wave, srow, mask;                           // srow: token row (inside the split) of the stage requested next
+  PFN_DEV void init(const TnProblem& pr, long mbeg, int rows, int p0, int q0, int wave_, int lane, int debug_mask) {
+    const long lda2 = pr.lda * 2, ldb2 = pr.ldb * 2;
+    ra = make_dma_rsrc(reinterpret_cast<const char*>(pr.A) + mbeg * lda2 + p0 * 2, (rows - 1) * lda2 + 512);
+    rb = make_dma_rsrc(reinterpret_cast<const char*>(pr.B) + mbeg * ldb2 + q0 * 2, (rows - 1) * ldb2 + 512);
+    a_lo = ra.w[0]; a_hi = ra.w[1]; b_lo = rb.w[0]; b_hi = rb.w[1];
+    step_a = __builtin_amdgcn_readfirstlane((unsigned)(TNB_KT * lda2));
+    step_b = __builtin_amdgcn_readfirstlane((unsigned)(TNB_KT * ldb2));
+    wave = wave_; srow = 0; mask = debug_mask;
+    const int row0 = wave * 2 + (lane >> 5);
+    const int colb = ((((lane & 31) >> 2) ^ (row0 & 3)) * 32 + (lane & 3) * 8) * 2;      // 2 NW i = 0 mod 4: the swizzle is the same for every piece
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      va[i] = (row0 + 2 * NW * i) * (int)lda2 + colb;
+      vb[i] = (row0 + 2 * NW * i) * (int)ldb2 + colb;
+    }
+  }
+  // request the next stage into the ring slot at `slot` (A tile, then B tile), then move on by one stage
+  PFN_DEV void issue(LdsPtr slot) {
+    LdsPtr ta = slot + wave * 1024;
+    LdsPtr tb = ta + TNB_TILE;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      // assembly form (pfn_device.h dma16): with the builtin hipcc waits vmcnt(0) in front of the first ds_read_b64_tr_b16 of
+      // the stage being MULTIPLIED -- the intrinsic carries no address, so the DMA just issued for a LATER stage "may alias" --
+      // and the copy never overlapped the MFMAs
+      dma16(ra, ta + i * NW * 1024, va[i]);
+      dma16(rb, tb + i * NW * 1024, vb[i]);
+    }
+    dma_rsrc_advance(ra, step_a);
+    dma_rsrc_advance(rb, step_b);
+    srow += TNB_KT;
+    // profiling with cache-resident operands (GemmTNGroup::debug_mask = 2^k - 1 >= TNB_KT - 1): the stage row wraps, i.e. the bases go back to the
+    // split's first row (num_records keeps counting down, so the ragged tail is still cut).  All ones otherwise: never taken.
+    if ((srow & mask) == 0) { ra.w[0] = a_lo; ra.w[1] = a_hi; rb.w[0] = b_lo; rb.w[1] = b_hi; }
+  }
+};
 
 template <typename T>
 __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
@@ -195,33 +258,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int wp = wave >> 2, wq = wave & 3;
 
-  // DMA sources: a 1-KiB piece is 2 token rows x 512 B; wave w moves pieces w, w + 8, ... of each operand's stage
-  const T* pa[TNB_PW];
-  const T* pb[TNB_PW];
-  int prow[TNB_PW];
-#pragma unroll
-  for (int i = 0; i < TNB_PW; ++i) {
-    const int row = (wave + 8 * i) * 2 + (lane >> 5);
-    const int unit = ((lane & 31) >> 2) ^ (row & 3);
-    const int col = unit * 32 + (lane & 3) * 8;
-    prow[i] = row;
-    pa[i] = reinterpret_cast<const T*>(pr.A) + mbeg * pr.lda + p0 + col;
-    pb[i] = reinterpret_cast<const T*>(pr.B) + mbeg * pr.ldb + q0 + col;
-  }
-  auto stage = [&](int slot, int r0) {
-    LdsPtr ta = smem + slot * 2 * TNB_TILE + wave * 1024;
-    LdsPtr tb = ta + TNB_TILE;
-#pragma unroll
-    for (int i = 0; i < TNB_PW; ++i) {
-      // tail rows are re-zeroed in LDS below; debug_mask is all ones except when profiling with cache-resident operands
-      const long r = min(r0 + prow[i], rows_total - 1) & g.debug_mask;
-      // assembly form (pfn_device.h dma16): with the builtin hipcc waits vmcnt(0) in front of the first ds_read_b64_tr_b16 of
-      // the stage being MULTIPLIED -- the intrinsic carries no address, so the DMA just issued for a LATER stage "may alias" --
-      // and the copy never overlapped the MFMAs
-      dma16_global(pa[i] + r * pr.lda, ta + i * 8192);
-      dma16_global(pb[i] + r * pr.ldb, tb + i * 8192);
-    }
-  };
+  TnStager<8> stg;
+  stg.init(pr, mbeg, rows_total, p0, q0, wave, lane, g.debug_mask);
+  static_assert(TnStager<8>::NP == TNB_PW, "wait_stage counts 2 TNB_PW DMA instructions per stage");
 
   f32x16 acc[4][2];
 #pragma unroll
@@ -246,8 +285,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
   // touching 2 / 3 / 5 stages ahead.)
 #pragma unroll
   for (int st = 0; st < TNB_NS - 1; ++st)
-    if (st < nt) stage(st, st * TNB_KT);
+    if (st < nt) stg.issue(smem + st * 2 * TNB_TILE);
   auto wait_stage = [&](int younger) {     // `younger` stages were requested after the one wanted now (wave-uniform)
+    if constexpr (TNB_NS == 2) { wait_vm_barrier<0>(); return; }      // one stage in flight: nothing to count, no branch
     switch (younger) {
       case 0: wait_vm_barrier<0>(); break;
       case 1: wait_vm_barrier<(TNB_NS > 2 ? 1 : 0) * 2 * TNB_PW>(); break;
@@ -263,19 +303,10 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
     int slot = 0, slot_next = TNB_NS - 1;
     for (int t = 0; t < nt; ++t) {
       wait_stage(min(nt - t - 1, TNB_NS - 2));
-      if (t + TNB_NS - 1 < nt) stage(slot_next, (t + TNB_NS - 1) * TNB_KT);
+      const bool more = t + TNB_NS - 1 < nt;
+      if (!PFN_TNB_LATE_ISSUE && more) stg.issue(smem + slot_next * 2 * TNB_TILE);
       LdsPtr ta = smem + slot * 2 * TNB_TILE;
       LdsPtr tb = ta + TNB_TILE;
-      const int valid = rows_total - t * TNB_KT;
-      if (valid < TNB_KT) {
-        // ragged last stage: the DMA clamped its source rows; clear the rows past the end (A only:
-        // a zero A row contributes nothing whatever B holds there, and B's clamped rows are finite data)
-        for (int idx = threadIdx.x; idx < (TNB_KT - valid) * 32; idx += 512) {
-          const u32x4 z = {0u, 0u, 0u, 0u};
-          lds_write16(ta + (valid + idx / 32) * 512 + (idx % 32) * 16, z);
-        }
-        __syncthreads();
-      }
 #pragma unroll
       for (int ks = 0; ks < TNB_KT; ks += 16) {
         Frag<T> fa[4], fb[2];
@@ -289,6 +320,11 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
           for (int j = 0; j < 2; ++j) acc[i][j] = mma32(fa[i], fb[j], acc[i][j]);
         // bias gradient: Q wave wq sums the columns of P sub-tile wq (one more fragment read, one more MFMA)
         if constexpr (CS) cs = mma32(load_frag_tr<T, 512, 1>(ta, ks, wp * 128 + wq * 32), ones, cs);
+        if (PFN_TNB_LATE_ISSUE && ks == 0) {      // the slot is free from the stage barrier on: the issue block goes under the first step's MFMAs
+          PFN_PIN_LDS_MFMA();
+          if (more) stg.issue(smem + slot_next * 2 * TNB_TILE);
+          PFN_PIN_LDS_MFMA();
+        }
       }
       slot_next = slot;
       slot = slot + 1 == TNB_NS ? 0 : slot + 1;
@@ -333,10 +369,14 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
 // Price: the 16 accumulator tiles are 256 registers, so a wave needs the whole register file (one wave per SIMD: no second wave to cover its LDS round trips) --
 // the fragments of step s + 1 are therefore requested before the MFMAs of step s (two fragment sets, PFN_PIN_LDS_MFMA keeps the machine scheduler from sinking the
 // reads back to their consumers), the first step of the next stage right behind the stage barrier.
+// With the staging of gemm_tn_big_kernel (TnStager; the clamp and the 64-bit multiply per piece were in this loop too): 1977-1985 us against 2014-2041 us at the
+// north star's 64 000 tokens, against 1566-1621 us of the eight-wave kernel (profiles/wgrad_stage_issue.txt): eight waves stay the default.
 // ---------------------------------------------------------------------------------------------
+// Written for two 64-token stages: the experiment builds with another stage depth / ring length (PFN_TNB_KT / PFN_TNB_NS above) leave it out, and the launcher then
+// refuses PFN_TUNE_WGRAD_WAVES = 4.
+#define PFN_TNW_BUILT (PFN_TNB_KT == 64 && PFN_TNB_NS == 2)
+#if PFN_TNW_BUILT
 constexpr int TNW_NW = 4;                              // waves: 2 (P) x 2 (Q), each 128 x 128
-constexpr int TNW_PW = TNB_KT / 2 / TNW_NW;            // 1-KiB DMA pieces per wave per operand per stage
-static_assert(TNB_KT == 64 && TNB_NS == 2, "gemm_tn_wide_kernel is written for two 64-token stages");
 template <typename T>
 __global__ __launch_bounds__(TNW_NW * 64, 1) void gemm_tn_wide_kernel(GemmTNGroup g) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -357,23 +397,8 @@ __global__ __launch_bounds__(TNW_NW * 64, 1) void gemm_tn_wide_kernel(GemmTNGrou
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int wp = wave >> 1, wq = wave & 1;
 
-  // DMA sources: piece i of this wave = token rows (wave + 4 i) * 2 + (lane >> 5); the swizzled column depends on row & 3 only, i.e. not on i (8 i = 0 mod 4):
-  // ONE pointer per operand, the row offset added per piece (sixteen 64-bit pointers would not fit beside 256 accumulator registers)
-  const int prow0 = wave * 2 + (lane >> 5);
-  const int pcol = ((((lane & 31) >> 2) ^ (prow0 & 3)) * 32) + (lane & 3) * 8;
-  const T* pa = reinterpret_cast<const T*>(pr.A) + mbeg * pr.lda + p0 + pcol;
-  const T* pb = reinterpret_cast<const T*>(pr.B) + mbeg * pr.ldb + q0 + pcol;
-  const long lda = pr.lda, ldb = pr.ldb;
-  auto stage = [&](int slot, int r0) {
-    LdsPtr ta = smem + slot * 2 * TNB_TILE + wave * 1024;
-    LdsPtr tb = ta + TNB_TILE;
-#pragma unroll
-    for (int i = 0; i < TNW_PW; ++i) {
-      const long r = min(r0 + prow0 + 2 * TNW_NW * i, rows_total - 1) & g.debug_mask;
-      dma16_global(pa + r * lda, ta + i * TNW_NW * 1024);
-      dma16_global(pb + r * ldb, tb + i * TNW_NW * 1024);
-    }
-  };
+  TnStager<TNW_NW> stg;      // the staging of gemm_tn_big_kernel: loop-invariant lane offsets, the descriptors advance per stage, the ragged tail arrives as zeros
+  stg.init(pr, mbeg, rows_total, p0, q0, wave, lane, g.debug_mask);
 
   f32x16 acc[4][4];
 #pragma unroll
@@ -412,19 +437,10 @@ __global__ __launch_bounds__(TNW_NW * 64, 1) void gemm_tn_wide_kernel(GemmTNGrou
       }
     };
     // stage t has landed for every wave and every read of the slot it is about to overwrite has retired (wait_vm_barrier waits lgkmcnt(0) too);
-    // request stage t + 1 into the other slot; clear the rows past the end of a ragged last stage
+    // request stage t + 1 into the other slot
     auto enter_stage = [&](int t, int slot) {
       wait_vm_barrier<0>();
-      if (t + 1 < nt) stage(slot ^ 1, (t + 1) * TNB_KT);
-      const int valid = rows_total - t * TNB_KT;
-      if (valid < TNB_KT) {
-        LdsPtr ta = smem + slot * 2 * TNB_TILE;
-        for (int idx = threadIdx.x; idx < (TNB_KT - valid) * 32; idx += TNW_NW * 64) {
-          const u32x4 z = {0u, 0u, 0u, 0u};
-          lds_write16(ta + (valid + idx / 32) * 512 + (idx % 32) * 16, z);
-        }
-        __syncthreads();
-      }
+      if (t + 1 < nt) stg.issue(smem + (slot ^ 1) * 2 * TNB_TILE);
     };
     int slot = 0;
     enter_stage(0, slot);
@@ -455,7 +471,7 @@ __global__ __launch_bounds__(TNW_NW * 64, 1) void gemm_tn_wide_kernel(GemmTNGrou
       PFN_PIN_LDS_MFMA();
     }
   };
-  stage(0, 0);
+  stg.issue(smem);
   if (do_colsum) main_loop(std::true_type{});
   else main_loop(std::false_type{});
 
@@ -480,6 +496,7 @@ __global__ __launch_bounds__(TNW_NW * 64, 1) void gemm_tn_wide_kernel(GemmTNGrou
         if (pp < pv) unsafeAtomicAdd(pr.C + (long)pp * pr.ldc + qq, acc[i][j][r] * osc);
       }
 }
+#endif      // PFN_TNW_BUILT
 
 // ---------------------------------------------------------------------------------------------
 // host launchers
@@ -546,8 +563,16 @@ int launch_gemm_tn_group(GemmTNGroup g, int precision, hipStream_t stream) {
   splits = (g.M + chunk - 1) / chunk;
   g.splits = splits;
   g.m_chunk = chunk;
-  g.debug_mask = g_tn_debug_wrap > 0 ? g_tn_debug_wrap - 1 : 0x7fffffff;
+  // TnStager: 32-bit lane offsets and num_records, and a row pitch that keeps the row behind the split's last one out of range
+  for (int i = 0; i < g.n; ++i) {
+    const TnProblem& p = g.p[i];
+    if (p.lda < 256 || p.ldb < 256 || (long)chunk * p.lda * 2 > TN_GROUP_MAX_SPLIT_BYTES || (long)chunk * p.ldb * 2 > TN_GROUP_MAX_SPLIT_BYTES) return PFN_ERR_UNSUPPORTED;
+  }
+  // PFN_TUNE_GEMM_TN_WRAP: a power of two >= TNB_KT wraps the stage row; anything else leaves the wrap off
+  const int wrap = g_tn_debug_wrap;
+  g.debug_mask = wrap >= TNB_KT && (wrap & (wrap - 1)) == 0 ? wrap - 1 : 0x7fffffff;
   if (g_tn_wide) {      // PFN_TUNE_WGRAD_WAVES = 4: four waves of 128 x 128 (gemm_tn_wide_kernel)
+#if PFN_TNW_BUILT
     static LdsAllowance allow_w[2];
     if (precision == PFN_PREC_FP16) {
       allow_w[1].ensure(gemm_tn_wide_kernel<f16>, TNB_LDS);
@@ -557,6 +582,9 @@ int launch_gemm_tn_group(GemmTNGroup g, int precision, hipStream_t stream) {
       hipLaunchKernelGGL(gemm_tn_wide_kernel<bf16>, dim3(tiles * splits), dim3(TNW_NW * 64), TNB_LDS, stream, g);
     }
     return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+#else
+    return PFN_ERR_UNSUPPORTED;
+#endif
   }
   static LdsAllowance allowance[2];
   if (precision == PFN_PREC_FP16) {

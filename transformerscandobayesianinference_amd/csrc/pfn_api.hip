@@ -477,15 +477,17 @@ bool tn_set_groupable(const std::vector<TnProblem>& probs, int prec) {
   return grouped;
 }
 int launch_tn_set(const std::vector<TnProblem>& probs, int rows, int prec, bool det, const float* lsc, int prof_slot, hipStream_t s, bool allow_group = true) {
-  if (!(allow_group && tn_set_groupable(probs, prec))) {
-    for (const TnProblem& t : probs) {
+  auto one_by_one = [&](size_t i0, size_t n) {
+    for (size_t i = i0; i < i0 + n; ++i) {
+      const TnProblem& t = probs[i];
       GemmTN g = tn(t.A, t.lda, t.B, t.ldb, t.C, t.ldc, rows, t.Pv ? t.Pv : t.P, t.Q, t.colsum);
       if (det) g.max_splits = 1;
       g.scale_amax = lsc;
       PFN_TRY(launch_gemm_tn(g, prec, s));
     }
-    return PFN_OK;
-  }
+    return (int)PFN_OK;
+  };
+  if (!(allow_group && tn_set_groupable(probs, prec))) return one_by_one(0, probs.size());
   for (size_t i0 = 0; i0 < probs.size(); i0 += TN_GROUP_MAX) {
     ProfScope ps(prof_slot, s);
     GemmTNGroup g;
@@ -495,7 +497,9 @@ int launch_tn_set(const std::vector<TnProblem>& probs, int rows, int prec, bool 
     g.splits = det ? 1 : 0;
     g.scale_amax = lsc;
     for (int i = 0; i < g.n; ++i) g.p[i] = probs[i0 + i];
-    PFN_TRY(launch_gemm_tn_group(g, prec, s));
+    const int rc = launch_gemm_tn_group(g, prec, s);
+    if (rc == PFN_ERR_UNSUPPORTED) PFN_TRY(one_by_one(i0, g.n));      // a token split beyond the grouped kernel's 32-bit byte range (gemm_tn.hip)
+    else PFN_TRY(rc);
   }
   return PFN_OK;
 }

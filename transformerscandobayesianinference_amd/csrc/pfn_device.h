@@ -342,6 +342,16 @@ PFN_DEV DmaRsrc make_dma_rsrc(const void* base, long bytes) {
   r.w[3] = 0x00020000u;
   return r;
 }
+// A descriptor that walks along its tensor in scalar registers: the base moves up by `bytes` and num_records shrinks by the same
+// (not below zero), so the range check keeps ending at the same last byte while the per-lane offsets stay loop-invariant.
+// (A scalar offset operand of the load would move the address as well, but it takes no part in the range check.)
+// bytes <= 0x7ffffff0; stride 0, so the upper half of word 1 is empty and the 48-bit base may carry into it freely.
+PFN_DEV void dma_rsrc_advance(DmaRsrc& r, unsigned bytes) {
+  const unsigned long long b = (((unsigned long long)r.w[1] << 32) | r.w[0]) + bytes;
+  r.w[0] = (unsigned)b;
+  r.w[1] = (unsigned)(b >> 32);
+  r.w[2] = (unsigned)max((int)r.w[2] - (int)bytes, 0);
+}
 PFN_DEV void dma16(const DmaRsrc& r, LdsPtr lds_dst_uniform, int byte_offset) {
   unsigned keep;
   const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)lds_dst_uniform);

@@ -157,10 +157,12 @@ struct GemmTNGroup {
   TnProblem p[TN_GROUP_MAX];
   int tile_start[TN_GROUP_MAX + 1];  // filled by the launcher
   int n, M, splits, m_chunk;
-  int debug_mask;                    // all ones; profiling only (pfn_set_tuning key 1): 2^k - 1 wraps the token index
+  int debug_mask;                    // filled by the launcher: all ones.  Profiling only (pfn_set_tuning key 1 = wrap rows): a wrap that is a power of two >= the 64-token
+                                     // stage gives wrap - 1, and the STAGE row inside a token split wraps there (the operand bases return to the split's first row: cache-resident
+                                     // operands, wrong products); any other value leaves the wrap off
   const float* scale_amax;           // fp16 backward: every C and colsum of the group receives its product times 2^-k (nullptr = 1)
 };
-void set_gemm_tn_debug_wrap(int rows);
+void set_gemm_tn_debug_wrap(int rows);         // PFN_TUNE_GEMM_TN_WRAP (see GemmTNGroup::debug_mask): powers of two >= 64 only, everything else = off
 void set_gemm_tn_group_waves(int waves);       // PFN_TUNE_WGRAD_WAVES: 8 = gemm_tn_big_kernel (eight waves of 128 x 64), 4 = gemm_tn_wide_kernel (four of 128 x 128)
 void set_gemm_tn_group_splits(int splits);      // PFN_TUNE_WGRAD_SPLITS: token-axis splits of the grouped weight-gradient launch when the caller leaves them automatic (0 = the occupancy rule)
 // GEMM + bias + residual + LayerNorm in one kernel (gemm_nt_ln_kernel): one workgroup owns 128 full rows of the

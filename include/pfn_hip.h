@@ -482,6 +482,27 @@ int pfn_nuts_advance(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int m
                      const float* value, const float* grad, const int32_t* info, const float* scale, const float* shift, float* trial,
                      float* samples, float* stats, float* warm, int32_t* done_count, void* stream);
 
+/* ---- BNN posterior target (ABI 10, additive; csrc/bnn_mcmc.hip): the potential of the two-layer Bayesian neural network of the reference's BNN study
+ * (mcmc_svi_transformer_on_bayesian.py:28-67, `BayesianModel`) and its gradient for C = P K chains in one launch -- the `fun` of pfn_nuts_advance's caller --
+ * and the chains' class-1 probabilities at test points.  Model: h = W1 x + b1, a = act(h), o = W2 a + b2; activation 0 = identity (the reference's
+ * nn.Sequential(fc1, fc2) has no non-linearity), 1 = tanh; every weight and bias ~ N(0, 1); y_i ~ Categorical(softmax(o_i)).  A chain's parameters are
+ * theta = (W1 [H,F] row-major, b1 [H], W2 [2,H], b2 [2]), D = H (F + 3) + 2 numbers in a row of stride ld >= D; chain c belongs to problem c / K.
+ * pfn_bnn_logp_grad: x [P,S,F], y [P,S] f32 (class = y > 0.5); problem p uses its first n = clamp(n_of[p], 0, S) rows (n_of [P] int32 on the device; NULL:
+ *   all S; n = 0 gives the prior), rows >= n are never read.  value [C] = |theta|^2 / 2 + (D / 2) log 2 pi - sum_{i<n} log softmax(o_i)[y_i], the potential
+ *   itself (pfn_nuts_advance takes it with scale = NULL); grad [C, ld] receives its gradient in the first D columns, columns >= D are never written; grad
+ *   NULL: value only.  The log-softmax is softplus of the signed logit difference: logits of any finite size give finite values.  A non-finite theta gives a
+ *   non-finite value (a divergent leaf for pfn_nuts_advance).
+ * pfn_bnn_predict: x_test [P,m,F], theta [C, ld] -> prob1 [C, m] = softmax(o)[1].  m = 0 returns at once.
+ * Both: caller-owned buffers, stream-ordered, no allocation, no device synchronisation, no atomics; the result for chain c is a deterministic function of
+ * its own problem's data and its own theta, bit for bit -- independent of P, K and of the chain's position in the call.  1 <= F <= 16, 1 <= H <= 64 and
+ * activation in {0, 1}, else PFN_ERR_UNSUPPORTED; P >= 1, K >= 1, S >= 1, m >= 0, ld >= D and non-NULL buffers, else PFN_ERR_ARGUMENT; the shapes are
+ * checked first, before any pointer is looked at and before any HIP call. */
+int pfn_bnn_logp_grad(const float* x, const float* y, const int32_t* n_of, const float* theta, int64_t ld,
+                      int P, int K, int S, int F, int H, int activation,
+                      float* value, float* grad, void* stream);
+int pfn_bnn_predict(const float* x_test, const float* theta, int64_t ld, int P, int K, int m, int F, int H, int activation,
+                    float* prob1, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

@@ -118,6 +118,10 @@ SIGNATURES = {
     'pfn_nuts_init': (_I, [_P, _L, _I, _I, _L, _I, _I, _I, _I, _P, _I, _I, _F, _F, _U64, _P, _P, _P, _P, _P, _P]),
     # (ws, ws_bytes, C, D, ld, max_tree_depth, num_warmup, num_samples, value, grad, info, scale, shift, trial, samples, stats, warm, done_count, stream)
     'pfn_nuts_advance': (_I, [_P, _L, _I, _I, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # BNN posterior target (ABI 10, additive).  (x, y, n_of, theta, ld, P, K, S, F, H, activation, value, grad, stream)
+    'pfn_bnn_logp_grad': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    # (x_test, theta, ld, P, K, m, F, H, activation, prob1, stream)
+    'pfn_bnn_predict': (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

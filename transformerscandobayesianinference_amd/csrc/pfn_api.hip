@@ -1577,6 +1577,34 @@ int pfn_nuts_advance(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int m
   return PFN_OK;
 }
 
+// ---- BNN posterior target (bnn_mcmc.hip; ABI 10, additive) ----
+static int bnn_check(int P, int K, int F, int H, int activation, int64_t ld) {      // shapes first: nothing here touches a pointer or HIP
+  if (F < 1 || F > 16) return fail(PFN_ERR_UNSUPPORTED, "F %d outside 1 .. 16 (a lane keeps its row of W1 in registers)", F);
+  if (H < 1 || H > 64) return fail(PFN_ERR_UNSUPPORTED, "H %d outside 1 .. 64 (lane = hidden unit, one wave per chain at most)", H);
+  if (activation < 0 || activation > 1) return fail(PFN_ERR_UNSUPPORTED, "activation %d (0 identity, 1 tanh)", activation);
+  if (P < 1 || K < 1 || (int64_t)P * K > 0x7fffffff) return fail(PFN_ERR_ARGUMENT, "P %d x K %d chains: need P >= 1, K >= 1, P K < 2^31", P, K);
+  if (ld < (int64_t)H * (F + 3) + 2) return fail(PFN_ERR_ARGUMENT, "ld %lld < D = H (F + 3) + 2 = %d", (long long)ld, H * (F + 3) + 2);
+  return PFN_OK;
+}
+int pfn_bnn_logp_grad(const float* x, const float* y, const int32_t* n_of, const float* theta, int64_t ld, int P, int K, int S, int F, int H, int activation,
+                      float* value, float* grad, void* stream) {
+  if (int rc = bnn_check(P, K, F, H, activation, ld)) return rc;
+  if (S < 1 || !x || !y || !theta || !value) return fail(PFN_ERR_ARGUMENT, "bad bnn_logp_grad arguments (S %d >= 1, x, y, theta, value not NULL)", S);
+  BnnArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.theta = theta; a.ld = ld; a.P = P; a.K = K; a.S = S; a.F = F; a.H = H; a.activation = activation; a.value = value; a.grad = grad;
+  PFN_TRY(launch_bnn_logp_grad(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_bnn_predict(const float* x_test, const float* theta, int64_t ld, int P, int K, int m, int F, int H, int activation, float* prob1, void* stream) {
+  if (int rc = bnn_check(P, K, F, H, activation, ld)) return rc;
+  if (m < 0 || !theta || (m > 0 && (!x_test || !prob1))) return fail(PFN_ERR_ARGUMENT, "bad bnn_predict arguments (m %d >= 0, x_test, theta, prob1 not NULL)", m);
+  if (m == 0) return PFN_OK;
+  BnnArgs a{};
+  a.theta = theta; a.ld = ld; a.P = P; a.K = K; a.F = F; a.H = H; a.activation = activation; a.x_test = x_test; a.m = m; a.prob1 = prob1;
+  PFN_TRY(launch_bnn_predict(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
 int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
                           float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
                           uint64_t seed, uint64_t offset, void* stream) {

@@ -515,6 +515,23 @@ int64_t nuts_workspace_bytes(int C, int D, int depth);
 int launch_nuts_init(const NutsInit& a, hipStream_t s);
 int launch_nuts_advance(const NutsAdvance& a, hipStream_t s);
 
+// ---- BNN posterior target (bnn_mcmc.hip): potential + gradient of every chain in one launch, and the predictive -----
+struct BnnArgs {
+  const float* x;        // [P,S,F]
+  const float* y;        // [P,S]: class = y > 0.5
+  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [0,S]); null = S
+  const float* theta;    // [P*K, ld]: W1 [H,F], b1 [H], W2 [2,H], b2 [2]
+  long ld;
+  int P, K, S, F, H, activation;      // activation: 0 identity, 1 tanh
+  float* value;          // [P*K]
+  float* grad;           // [P*K, ld] or null; columns >= D are never written
+  const float* x_test;   // [P,m,F]   (predict)
+  int m;
+  float* prob1;          // [P*K, m]
+};
+int launch_bnn_logp_grad(const BnnArgs& a, hipStream_t s);
+int launch_bnn_predict(const BnnArgs& a, hipStream_t s);
+
 // ---- BNN prior sampler (mlp_prior.hip) -----------------------------------------------------------
 struct MlpPriorArgs {
   const float* weights;   // [num_models][Lmax][HP][HP]: layer l transposed ([in][out]), zero padded

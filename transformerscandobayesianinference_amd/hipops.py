@@ -304,3 +304,52 @@ def nuts_advance(ws, D, max_tree_depth, value, grad, trial, samples, stats, done
 def nuts_inv_mass(ws, C, D):
     """The chains' current inverse mass [C, D]: a view of the workspace at PFN_NUTS_INV_MASS_OFFSET."""
     return ws[_hip.NUTS_INV_MASS_OFFSET:_hip.NUTS_INV_MASS_OFFSET + 4 * C * D].view(torch.float32).view(C, D)
+
+
+# ---- BNN posterior target (csrc/bnn_mcmc.hip; include/pfn_hip.h "BNN posterior target") ----
+BNN_ACTIVATIONS = {'identity': 0, 'tanh': 1, 0: 0, 1: 1}
+
+
+def bnn_num_params(F, H):
+    """D = H (F + 3) + 2: W1 [H,F], b1 [H], W2 [2,H], b2 [2]."""
+    return int(H) * (int(F) + 3) + 2
+
+
+def bnn_logp_grad(x, y, theta, H, K=None, n_of=None, activation=0, want_grad=True, value=None, grad=None):
+    """Potential and gradient of the two-layer BNN for every chain (pfn_bnn_logp_grad).  x [P,S,F], y [P,S], theta [P K, ld >= D] contiguous f32 on the GPU,
+    n_of [P] int32 or None; chain c belongs to problem c // K (K defaults to theta.shape[0] // P).  Returns (value [P K], grad [P K, ld] or None); only the
+    first D columns of `grad` are written (a fresh one is zero-filled; a caller-owned one keeps its tail)."""
+    _hip.require_gpu_tensor(x, 'x')
+    P, S, F = x.shape
+    C, ld = theta.shape
+    K = C // P if K is None else int(K)
+    assert C == P * K and y.shape == (P, S), 'theta [P K, ld], y [P, S]'
+    for t in (x, y, theta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
+    if n_of is not None:
+        assert n_of.dtype == torch.int32 and n_of.shape == (P,) and n_of.is_contiguous() and n_of.device == x.device
+    value = torch.empty(C, dtype=torch.float32, device=x.device) if value is None else value
+    if want_grad and grad is None:
+        grad = torch.zeros(C, ld, dtype=torch.float32, device=x.device)
+    if not want_grad:
+        grad = None
+    assert value.shape == (C,) and value.dtype == torch.float32 and value.is_contiguous() and value.device == x.device
+    assert grad is None or (grad.shape == (C, ld) and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == x.device)
+    _hip.check(_hip.lib().pfn_bnn_logp_grad(x.data_ptr(), y.data_ptr(), _hip.ptr(n_of), theta.data_ptr(), ld, P, K, S, F, int(H), BNN_ACTIVATIONS[activation],
+                                            value.data_ptr(), _hip.ptr(grad), _hip.stream_ptr(x.device)), 'pfn_bnn_logp_grad')
+    return value, grad
+
+
+def bnn_predict(x_test, theta, H, K=None, activation=0):
+    """Class-1 probability of every chain at x_test [P,m,F] (pfn_bnn_predict): theta [P K, ld] -> prob1 [P K, m]."""
+    _hip.require_gpu_tensor(x_test, 'x_test')
+    P, m, F = x_test.shape
+    C, ld = theta.shape
+    K = C // P if K is None else int(K)
+    assert C == P * K, 'theta [P K, ld]'
+    for t in (x_test, theta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x_test.device
+    prob1 = torch.empty(C, m, dtype=torch.float32, device=x_test.device)
+    _hip.check(_hip.lib().pfn_bnn_predict(x_test.data_ptr(), theta.data_ptr(), ld, P, K, m, F, int(H), BNN_ACTIVATIONS[activation], prob1.data_ptr(),
+                                          _hip.stream_ptr(x_test.device)), 'pfn_bnn_predict')
+    return prob1

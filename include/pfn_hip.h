@@ -503,6 +503,28 @@ int pfn_bnn_logp_grad(const float* x, const float* y, const int32_t* n_of, const
 int pfn_bnn_predict(const float* x_test, const float* theta, int64_t ld, int P, int K, int m, int F, int H, int activation,
                     float* prob1, void* stream);
 
+/* ---- SVI on the BNN (ABI 10, additive; csrc/bnn_svi.hip): the mean-field Gaussian guide of the reference's `eval_svi` (mcmc_svi_transformer_on_bayesian.py:211-246:
+ * pyro's AutoDiagonalNormal + Trace_ELBO(num_particles) + Adam) for P problems, num_steps steps in ONE launch, one block per problem.
+ * Guide: q(theta) = N(loc, diag(scale^2)), scale = softplus(u); theta_k = loc + scale eps_k for particles k < K = num_particles.  Per step
+ *   L = mean_k [ U(theta_k) - sum_i (log scale_i + eps_ki^2 / 2) - (D / 2) log 2 pi ]      (what pyro's svi.step returns; U: the potential of pfn_bnn_logp_grad,
+ *   prior included, same theta layout, activation and n_of), g_loc = mean_k grad U(theta_k), g_scale = mean_k grad U(theta_k) * eps_k - 1 / scale,
+ *   g_u = g_scale sigmoid(u), then torch.optim.Adam without weight decay on loc and u: m <- beta1 m + (1 - beta1) g, v <- beta2 v + (1 - beta2) g^2,
+ *   p <- p - lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps), t = absolute step index + 1 (beta^t in f64).
+ * state [P, 6, ld] f32, ld >= D, caller-owned: rows loc, u, m_loc, v_loc, m_u, v_u; columns >= D are never read or written.  The launch runs steps
+ *   step0 .. step0 + num_steps - 1; loss [P, num_steps] (or NULL) receives L of every step, evaluated before the step's update.
+ * Noise: eps of (problem id q, absolute step t, particle k, coordinate i) is component i & 3 of normal4(philox4x32_10(idx = ((t K + k) << 10) | (i >> 2),
+ *   stream = q, key = seed)) (Box-Muller on the block's four words); q = problem_ids[p] (int64 [P] on the device), or p when NULL.  It depends on
+ *   (seed, q, t, k, i) alone -- not on P, on the block shape or on how the steps are split over launches.
+ * A problem's result is a bitwise function of its own rows, state, q, seed and (H, F, K): the same alone and in a batch, and steps(0, a + b) equals
+ *   steps(0, a) followed by steps(a, b).  Rows >= n of x / y are never read.  A problem whose state is or becomes non-finite stays alone in that.
+ * Stream-ordered, no allocation, no host synchronisation, no atomics.  1 <= F <= 16, 1 <= H <= 64, activation in {0, 1}, else PFN_ERR_UNSUPPORTED;
+ *   P >= 1, S >= 1, num_particles >= 1, 0 <= step0 <= 2^40, num_steps >= 0, (step0 + num_steps + 1) num_particles < 2^53, ld >= D, lr >= 0, beta1 / beta2 in [0, 1),
+ *   eps >= 0 and non-NULL x, y, state, else PFN_ERR_ARGUMENT; the shapes are checked first, before any pointer is looked at and before any HIP call.
+ *   num_steps = 0 returns at once. */
+int pfn_bnn_svi_steps(const float* x, const float* y, const int32_t* n_of, float* state, int64_t ld, int P, int S, int F, int H, int activation,
+                      int num_particles, int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, uint64_t seed,
+                      const int64_t* problem_ids, float* loss, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

@@ -122,6 +122,8 @@ SIGNATURES = {
     'pfn_bnn_logp_grad': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     # (x_test, theta, ld, P, K, m, F, H, activation, prob1, stream)
     'pfn_bnn_predict': (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
+    # SVI on the BNN (ABI 10, additive).  (x, y, n_of, state, ld, P, S, F, H, activation, num_particles, step0, num_steps, lr, beta1, beta2, eps, seed, problem_ids, loss, stream)
+    'pfn_bnn_svi_steps': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _I, _F, _F, _F, _F, _U64, _P, _P, _P]),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

@@ -11,44 +11,12 @@
 // to one problem; the block stages that problem's rows in LDS in chunks of 64 (zero padded to Fp = 4 / 8 / 16 columns) and every lane reads them as broadcasts.
 // Rows >= n are never read.  Padding lanes (j >= H) and the lanes of chains beyond K hold zeros for every parameter: they add exact zeros.
 #include <algorithm>
-#include <type_traits>
-#include "pfn_device.h"
+#include "bnn_device.h"
 #include "pfn_kernels.h"
 
 namespace pfn {
 
 namespace {
-
-constexpr int BNN_CHUNK = 64;      // rows of x / y staged per pass
-constexpr int BNN_ROWS = 4;        // rows in flight (independent butterflies)
-constexpr int BNN_MAX_WAVES = 4;
-constexpr float HALF_LOG_2PI = 0.91893853320467274178f;
-
-template <int FP> struct BnnLane {
-  float w1[FP];      // W1[j, :], zero beyond F
-  float b1, w2d;     // b1[j], W2[1,j] - W2[0,j]
-};
-
-template <int HP> PFN_DEV float bnn_group_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < HP; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the forward device function of both entries: a_j = act(b1[j] + W1[j,:] . x) for the row at `xr` (LDS, Fp floats, 16-byte aligned)
-template <int FP, int ACT> PFN_DEV float bnn_hidden(const BnnLane<FP>& L, const float* xr) {
-  float h = L.b1;
-#pragma unroll
-  for (int q = 0; q < FP / 4; ++q) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(xr + 4 * q);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) h = __builtin_fmaf(L.w1[4 * q + e], v[e], h);
-  }
-  return ACT ? tanhf(h) : h;
-}
-
-// sigmoid(z) from e = exp(-|z|): no overflow, no cancellation on either side
-PFN_DEV float bnn_sigmoid(float z, float e) { return (z >= 0.f ? 1.f : e) / (1.f + e); }
 
 struct BnnChain {
   int p, k, j;
@@ -72,14 +40,6 @@ template <int HP> PFN_DEV BnnChain bnn_chain(int K, int H) {
   return ch;
 }
 
-// rows [r0, r0 + rows) of src[p] ([*, F] row-major) into xs [BNN_CHUNK, FP], zero padded in both directions; nothing beyond the last row is read
-template <int FP> PFN_DEV void bnn_stage(float* xs, const float* src_p, int r0, int rows, int F) {
-  for (int idx = threadIdx.x; idx < BNN_CHUNK * FP; idx += blockDim.x) {
-    const int r = idx / FP, f = idx % FP;
-    xs[idx] = (r < rows && f < F) ? src_p[(long)(r0 + r) * F + f] : 0.f;
-  }
-}
-
 template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MAX_WAVES) bnn_logp_grad_kernel(BnnArgs a) {
   __shared__ __attribute__((aligned(16))) float xs[BNN_CHUNK * FP];
   __shared__ float ys[BNN_CHUNK];
@@ -99,45 +59,8 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
   int n = a.S;
   if (a.n_of) n = min(max(a.n_of[ch.p], 0), a.S);
 
-  float dw1[FP], db1 = 0.f, A = 0.f, G = 0.f, U = 0.f;      // A = sum_i g_i a_j, G = sum_i g_i, U = sum_i softplus
-#pragma unroll
-  for (int f = 0; f < FP; ++f) dw1[f] = 0.f;
-
-  auto step = [&](int r, auto rr) {
-    constexpr int RR = decltype(rr)::value;
-    float av[RR], pv[RR];
-#pragma unroll
-    for (int q = 0; q < RR; ++q) {
-      av[q] = bnn_hidden<FP, ACT>(L, xs + (r + q) * FP);
-      pv[q] = L.w2d * av[q];
-    }
-#pragma unroll
-    for (int o = 1; o < HP; o <<= 1) {
-#pragma unroll
-      for (int q = 0; q < RR; ++q) pv[q] += __shfl_xor(pv[q], o, 64);
-    }
-#pragma unroll
-    for (int q = 0; q < RR; ++q) {
-      const float d = pv[q] + b2d;      // o_1 - o_0
-      const bool y1 = ys[r + q] > 0.5f;
-      const float z = y1 ? -d : d;      // -log softmax(o)[y] = softplus(z)
-      const float e = expf(-fabsf(z));
-      U += fmaxf(z, 0.f) + log1pf(e);
-      const float s = bnn_sigmoid(z, e);
-      const float g = y1 ? -s : s;      // d softplus(z) / d d
-      G += g;
-      A = __builtin_fmaf(g, av[q], A);
-      const float dh = g * L.w2d * (ACT ? 1.f - av[q] * av[q] : 1.f);
-      db1 += dh;
-      const float* xr = xs + (r + q) * FP;
-#pragma unroll
-      for (int f4 = 0; f4 < FP / 4; ++f4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(xr + 4 * f4);
-#pragma unroll
-        for (int e4 = 0; e4 < 4; ++e4) dw1[4 * f4 + e4] = __builtin_fmaf(dh, v[e4], dw1[4 * f4 + e4]);
-      }
-    }
-  };
+  BnnSums<FP> sm;      // dW1[j,:], db1[j], A = sum_i g_i a_j, G = sum_i g_i, U = sum_i softplus
+  sm.clear();
 
   for (int r0 = 0; r0 < n; r0 += BNN_CHUNK) {
     const int rows = min(BNN_CHUNK, n - r0);
@@ -145,11 +68,7 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
     bnn_stage<FP>(xs, a.x + (long)ch.p * a.S * F, r0, rows, F);
     if (threadIdx.x < BNN_CHUNK) ys[threadIdx.x] = ((int)threadIdx.x < rows && a.y[(long)ch.p * a.S + r0 + threadIdx.x] > 0.5f) ? 1.f : 0.f;
     __syncthreads();
-    if (ch.wave_on) {      // wave-uniform: the butterflies run with all 64 lanes
-      int r = 0;
-      for (; r + BNN_ROWS <= rows; r += BNN_ROWS) step(r, std::integral_constant<int, BNN_ROWS>());
-      for (; r < rows; ++r) step(r, std::integral_constant<int, 1>());
-    }
+    if (ch.wave_on) bnn_rows<HP, FP, ACT>(L, b2d, xs, ys, rows, sm);      // wave-uniform: the butterflies run with all 64 lanes
   }
   if (!ch.wave_on) return;
   float q = L.b1 * L.b1 + w20 * w20 + w21 * w21;
@@ -158,18 +77,18 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
   q = bnn_group_sum<HP>(q) + b20 * b20 + b21 * b21;
   if (!ch.on) return;
   const int D = H * (F + 3) + 2;
-  if (j == 0) a.value[ch.c] = 0.5f * q + (float)D * HALF_LOG_2PI + U;
+  if (j == 0) a.value[ch.c] = 0.5f * q + (float)D * HALF_LOG_2PI + sm.U;
   if (!a.grad) return;
   float* gr = a.grad + ch.c * a.ld;
 #pragma unroll
   for (int f = 0; f < FP; ++f)
-    if (f < F) gr[j * F + f] = dw1[f] + L.w1[f];
-  gr[oB1 + j] = db1 + L.b1;
-  gr[oW2 + j] = w20 - A;
-  gr[oW2 + H + j] = w21 + A;
+    if (f < F) gr[j * F + f] = sm.dw1[f] + L.w1[f];
+  gr[oB1 + j] = sm.db1 + L.b1;
+  gr[oW2 + j] = w20 - sm.A;
+  gr[oW2 + H + j] = w21 + sm.A;
   if (j == 0) {
-    gr[oB2] = b20 - G;
-    gr[oB2 + 1] = b21 + G;
+    gr[oB2] = b20 - sm.G;
+    gr[oB2 + 1] = b21 + sm.G;
   }
 }
 

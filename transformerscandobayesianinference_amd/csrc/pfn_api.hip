@@ -1605,6 +1605,25 @@ int pfn_bnn_predict(const float* x_test, const float* theta, int64_t ld, int P, 
   return PFN_OK;
 }
 
+// ---- SVI on the BNN (bnn_svi.hip; ABI 10, additive) ----
+int pfn_bnn_svi_steps(const float* x, const float* y, const int32_t* n_of, float* state, int64_t ld, int P, int S, int F, int H, int activation, int num_particles,
+                      int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, uint64_t seed, const int64_t* problem_ids, float* loss, void* stream) {
+  if (int rc = bnn_check(P, 1, F, H, activation, ld)) return rc;      // F, H, activation, P >= 1 and ld >= D: nothing here touches a pointer or HIP
+  if (num_particles < 1 || step0 < 0 || num_steps < 0 || S < 1 || !x || !y || !state)
+    return fail(PFN_ERR_ARGUMENT, "bad bnn_svi_steps arguments (num_particles %d >= 1, step0 %lld >= 0, num_steps %d >= 0, S %d >= 1, x, y, state not NULL)", num_particles,
+                (long long)step0, num_steps, S);
+  if (step0 > (int64_t)1 << 40 || (step0 + num_steps + 1) * (int64_t)num_particles >= (int64_t)1 << 53)
+    return fail(PFN_ERR_ARGUMENT, "step0 %lld must not exceed 2^40 and (step0 + num_steps + 1) num_particles must stay below 2^53 (the Philox counter of a particle's noise)", (long long)step0);
+  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
+    return fail(PFN_ERR_ARGUMENT, "bad bnn_svi_steps arguments (lr %g >= 0, beta1 %g and beta2 %g in [0, 1), eps %g >= 0)", lr, beta1, beta2, eps);
+  if (num_steps == 0) return PFN_OK;
+  BnnSviArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.state = state; a.ld = ld; a.P = P; a.S = S; a.F = F; a.H = H; a.activation = activation; a.K = num_particles; a.step0 = step0;
+  a.num_steps = num_steps; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.seed = seed; a.problem_ids = problem_ids; a.loss = loss;
+  PFN_TRY(launch_bnn_svi_steps(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
 int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
                           float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
                           uint64_t seed, uint64_t offset, void* stream) {

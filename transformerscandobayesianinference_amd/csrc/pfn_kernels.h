@@ -532,6 +532,23 @@ struct BnnArgs {
 int launch_bnn_logp_grad(const BnnArgs& a, hipStream_t s);
 int launch_bnn_predict(const BnnArgs& a, hipStream_t s);
 
+// ---- SVI on the BNN (bnn_svi.hip): num_steps steps of (noise -> ELBO gradient -> Adam) for every problem in one launch -----
+struct BnnSviArgs {
+  const float* x;        // [P,S,F]
+  const float* y;        // [P,S]: class = y > 0.5
+  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [0,S]); null = S
+  float* state;          // [P,6,ld]: loc, u (scale = softplus(u)), m_loc, v_loc, m_u, v_u; columns >= D are never touched
+  long ld;
+  int P, S, F, H, activation, K;      // K particles per step
+  long step0;
+  int num_steps;
+  float lr, beta1, beta2, eps;
+  unsigned long long seed;
+  const int64_t* problem_ids;   // [P] or null (the problem's index): the Philox stream
+  float* loss;           // [P,num_steps] or null
+};
+int launch_bnn_svi_steps(const BnnSviArgs& a, hipStream_t s);
+
 // ---- BNN prior sampler (mlp_prior.hip) -----------------------------------------------------------
 struct MlpPriorArgs {
   const float* weights;   // [num_models][Lmax][HP][HP]: layer l transposed ([in][out]), zero padded

@@ -1,6 +1,7 @@
 """Tensor-level wrappers around the single-op C-ABI entry points (`pfn_op_*`, include/pfn_hip.h): one kernel launch per call on the
 current stream.  Used by the per-kernel parity tests (tests/test_gpu_ops.py), by bench.py's kernel table and by tools/."""
 import ctypes
+import math
 
 import torch
 
@@ -353,3 +354,46 @@ def bnn_predict(x_test, theta, H, K=None, activation=0):
     _hip.check(_hip.lib().pfn_bnn_predict(x_test.data_ptr(), theta.data_ptr(), ld, P, K, m, F, int(H), BNN_ACTIVATIONS[activation], prob1.data_ptr(),
                                           _hip.stream_ptr(x_test.device)), 'pfn_bnn_predict')
     return prob1
+
+
+# ---- SVI on the BNN (csrc/bnn_svi.hip; include/pfn_hip.h "SVI on the BNN") ----
+SVI_ROWS = ('loc', 'u', 'm_loc', 'v_loc', 'm_u', 'v_u')      # the rows of a guide's state
+
+
+def bnn_svi_state(P, F, H, device, loc0=None, init_scale=0.1):
+    """The state of P mean-field Gaussian guides at step 0: [P, 6, D] f32 with loc = loc0 ([P, D] or None: zeros), u = softplus^-1(init_scale) (the guide's
+    scale is softplus(u)) and zero Adam moments."""
+    D = bnn_num_params(F, H)
+    assert init_scale > 0
+    state = torch.zeros(int(P), 6, D, dtype=torch.float32, device=device)
+    if loc0 is not None:
+        assert tuple(loc0.shape) == (int(P), D), 'loc0 [P, D]'
+        state[:, 0] = loc0.to(device=device, dtype=torch.float32)
+    state[:, 1] = math.log(math.expm1(float(init_scale)))
+    return state
+
+
+def bnn_svi_steps(x, y, state, H, num_steps, step0=0, num_particles=1, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, n_of=None, activation=0, problem_ids=None,
+                  loss=None):
+    """`num_steps` steps of SVI (noise -> ELBO gradient -> Adam) on the guides of P problems in one launch (pfn_bnn_svi_steps).  x [P,S,F], y [P,S],
+    state [P, 6, ld >= D] contiguous f32 on the GPU (updated in place; bnn_svi_state), n_of [P] int32 or None, problem_ids [P] int64 or None (the noise
+    stream of problem p: its index).  The launch covers the absolute steps step0 .. step0 + num_steps - 1.  Returns loss [P, num_steps] (a fresh tensor
+    unless given): the ELBO loss of every step before its update."""
+    _hip.require_gpu_tensor(x, 'x')
+    P, S, F = x.shape
+    num_steps, step0, K = int(num_steps), int(step0), int(num_particles)
+    assert state.dim() == 3 and state.shape[:2] == (P, 6) and y.shape == (P, S), 'state [P, 6, ld], y [P, S]'
+    ld = state.shape[2]
+    for t in (x, y, state):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
+    if n_of is not None:
+        assert n_of.dtype == torch.int32 and n_of.shape == (P,) and n_of.is_contiguous() and n_of.device == x.device
+    if problem_ids is not None:
+        assert problem_ids.dtype == torch.int64 and problem_ids.shape == (P,) and problem_ids.is_contiguous() and problem_ids.device == x.device
+    if loss is None:
+        loss = torch.empty(P, max(num_steps, 0), dtype=torch.float32, device=x.device)
+    assert loss.shape == (P, num_steps) and loss.dtype == torch.float32 and loss.is_contiguous() and loss.device == x.device
+    _hip.check(_hip.lib().pfn_bnn_svi_steps(x.data_ptr(), y.data_ptr(), _hip.ptr(n_of), state.data_ptr(), ld, P, S, F, int(H), BNN_ACTIVATIONS[activation], K, step0,
+                                            num_steps, float(lr), float(betas[0]), float(betas[1]), float(eps), int(seed), _hip.ptr(problem_ids), loss.data_ptr(),
+                                            _hip.stream_ptr(x.device)), 'pfn_bnn_svi_steps')
+    return loss

@@ -1,11 +1,16 @@
-"""The BNN study of the reference (mcmc_svi_transformer_on_bayesian.py): a PFN trained on a Bayesian-neural-network prior against NUTS on the same BNN.
+"""The BNN study of the reference (mcmc_svi_transformer_on_bayesian.py): a PFN trained on a Bayesian-neural-network prior against NUTS and against stochastic
+variational inference on the same BNN.
 
 The reference builds the BNN as a PyroModule and runs pyro's NUTS on one dataset and one chain at a time (`eval_mcmc`, :249-267).  Here the model is a plain
 class, its potential and gradient are ONE HIP launch for every chain of every dataset (`hipops.bnn_logp_grad`, csrc/bnn_mcmc.hip) and the sampler is
-`mcmc.batched_nuts`, which advances all of them in the same pass; the posterior predictive is a second kernel (`hipops.bnn_predict`).  Nothing depends on pyro.
-DESIGN.md section 16 has the kernel; INTEGRATION.md lists what differs from the reference.
+`mcmc.batched_nuts`, which advances all of them in the same pass; the posterior predictive is a second kernel (`hipops.bnn_predict`).
 
-Not built: SVI and SVGD (`eval_svi`, :211-246) -- they need a reparameterised-ELBO step kernel of their own -- and the plotting helpers."""
+The reference's SVI arm (`eval_svi`, :211-246) fits pyro's AutoDiagonalNormal guide with Trace_ELBO and Adam, one dataset and one Python iteration per step.
+Here the whole step loop of every dataset is one persistent launch (`hipops.bnn_svi_steps`, csrc/bnn_svi.hip, one block per dataset): `fit_bnn_svi` returns
+a `BnnGuide`, `eval_svi` scores it through the same predictive kernel.  A guide has no limit on D, so SVI also runs the 'big' spec that NUTS refuses.
+Nothing depends on pyro.  DESIGN.md sections 16 and 17 have the kernels; INTEGRATION.md lists what differs from the reference.
+
+Not built: SVGD (`eval_svi(svgd=True)`) -- it needs a Stein-kernel particle step beside the ELBO kernel -- and the plotting helpers."""
 import math
 import os
 import time
@@ -216,6 +221,18 @@ def _spec_of(model_spec):
     return model_spec, 'identity'
 
 
+def _score(prob1, y_test, sample_obs, seed):
+    """(nll [P], acc [P]) of the draws' class-1 probabilities prob1 [P, N, m] against y_test [P, m]: the mean probability, or the reference's estimator."""
+    if sample_obs:
+        obs = torch.bernoulli(prob1, generator=torch.Generator(device=prob1.device).manual_seed(int(seed)))
+        acc, nll = zip(*[evaluate_preds({'obs': obs[p]}, y_test[p])[:2] for p in range(prob1.shape[0])])
+        return torch.stack(nll).cpu().numpy(), torch.stack(acc).cpu().numpy()
+    mean = prob1.mean(1)
+    acc = ((mean > 0.5) == (y_test > 0.5)).float().mean(1)
+    nll = nn.BCELoss(reduction='none')(mean, (y_test > 0.5).float()).mean(1)
+    return nll.cpu().numpy(), acc.cpu().numpy()
+
+
 def eval_mcmc(X, y, device, model_spec, training_samples_n, warmup_steps, num_pred_samples, sample_obs=False, seed=0):
     """NUTS on the BNN for every dataset of X [P, T, F], y [P, T] at once, trained on the first `training_samples_n` rows and scored on the rest: returns
     (nll [P], acc [P]) as numpy arrays (reference :249-267, one dataset at a time there).  By default the prediction is the mean class-1 probability over
@@ -226,22 +243,87 @@ def eval_mcmc(X, y, device, model_spec, training_samples_n, warmup_steps, num_pr
     X_train, y_train, X_test, y_test = X[:, :n].contiguous(), y[:, :n].contiguous(), X[:, n:].contiguous(), y[:, n:].contiguous()
     post = sample_bnn_posterior(X_train, y_train, spec, num_samples=num_pred_samples, warmup_steps=warmup_steps, num_chains=1, seed=seed, activation=activation)
     prob1 = post.predictive(X_test)      # [P, N, m]
-    if sample_obs:
-        obs = torch.bernoulli(prob1, generator=torch.Generator(device=prob1.device).manual_seed(int(seed)))
-        acc, nll = zip(*[evaluate_preds({'obs': obs[p]}, y_test[p])[:2] for p in range(X.shape[0])])
-        return torch.stack(nll).cpu().numpy(), torch.stack(acc).cpu().numpy()
-    mean = prob1.mean(1)
-    acc = ((mean > 0.5) == (y_test > 0.5)).float().mean(1)
-    nll = nn.BCELoss(reduction='none')(mean, (y_test > 0.5).float()).mean(1)
-    return nll.cpu().numpy(), acc.cpu().numpy()
+    return _score(prob1, y_test, sample_obs, seed)
+
+
+class BnnGuide:
+    """Mean-field Gaussian guides of P problems (fit_bnn_svi): loc, scale [P, D] in the layout of BayesianModel.pack, losses [P, T] (the ELBO loss of every
+    step, before its update), state [P, 6, D] (hipops.bnn_svi_state: what a further hipops.bnn_svi_steps call continues from)."""
+
+    def __init__(self, state, losses, model_spec, activation):
+        self.state, self.losses, self.model_spec, self.activation = state, losses, dict(model_spec), activation
+        self.loc, self.scale = state[:, 0], torch.nn.functional.softplus(state[:, 1])
+
+    def sample(self, num_samples, seed=0):
+        """theta [P, N, D] ~ N(loc, diag(scale^2)), seeded."""
+        P, D = self.loc.shape
+        z = torch.randn(P, int(num_samples), D, generator=torch.Generator(device=self.loc.device).manual_seed(int(seed)), device=self.loc.device)
+        return self.loc[:, None, :] + self.scale[:, None, :] * z
+
+    def predictive(self, x_test, num_samples, seed=0):
+        """Class-1 probability of `num_samples` draws from the guide at x_test [P, m, F]: prob1 [P, N, m] (pfn_bnn_predict)."""
+        P, D = self.loc.shape
+        N = int(num_samples)
+        x_test = x_test.to(self.loc.device).float().contiguous()
+        assert x_test.shape[0] == P and x_test.shape[2] == self.model_spec['num_features']
+        theta = self.sample(N, seed).reshape(P * N, D).contiguous()
+        return hipops.bnn_predict(x_test, theta, self.model_spec['embed'], K=N, activation=self.activation).view(P, N, x_test.shape[1])
+
+
+def fit_bnn_svi(x, y, model_spec, n_of=None, num_steps=1024, lr=1e-3, num_particles=1, seed=0, activation='identity', init_scale=0.1, steps_per_launch=256):
+    """SVI on the weights of the BNN given x [P, S, F], y [P, S] (class = y > 0.5; problem p uses its first n_of[p] rows, all when None): a mean-field
+    Gaussian guide per problem, `num_steps` Adam steps on the `num_particles`-particle ELBO, every problem in the same launches (hipops.bnn_svi_steps).
+    The initial loc is the median of 15 N(0, 1) draws per coordinate from `seed` (pyro's init_to_median for this prior), the initial scale `init_scale`.
+    `steps_per_launch` only bounds the length of one launch: the result does not depend on it, bit for bit.  Returns a BnnGuide."""
+    activation = _activation_name(activation)
+    F, H = int(model_spec['num_features']), int(model_spec['embed'])
+    D = hipops.bnn_num_params(F, H)
+    hipops._hip.require_gpu_tensor(x, 'x')
+    x, y = x.float().contiguous(), y.to(x.device).float().contiguous()
+    P, S, _ = x.shape
+    assert x.shape[2] == F and y.shape == (P, S)
+    num_steps, per = int(num_steps), max(int(steps_per_launch), 1)
+    if n_of is not None:
+        n_of = torch.as_tensor(n_of, dtype=torch.int32, device=x.device).contiguous()
+    loc0 = torch.randn(15, P, D, generator=torch.Generator(device=x.device).manual_seed(int(seed)), device=x.device).median(0).values
+    state = hipops.bnn_svi_state(P, F, H, x.device, loc0=loc0, init_scale=init_scale)
+    losses = torch.empty(P, num_steps, device=x.device)
+    for step0 in range(0, num_steps, per):
+        n = min(per, num_steps - step0)
+        losses[:, step0:step0 + n] = hipops.bnn_svi_steps(x, y, state, H, n, step0=step0, num_particles=num_particles, lr=lr, seed=seed, n_of=n_of, activation=activation)
+    return BnnGuide(state, losses, model_spec, activation)
+
+
+def _require_gpu(device, what):
+    if torch.device(device).type != 'cuda':
+        raise NotImplementedError(f'{what}: the ELBO step kernel (pfn_bnn_svi_steps) runs on the GPU only and there is no CPU fallback; got device {device!r}')
+
+
+def eval_svi(X, y, device, model_sampler, training_samples_n, num_train_steps, num_pred_samples, lr=1e-3, num_particles=1, svgd=False, sample_obs=False, seed=0):
+    """SVI on the BNN for every dataset of X [P, T, F], y [P, T] at once, trained on the first `training_samples_n` rows and scored on the rest with
+    `num_pred_samples` draws from the guide: returns (nll [P], acc [P]) as numpy arrays (reference :211-246, one dataset and one step at a time there).
+    `model_sampler`: a spec dict or the reference's callable.  The estimators are eval_mcmc's: the mean class-1 probability by default, sample_obs=True for
+    the reference's sampled observations."""
+    if svgd:
+        raise NotImplementedError('svgd=True: SVGD is not built here -- it needs a Stein-kernel particle step beside the ELBO kernel; svgd=False (SVI) is available')
+    _require_gpu(device, 'eval_svi')
+    spec, activation = _spec_of(model_sampler)
+    X, y = X.to(device).float(), y.to(device).float()
+    n = int(training_samples_n)
+    X_train, y_train, X_test, y_test = X[:, :n].contiguous(), y[:, :n].contiguous(), X[:, n:].contiguous(), y[:, n:].contiguous()
+    guide = fit_bnn_svi(X_train, y_train, spec, num_steps=num_train_steps, lr=lr, num_particles=num_particles, seed=seed, activation=activation)
+    prob1 = guide.predictive(X_test, num_pred_samples, seed=seed)      # [P, N, m]
+    return _score(prob1, y_test, sample_obs, seed)
 
 
 def _eval(method, X, y, device, model_spec, training_samples_n, steps):
     if method == 'mcmc':
         return eval_mcmc(X, y, device, model_spec, training_samples_n, warmup_steps=steps, num_pred_samples=steps)
-    if method in ('svi', 'svgd'):
-        raise NotImplementedError(f"method {method!r}: SVI and SVGD are not built here -- they need a reparameterised-ELBO step kernel of their own; only 'mcmc' "
-                                  f'(NUTS through mcmc.batched_nuts) is available')
+    if method == 'svi':
+        return eval_svi(X, y, device, model_spec, training_samples_n, num_train_steps=steps, num_pred_samples=steps)
+    if method == 'svgd':
+        raise NotImplementedError("method 'svgd': SVGD is not built here -- it needs a Stein-kernel particle step beside the ELBO kernel; 'mcmc' (NUTS through "
+                                  "mcmc.batched_nuts) and 'svi' (pfn_bnn_svi_steps) are available")
     raise ValueError(f'unknown method {method!r}')
 
 

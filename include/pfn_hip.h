@@ -525,6 +525,34 @@ int pfn_bnn_svi_steps(const float* x, const float* y, const int32_t* n_of, float
                       int num_particles, int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, uint64_t seed,
                       const int64_t* problem_ids, float* loss, void* stream);
 
+/* ---- SVGD on the BNN (ABI 10, additive; csrc/bnn_svgd.hip): Stein variational gradient descent, the reference's `eval_svi(..., svgd=True)`
+ * (mcmc_svi_transformer_on_bayesian.py:211-246: pyro's SVGD(model, RBFSteinKernel(), adam, num_particles)) for P problems, num_steps steps in ONE launch, one
+ * block per problem.  N = num_particles points x_n in R^D per problem; U is the potential of pfn_bnn_logp_grad (prior included, same theta layout,
+ * activation and n_of).  One step:
+ *   g_n = grad U(x_n);
+ *   h_d = bandwidth_factor * median_{i<j} (x_id - x_jd)^2 / log(N + 1) per coordinate d (RBFSteinKernel, "univariate"): torch.median's median of the
+ *     N (N - 1) / 2 pairs, the lower of the two middle values when their count is even -- exactly one of the pairwise values, the f32 square of the selected
+ *     k-th smallest f32 |x_id - x_jd|; h is a constant of the step; h_d = 0 (coincident particles) makes that problem non-finite, as the formula does;
+ *   k_d(n,m) = exp(-(x_nd - x_md)^2 / h_d),  s_nd = (1/N) sum_m [ k_d(n,m) g_md + k_d(n,m) 2 (x_md - x_nd) / h_d ]  (summed over m in index order);
+ *   torch.optim.Adam without weight decay on every x_nd with gradient s_nd: m <- beta1 m + (1 - beta1) s, v <- beta2 v + (1 - beta2) s^2,
+ *     x <- x - lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps), t = absolute step index + 1 (beta^t in f64).  No randomness inside a step.
+ * state [P, 3, N, ld] f32, ld >= D, caller-owned: N rows of particles, N rows of m, N rows of v per problem; updated in place; columns >= D are never read
+ *   or written.  The launch runs steps step0 .. step0 + num_steps - 1.  potential [P, num_steps] (or NULL): the mean over particles of U(x_n) before the
+ *   step's update.  bandwidth [P, ld] (or NULL): h of the last step run, first D columns.
+ * workspace: pfn_bnn_svgd_workspace_bytes(P, num_particles, F, H) bytes (negative on bad arguments; 0 when particles, gradients and moments stay in LDS
+ *   for the whole launch, and workspace may then be NULL); otherwise it carries the particles' gradients between the phases of a step.
+ * A problem's result is a bitwise function of its own rows, its own state and (H, F, N): the same alone and in a batch, and steps(0, a + b) equals
+ *   steps(0, a) followed by steps(a, b).  Rows >= n of x / y are never read.  A problem whose state is or becomes non-finite stays alone in that.
+ * Stream-ordered, no allocation, no host synchronisation, no atomics.  1 <= F <= 16, 1 <= H <= 64, activation in {0, 1} and
+ *   2 <= num_particles <= PFN_BNN_SVGD_MAX_PARTICLES, else PFN_ERR_UNSUPPORTED; P >= 1, S >= 1, step0 >= 0, num_steps >= 0, ld >= D, lr >= 0 and finite,
+ *   beta1 / beta2 in [0, 1), eps >= 0, bandwidth_factor > 0, non-NULL x, y, state and a workspace of at least the stated bytes, else PFN_ERR_ARGUMENT; the
+ *   limits are checked first, before any pointer is looked at and before any HIP call.  num_steps = 0 returns at once. */
+#define PFN_BNN_SVGD_MAX_PARTICLES 64
+int64_t pfn_bnn_svgd_workspace_bytes(int P, int num_particles, int F, int H);
+int pfn_bnn_svgd_steps(const float* x, const float* y, const int32_t* n_of, float* state, int64_t ld, int P, int S, int F, int H, int activation,
+                       int num_particles, int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, float bandwidth_factor,
+                       void* workspace, int64_t workspace_bytes, float* potential, float* bandwidth, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

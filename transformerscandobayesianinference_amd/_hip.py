@@ -124,6 +124,11 @@ SIGNATURES = {
     'pfn_bnn_predict': (_I, [_P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
     # SVI on the BNN (ABI 10, additive).  (x, y, n_of, state, ld, P, S, F, H, activation, num_particles, step0, num_steps, lr, beta1, beta2, eps, seed, problem_ids, loss, stream)
     'pfn_bnn_svi_steps': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _I, _F, _F, _F, _F, _U64, _P, _P, _P]),
+    # SVGD on the BNN (ABI 10, additive).  (P, num_particles, F, H)
+    'pfn_bnn_svgd_workspace_bytes': (_L, [_I, _I, _I, _I]),
+    # (x, y, n_of, state, ld, P, S, F, H, activation, num_particles, step0, num_steps, lr, beta1, beta2, eps, bandwidth_factor, workspace, workspace_bytes, potential,
+    #  bandwidth, stream)
+    'pfn_bnn_svgd_steps': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _I, _F, _F, _F, _F, _F, _P, _L, _P, _P, _P]),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

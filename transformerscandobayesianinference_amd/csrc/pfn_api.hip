@@ -1624,6 +1624,41 @@ int pfn_bnn_svi_steps(const float* x, const float* y, const int32_t* n_of, float
   return PFN_OK;
 }
 
+// ---- SVGD on the BNN (bnn_svgd.hip; ABI 10, additive) ----
+static int bnn_svgd_limits(int F, int H, int activation, int N) {      // what the kernel is built for: nothing here touches a pointer or HIP
+  if (int rc = bnn_check(1, 1, F, H, activation, (int64_t)1 << 40)) return rc;
+  if (N < 2 || N > PFN_BNN_SVGD_MAX_PARTICLES)
+    return fail(PFN_ERR_UNSUPPORTED, "num_particles %d outside 2 .. %d (lane = particle in the Stein step; the median needs a pair)", N, PFN_BNN_SVGD_MAX_PARTICLES);
+  return PFN_OK;
+}
+int64_t pfn_bnn_svgd_workspace_bytes(int P, int num_particles, int F, int H) {
+  if (P < 1 || bnn_svgd_limits(F, H, 0, num_particles)) return -1;
+  return bnn_svgd_workspace_bytes(P, num_particles, H * (F + 3) + 2);
+}
+int pfn_bnn_svgd_steps(const float* x, const float* y, const int32_t* n_of, float* state, int64_t ld, int P, int S, int F, int H, int activation, int num_particles,
+                       int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, float bandwidth_factor, void* workspace,
+                       int64_t workspace_bytes, float* potential, float* bandwidth, void* stream) {
+  if (int rc = bnn_svgd_limits(F, H, activation, num_particles)) return rc;
+  const int D = H * (F + 3) + 2;
+  if (P < 1 || S < 1 || step0 < 0 || num_steps < 0 || !x || !y || !state)
+    return fail(PFN_ERR_ARGUMENT, "bad bnn_svgd_steps arguments (P %d >= 1, S %d >= 1, step0 %lld >= 0, num_steps %d >= 0, x, y, state not NULL)", P, S, (long long)step0,
+                num_steps);
+  if (ld < D) return fail(PFN_ERR_ARGUMENT, "ld %lld < D = H (F + 3) + 2 = %d", (long long)ld, D);
+  if (!(lr >= 0.f && lr <= 3.4e38f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) || !(bandwidth_factor > 0.f))
+    return fail(PFN_ERR_ARGUMENT, "bad bnn_svgd_steps arguments (lr %g >= 0 and finite, beta1 %g and beta2 %g in [0, 1), eps %g >= 0, bandwidth_factor %g > 0)", lr, beta1,
+                beta2, eps, bandwidth_factor);
+  const int64_t need = bnn_svgd_workspace_bytes(P, num_particles, D);
+  if (workspace_bytes < need || (need > 0 && !workspace))
+    return fail(PFN_ERR_ARGUMENT, "workspace_bytes %lld < pfn_bnn_svgd_workspace_bytes = %lld (or a NULL workspace)", (long long)workspace_bytes, (long long)need);
+  if (num_steps == 0) return PFN_OK;
+  BnnSvgdArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.state = state; a.ld = ld; a.P = P; a.S = S; a.F = F; a.H = H; a.activation = activation; a.N = num_particles; a.step0 = step0;
+  a.num_steps = num_steps; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.bandwidth_factor = bandwidth_factor;
+  a.grads = need > 0 ? (float*)workspace : nullptr; a.potential = potential; a.bandwidth = bandwidth;
+  PFN_TRY(launch_bnn_svgd_steps(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
 int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
                           float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
                           uint64_t seed, uint64_t offset, void* stream) {

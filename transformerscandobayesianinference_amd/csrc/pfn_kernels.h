@@ -549,6 +549,28 @@ struct BnnSviArgs {
 };
 int launch_bnn_svi_steps(const BnnSviArgs& a, hipStream_t s);
 
+// ---- SVGD on the BNN (bnn_svgd.hip): num_steps steps of (grad U -> median bandwidth -> Stein direction -> Adam) on N particles per problem in one launch -----
+struct BnnSvgdArgs {
+  const float* x;        // [P,S,F]
+  const float* y;        // [P,S]: class = y > 0.5
+  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [0,S]); null = S
+  float* state;          // [P,3,N,ld]: particles, m, v; columns >= D are never touched
+  long ld;
+  int P, S, F, H, activation, N;      // N particles per problem
+  long step0;
+  int num_steps;
+  float lr, beta1, beta2, eps, bandwidth_factor;
+  float* grads;          // [P,N,D] (the workspace) when the state is not resident in LDS, else unused
+  float* potential;      // [P,num_steps] or null
+  float* bandwidth;      // [P,ld] or null
+};
+// particles, gradients and both Adam moments ([4][N][D | 1] f32) stay in LDS for the whole launch when they fit this many bytes; otherwise the state stays in
+// the caller's buffer, the gradients go through the workspace and LDS holds a tile of 64 coordinate columns
+constexpr long BNN_SVGD_STATE_BUDGET = 66560;
+inline bool bnn_svgd_resident(int N, int D) { return 16L * N * (D | 1) <= BNN_SVGD_STATE_BUDGET; }
+inline int64_t bnn_svgd_workspace_bytes(int P, int N, int D) { return bnn_svgd_resident(N, D) ? 0 : (int64_t)P * N * D * 4; }
+int launch_bnn_svgd_steps(const BnnSvgdArgs& a, hipStream_t s);
+
 // ---- BNN prior sampler (mlp_prior.hip) -----------------------------------------------------------
 struct MlpPriorArgs {
   const float* weights;   // [num_models][Lmax][HP][HP]: layer l transposed ([in][out]), zero padded

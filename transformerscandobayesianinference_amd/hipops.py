@@ -397,3 +397,49 @@ def bnn_svi_steps(x, y, state, H, num_steps, step0=0, num_particles=1, lr=1e-3, 
                                             num_steps, float(lr), float(betas[0]), float(betas[1]), float(eps), int(seed), _hip.ptr(problem_ids), loss.data_ptr(),
                                             _hip.stream_ptr(x.device)), 'pfn_bnn_svi_steps')
     return loss
+
+
+# ---- SVGD on the BNN (csrc/bnn_svgd.hip; include/pfn_hip.h "SVGD on the BNN") ----
+SVGD_ROWS = ('particles', 'm', 'v')      # the row blocks of a particle state
+SVGD_MAX_PARTICLES = 64                  # PFN_BNN_SVGD_MAX_PARTICLES
+
+
+def bnn_svgd_state(P, N, F, H, device, particles0=None):
+    """The state of N Stein particles per problem at step 0: [P, 3, N, D] f32 with the particles particles0 ([P, N, D]) and zero Adam moments.  None leaves
+    the particles at zero for the caller to fill: coincident particles have no bandwidth (h = 0) and a step from them is non-finite."""
+    D = bnn_num_params(F, H)
+    state = torch.zeros(int(P), 3, int(N), D, dtype=torch.float32, device=device)
+    if particles0 is not None:
+        assert tuple(particles0.shape) == (int(P), int(N), D), 'particles0 [P, N, D]'
+        state[:, 0] = particles0.to(device=device, dtype=torch.float32)
+    return state
+
+
+def bnn_svgd_steps(x, y, state, H, num_steps, step0=0, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, bandwidth_factor=1.0, n_of=None, activation=0, potential=None,
+                   bandwidth=None):
+    """`num_steps` steps of SVGD (grad U -> per-coordinate median bandwidth -> Stein direction -> Adam) on the particles of P problems in one launch
+    (pfn_bnn_svgd_steps).  x [P,S,F], y [P,S], state [P, 3, N, ld >= D] contiguous f32 on the GPU (updated in place; bnn_svgd_state), n_of [P] int32 or None.
+    The launch covers the absolute steps step0 .. step0 + num_steps - 1.  Returns (potential [P, num_steps], bandwidth [P, ld]) (fresh tensors unless given):
+    the mean over particles of U before every step's update, and h of the last step in the first D columns (untouched when num_steps = 0)."""
+    _hip.require_gpu_tensor(x, 'x')
+    P, S, F = x.shape
+    num_steps, step0 = int(num_steps), int(step0)
+    assert state.dim() == 4 and state.shape[:2] == (P, 3) and y.shape == (P, S), 'state [P, 3, N, ld], y [P, S]'
+    N, ld = state.shape[2], state.shape[3]
+    for t in (x, y, state):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
+    if n_of is not None:
+        assert n_of.dtype == torch.int32 and n_of.shape == (P,) and n_of.is_contiguous() and n_of.device == x.device
+    if potential is None:
+        potential = torch.empty(P, max(num_steps, 0), dtype=torch.float32, device=x.device)
+    if bandwidth is None:
+        bandwidth = torch.zeros(P, ld, dtype=torch.float32, device=x.device)
+    assert potential.shape == (P, num_steps) and potential.dtype == torch.float32 and potential.is_contiguous() and potential.device == x.device
+    assert bandwidth.shape == (P, ld) and bandwidth.dtype == torch.float32 and bandwidth.is_contiguous() and bandwidth.device == x.device
+    lib = _hip.lib()
+    ws_bytes = int(lib.pfn_bnn_svgd_workspace_bytes(P, N, F, int(H)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes > 0 else None      # negative (bad shapes): the call below names what is wrong
+    _hip.check(lib.pfn_bnn_svgd_steps(x.data_ptr(), y.data_ptr(), _hip.ptr(n_of), state.data_ptr(), ld, P, S, F, int(H), BNN_ACTIVATIONS[activation], N, step0,
+                                      num_steps, float(lr), float(betas[0]), float(betas[1]), float(eps), float(bandwidth_factor), _hip.ptr(ws), max(ws_bytes, 0),
+                                      potential.data_ptr(), bandwidth.data_ptr(), _hip.stream_ptr(x.device)), 'pfn_bnn_svgd_steps')
+    return potential, bandwidth

@@ -8,9 +8,14 @@ class, its potential and gradient are ONE HIP launch for every chain of every da
 The reference's SVI arm (`eval_svi`, :211-246) fits pyro's AutoDiagonalNormal guide with Trace_ELBO and Adam, one dataset and one Python iteration per step.
 Here the whole step loop of every dataset is one persistent launch (`hipops.bnn_svi_steps`, csrc/bnn_svi.hip, one block per dataset): `fit_bnn_svi` returns
 a `BnnGuide`, `eval_svi` scores it through the same predictive kernel.  A guide has no limit on D, so SVI also runs the 'big' spec that NUTS refuses.
-Nothing depends on pyro.  DESIGN.md sections 16 and 17 have the kernels; INTEGRATION.md lists what differs from the reference.
 
-Not built: SVGD (`eval_svi(svgd=True)`) -- it needs a Stein-kernel particle step beside the ELBO kernel -- and the plotting helpers."""
+The reference's SVGD arm (`eval_svi(..., svgd=True)`: pyro's SVGD with RBFSteinKernel and 50 particles) is `eval_svgd` here: `fit_bnn_svgd` keeps N particles
+per dataset and advances them by the Stein step (potential gradient, per-coordinate median bandwidth, kernel-weighted direction, Adam), again the whole step
+loop of every dataset in one persistent launch (`hipops.bnn_svgd_steps`, csrc/bnn_svgd.hip); it returns `BnnParticles`, whose predictive is the particles
+themselves.  `training_steps` / `training_samples` take the methods 'mcmc', 'svi' and 'svgd'.
+Nothing depends on pyro.  DESIGN.md sections 16, 17 and 18 have the kernels; INTEGRATION.md lists what differs from the reference.
+
+Not built: the plotting helpers."""
 import math
 import os
 import time
@@ -294,9 +299,9 @@ def fit_bnn_svi(x, y, model_spec, n_of=None, num_steps=1024, lr=1e-3, num_partic
     return BnnGuide(state, losses, model_spec, activation)
 
 
-def _require_gpu(device, what):
+def _require_gpu(device, what, kernel='the ELBO step kernel (pfn_bnn_svi_steps) runs on the GPU only and there is no CPU fallback'):
     if torch.device(device).type != 'cuda':
-        raise NotImplementedError(f'{what}: the ELBO step kernel (pfn_bnn_svi_steps) runs on the GPU only and there is no CPU fallback; got device {device!r}')
+        raise NotImplementedError(f'{what}: {kernel}; got device {device!r}')
 
 
 def eval_svi(X, y, device, model_sampler, training_samples_n, num_train_steps, num_pred_samples, lr=1e-3, num_particles=1, svgd=False, sample_obs=False, seed=0):
@@ -305,7 +310,8 @@ def eval_svi(X, y, device, model_sampler, training_samples_n, num_train_steps, n
     `model_sampler`: a spec dict or the reference's callable.  The estimators are eval_mcmc's: the mean class-1 probability by default, sample_obs=True for
     the reference's sampled observations."""
     if svgd:
-        raise NotImplementedError('svgd=True: SVGD is not built here -- it needs a Stein-kernel particle step beside the ELBO kernel; svgd=False (SVI) is available')
+        raise NotImplementedError('svgd=True: eval_svi fits the ELBO guide only; the Stein-kernel particle step is eval_svgd(X, y, device, model_sampler, '
+                                  'training_samples_n, num_train_steps)')
     _require_gpu(device, 'eval_svi')
     spec, activation = _spec_of(model_sampler)
     X, y = X.to(device).float(), y.to(device).float()
@@ -314,6 +320,61 @@ def eval_svi(X, y, device, model_sampler, training_samples_n, num_train_steps, n
     guide = fit_bnn_svi(X_train, y_train, spec, num_steps=num_train_steps, lr=lr, num_particles=num_particles, seed=seed, activation=activation)
     prob1 = guide.predictive(X_test, num_pred_samples, seed=seed)      # [P, N, m]
     return _score(prob1, y_test, sample_obs, seed)
+
+
+class BnnParticles:
+    """Stein particles of the BNN's weights for P problems (fit_bnn_svgd): particles [P, N, D] in the layout of BayesianModel.pack, potentials [P, T] (the mean
+    over particles of U before every step's update), state [P, 3, N, D] (hipops.bnn_svgd_state: what a further hipops.bnn_svgd_steps call continues from)."""
+
+    def __init__(self, state, potentials, model_spec, activation):
+        self.state, self.potentials, self.model_spec, self.activation = state, potentials, dict(model_spec), activation
+        self.particles = state[:, 0]
+
+    def predictive(self, x_test):
+        """Class-1 probability of every particle at x_test [P, m, F]: prob1 [P, N, m] (pfn_bnn_predict)."""
+        P, N, D = self.particles.shape
+        x_test = x_test.to(self.particles.device).float().contiguous()
+        assert x_test.shape[0] == P and x_test.shape[2] == self.model_spec['num_features']
+        theta = self.particles.reshape(P * N, D).contiguous()
+        return hipops.bnn_predict(x_test, theta, self.model_spec['embed'], K=N, activation=self.activation).view(P, N, x_test.shape[1])
+
+
+def fit_bnn_svgd(x, y, model_spec, n_of=None, num_steps=1024, lr=1e-3, num_particles=50, seed=0, activation='identity', bandwidth_factor=1.0, steps_per_launch=256):
+    """SVGD on the weights of the BNN given x [P, S, F], y [P, S] (class = y > 0.5; problem p uses its first n_of[p] rows, all when None): `num_particles`
+    particles per problem, `num_steps` Stein steps with Adam, every problem in the same launches (hipops.bnn_svgd_steps).  Every coordinate of every initial
+    particle is the median of 15 N(0, 1) draws from `seed` (pyro's init_to_median under the particle plate).  `steps_per_launch` only bounds the length of one
+    launch: the result does not depend on it, bit for bit.  Returns BnnParticles."""
+    activation = _activation_name(activation)
+    F, H = int(model_spec['num_features']), int(model_spec['embed'])
+    D = hipops.bnn_num_params(F, H)
+    hipops._hip.require_gpu_tensor(x, 'x')
+    x, y = x.float().contiguous(), y.to(x.device).float().contiguous()
+    P, S, _ = x.shape
+    assert x.shape[2] == F and y.shape == (P, S)
+    N, num_steps, per = int(num_particles), int(num_steps), max(int(steps_per_launch), 1)
+    if n_of is not None:
+        n_of = torch.as_tensor(n_of, dtype=torch.int32, device=x.device).contiguous()
+    draws = torch.randn(15, P, N, D, generator=torch.Generator().manual_seed(int(seed)))      # on the host: the start does not depend on the device
+    state = hipops.bnn_svgd_state(P, N, F, H, x.device, particles0=draws.median(0).values)
+    potentials = torch.empty(P, num_steps, device=x.device)
+    for step0 in range(0, num_steps, per):
+        n = min(per, num_steps - step0)
+        potentials[:, step0:step0 + n] = hipops.bnn_svgd_steps(x, y, state, H, n, step0=step0, lr=lr, bandwidth_factor=bandwidth_factor, n_of=n_of, activation=activation)[0]
+    return BnnParticles(state, potentials, model_spec, activation)
+
+
+def eval_svgd(X, y, device, model_sampler, training_samples_n, num_train_steps, num_pred_samples=None, lr=1e-3, num_particles=50, sample_obs=False, seed=0):
+    """SVGD on the BNN for every dataset of X [P, T, F], y [P, T] at once, trained on the first `training_samples_n` rows and scored on the rest with the
+    particles themselves: returns (nll [P], acc [P]) as numpy arrays (the reference's eval_svi(..., svgd=True), :211-246, which scores the untrained guide
+    instead).  `num_pred_samples` is accepted for signature parity and ignored: the predictive is the `num_particles` particles.  The estimators are
+    eval_mcmc's: the mean class-1 probability by default, sample_obs=True for the reference's sampled observations."""
+    _require_gpu(device, 'eval_svgd', 'the Stein step kernel (pfn_bnn_svgd_steps) runs on the GPU only, like the ELBO step kernel; no CPU fallback')
+    spec, activation = _spec_of(model_sampler)
+    X, y = X.to(device).float(), y.to(device).float()
+    n = int(training_samples_n)
+    X_train, y_train, X_test, y_test = X[:, :n].contiguous(), y[:, :n].contiguous(), X[:, n:].contiguous(), y[:, n:].contiguous()
+    fit = fit_bnn_svgd(X_train, y_train, spec, num_steps=num_train_steps, lr=lr, num_particles=num_particles, seed=seed, activation=activation)
+    return _score(fit.predictive(X_test), y_test, sample_obs, seed)
 
 
 def _eval(method, X, y, device, model_spec, training_samples_n, steps):
@@ -336,7 +397,10 @@ def training_steps(method, X, y, model_spec, device='cuda', path_interfix='', ov
             print(f'already done {s}')
             continue
         start = time.time()
-        nll, acc = _eval(method, X, y, device, model_spec, training_samples_n, s)
+        if method == 'svgd':
+            nll, acc = eval_svgd(X, y, device, model_spec, training_samples_n, num_train_steps=s)
+        else:
+            nll, acc = _eval(method, X, y, device, model_spec, training_samples_n, s)
         elapsed = time.time() - start
         print(s)
         print('NLL ', compute_mean_and_conf_interval(nll))
@@ -348,15 +412,18 @@ def training_steps(method, X, y, model_spec, device='cuda', path_interfix='', ov
 
 
 def training_samples(method, X, y, model_spec, evaluation_points, steps=None, device='cuda', path_interfix='', overwrite=False):
-    """The same at a fixed number of transitions (512 for NUTS) for every training-set size of `evaluation_points`."""
-    num_pred_samples = steps if steps else (1024 if method == 'svi' else 512)
+    """The same at a fixed number of transitions (512 for NUTS, 1024 steps for SVI and SVGD) for every training-set size of `evaluation_points`."""
+    num_pred_samples = steps if steps else (1024 if method in ('svi', 'svgd') else 512)
     for training_samples_n in evaluation_points:
         path = f'{path_interfix}/results_{method}_{num_pred_samples}_training_samples_{training_samples_n}.npy'
         if os.path.isfile(path) and not overwrite:
             print(f'already done {training_samples_n}')
             continue
         start = time.time()
-        nll, acc = _eval(method, X, y, device, model_spec, training_samples_n, num_pred_samples)
+        if method == 'svgd':
+            nll, acc = eval_svgd(X, y, device, model_spec, training_samples_n, num_train_steps=num_pred_samples)
+        else:
+            nll, acc = _eval(method, X, y, device, model_spec, training_samples_n, num_pred_samples)
         elapsed = time.time() - start
         print('NLL ', compute_mean_and_conf_interval(nll))
         print('ACC ', compute_mean_and_conf_interval(acc))

@@ -13,34 +13,12 @@ import numpy as np
 import torch
 
 import bnn_f64 as ref
+from bnn_f64 import adam, f32, potentials      # noqa: F401  (shared with the other restatement; the tests reach them through this module)
 
 ROWS = ('particles', 'm', 'v')
 # The no-data case of the host and the GPU test: n = 0, so the target is the prior N(0, I) in every coordinate.  The start is fit_bnn_svgd's: every coordinate
 # of every particle the median of 15 N(0, 1) draws (standard deviation about 0.32).
 NO_DATA = dict(F=3, H=5, P=2, N=50, T=300, lr=0.05, seed=5)
-
-
-def f32(v):
-    """The f64 value of v rounded to f32: what the kernel receives for lr, beta1, beta2, eps and bandwidth_factor."""
-    return float(np.float32(v))
-
-
-def potentials(theta, x, y, n, F, H, activation=0):
-    """U(x_k) [N] for theta [N, D] (differentiable): tests/bnn_f64.potential, batched over the particles."""
-    N, D = theta.shape
-    U = 0.5 * (theta * theta).sum(1) + 0.5 * D * math.log(2. * math.pi)
-    if n > 0:
-        W1 = theta[:, :H * F].reshape(N, H, F)
-        b1 = theta[:, H * F:H * F + H]
-        W2 = theta[:, H * F + H:H * F + 3 * H].reshape(N, 2, H)
-        b2 = theta[:, H * F + 3 * H:]
-        h = torch.einsum('nf,khf->knh', x[:n].double(), W1) + b1[:, None, :]
-        if ref.ACT[activation]:
-            h = torch.tanh(h)
-        o = torch.einsum('knh,kch->knc', h, W2) + b2[:, None, :]
-        cls = (y[:n] > 0.5).long()[None, :, None].expand(N, n, 1)
-        U = U - torch.log_softmax(o, -1).gather(2, cls).sum((1, 2))
-    return U
 
 
 def potentials_and_grads(theta, x, y, n, F, H, activation=0):
@@ -65,14 +43,6 @@ def stein_direction(x, g, h):
     diff = x[:, None, :] - x[None, :, :]      # [n, m, d] = x_nd - x_md
     k = torch.exp(-diff * diff / h)
     return (k * g[None, :, :] + k * 2. * (-diff) / h).sum(1) / N
-
-
-def adam(p, m, v, g, t, lr, beta1, beta2, eps):
-    """One Adam update of (p, m, v) with gradient g at t = step index + 1."""
-    m = beta1 * m + (1. - beta1) * g
-    v = beta2 * v + (1. - beta2) * g * g
-    p = p - lr * (m / (1. - beta1 ** t)) / (torch.sqrt(v / (1. - beta2 ** t)) + eps)
-    return p, m, v
 
 
 def step_terms(particles, x, y, n, F, H, activation=0, bandwidth_factor=1.0):

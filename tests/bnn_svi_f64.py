@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 import bnn_f64 as ref
+from bnn_f64 import adam, f32, potentials      # noqa: F401  (shared with the other restatement; the tests reach them through this module)
 import nuts_f64 as emu
 
 ROWS = ('loc', 'u', 'm_loc', 'v_loc', 'm_u', 'v_u')
@@ -33,24 +34,6 @@ def noise(seed, q, t, K, D):
     a0, a1 = 2. * math.pi * u(y), 2. * math.pi * u(w)
     out = np.stack([r0 * np.cos(a0), r0 * np.sin(a0), r1 * np.cos(a1), r1 * np.sin(a1)], -1).reshape(K, 4 * nb)
     return torch.from_numpy(out[:, :D].copy())
-
-
-def potentials(theta, x, y, n, F, H, activation=0):
-    """U(theta_k) [K] for theta [K, D] (differentiable): tests/bnn_f64.potential, batched over the particles."""
-    K, D = theta.shape
-    U = 0.5 * (theta * theta).sum(1) + 0.5 * D * math.log(2. * math.pi)
-    if n > 0:
-        W1 = theta[:, :H * F].reshape(K, H, F)
-        b1 = theta[:, H * F:H * F + H]
-        W2 = theta[:, H * F + H:H * F + 3 * H].reshape(K, 2, H)
-        b2 = theta[:, H * F + 3 * H:]
-        h = torch.einsum('nf,khf->knh', x[:n].double(), W1) + b1[:, None, :]
-        if ref.ACT[activation]:
-            h = torch.tanh(h)
-        o = torch.einsum('knh,kch->knc', h, W2) + b2[:, None, :]
-        cls = (y[:n] > 0.5).long()[None, :, None].expand(K, n, 1)
-        U = U - torch.log_softmax(o, -1).gather(2, cls).sum((1, 2))
-    return U
 
 
 def softplus(u):
@@ -76,19 +59,6 @@ def loss_and_grads(loc, u, eps, x, y, n, F, H, activation=0):
     g_loc = gU.mean(0)
     g_scale = (gU * eps).mean(0) - 1. / scale
     return float(L), g_loc, g_scale * torch.sigmoid(u)
-
-
-def adam(p, m, v, g, t, lr, beta1, beta2, eps):
-    """One Adam update of (p, m, v) with gradient g at t = step index + 1."""
-    m = beta1 * m + (1. - beta1) * g
-    v = beta2 * v + (1. - beta2) * g * g
-    p = p - lr * (m / (1. - beta1 ** t)) / (torch.sqrt(v / (1. - beta2 ** t)) + eps)
-    return p, m, v
-
-
-def f32(v):
-    """The f64 value of v rounded to f32: what the kernel receives for lr, beta1, beta2 and eps."""
-    return float(np.float32(v))
 
 
 def run(state, x, y, n, F, H, activation=0, K=1, step0=0, num_steps=1, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, seed=0, q=0):

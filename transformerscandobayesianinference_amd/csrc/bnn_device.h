@@ -1,10 +1,19 @@
 // Device functions shared by the kernels of the two-layer BNN (bnn_mcmc.hip: potential / gradient / predictive of NUTS chains; bnn_svi.hip: the SVI step
-// loop): the lane's registers, the forward of one hidden unit, the staging of data rows in LDS and the per-row step of the potential and its gradient.
+// loop; bnn_svgd.hip: the SVGD step loop): the lane's registers, the forward of one hidden unit, the staging of data rows in LDS and the per-row step of the
+// potential and its gradient.
 // Mapping: lane = hidden unit, Hp = H rounded up to 8 / 16 / 32 / 64 lanes form a group that holds one parameter vector; a lane
 // keeps W1[j,:], b1[j] and W2[1,j] - W2[0,j] in registers and accumulates its own part of the gradient there.  Only ONE number per data row is reduced over
 // the Hp lanes of a group (the logit difference o_1 - o_0), with a __shfl_xor butterfly in a fixed order (offsets 1, 2, .. Hp/2).
+// Also here, each written once ("The shared pieces", says why the rest is not): the slot map of a lane's Fp + 5 parameters (BnnSlots:
+// SVI and SVGD, and the offsets of the NUTS and predict kernels), slots -> lane registers (bnn_lane: SVI, SVGD), the data-row loop over resident or chunked
+// rows (bnn_data_rows: all three gradient kernels, the NUTS kernel never resident) with its staging prologue (bnn_stage_all: SVI, SVGD) and the n_of clamp
+// (bnn_n_rows: all three), Adam's bias corrections and its update of one coordinate (bnn_ipow, bnn_adam_at, bnn_adam: SVI's loc and u, SVGD's particle
+// coordinate) and, on the host, bnn_dispatch (the H / F / activation dispatch of all three files) and bnn_launch_lds (the launch with more than 64 KB of LDS
+// of SVI and SVGD).
 #pragma once
+#include <type_traits>
 #include "pfn_device.h"
+#include "pfn_kernels.h"
 
 namespace pfn {
 
@@ -29,6 +38,28 @@ template <int FP> struct BnnSums {
     db1 = 0.f, A = 0.f, G = 0.f, U = 0.f;
   }
 };
+
+// a lane's parameters, slot by slot: W1[j,:] (FP), b1[j], W2[0,j], W2[1,j], and b2[0], b2[1]; index(s) is the slot's place in the parameter vector
+template <int FP> struct BnnSlots {
+  static constexpr int NS = FP + 5;
+  int F, H, j, oB1, oW2, oB2;
+  bool unit;
+  PFN_DEV BnnSlots(int F_, int H_, int j_) : F(F_), H(H_), j(j_), oB1(H_ * F_), oW2(oB1 + H_), oB2(oW2 + 2 * H_), unit(j_ < H_) {}
+  PFN_DEV int index(int s) const { return s < FP ? j * F + s : s == FP ? oB1 + j : s == FP + 1 ? oW2 + j : s == FP + 2 ? oW2 + H + j : oB2 + (s - FP - 3); }
+  PFN_DEV bool held(int s) const { return s < FP ? unit && s < F : s < FP + 3 ? unit : true; }      // the lane reads it (every lane of a group reads b2)
+  PFN_DEV bool owned(int s) const { return s < FP + 3 ? held(s) : j == 0; }                        // the lane reports it
+};
+
+// the lane's registers from its slots; b2d = b2[1] - b2[0]
+template <int FP> PFN_DEV BnnLane<FP> bnn_lane(const float (&th)[FP + 5], float& b2d) {
+  BnnLane<FP> L;
+#pragma unroll
+  for (int f = 0; f < FP; ++f) L.w1[f] = th[f];
+  L.b1 = th[FP];
+  L.w2d = th[FP + 2] - th[FP + 1];
+  b2d = th[FP + 4] - th[FP + 3];
+  return L;
+}
 
 template <int HP> PFN_DEV float bnn_group_sum(float v) {
 #pragma unroll
@@ -102,6 +133,81 @@ template <int HP, int FP, int ACT, int RR = BNN_ROWS> PFN_DEV void bnn_rows(cons
   int r = 0;
   for (; r + RR <= rows; r += RR) bnn_row_step<HP, FP, ACT, RR>(L, b2d, xs, ys, r, s);
   for (; r < rows; ++r) bnn_row_step<HP, FP, ACT, 1>(L, b2d, xs, ys, r, s);
+}
+
+// the n_of clamp: the rows of problem p that count
+PFN_DEV int bnn_n_rows(const int* n_of, int p, int S) { return n_of ? min(max(n_of[p], 0), S) : S; }
+
+// the resident staging prologue: all n rows of the problem into xs [n, FP], their thresholded labels into ys [n]; the caller's barrier follows
+template <int FP> PFN_DEV void bnn_stage_all(float* xs, float* ys, const float* xp, const float* yp, int n, int F) {
+  bnn_stage<FP>(xs, xp, 0, n, F, n);
+  for (int r = threadIdx.x; r < n; r += blockDim.x) ys[r] = yp[r] > 0.5f ? 1.f : 0.f;
+}
+
+// the data-row loop: the n rows of the problem (xp [n, F], yp [n]) added to the lane's sums.  Resident rows are in xs / ys already (bnn_stage_all); otherwise
+// they pass through xs [BNN_CHUNK, FP] / ys [BNN_CHUNK] in chunks.  Every thread of the block must be here (the barriers); wave_on (wave-uniform: the
+// butterflies run with all 64 lanes) gates the row steps only.
+template <int HP, int FP, int ACT, int RR> PFN_DEV void bnn_data_rows(const BnnLane<FP>& L, float b2d, float* xs, float* ys, const float* xp, const float* yp, int n, int F, bool resident, bool wave_on, BnnSums<FP>& s) {
+  if (resident) {
+    if (wave_on) bnn_rows<HP, FP, ACT, RR>(L, b2d, xs, ys, n, s);
+    return;
+  }
+  for (int r0 = 0; r0 < n; r0 += BNN_CHUNK) {
+    const int rows = min(BNN_CHUNK, n - r0);
+    __syncthreads();      // the previous chunk has been consumed
+    bnn_stage<FP>(xs, xp, r0, rows, F);
+    if (threadIdx.x < BNN_CHUNK) ys[threadIdx.x] = ((int)threadIdx.x < rows && yp[r0 + threadIdx.x] > 0.5f) ? 1.f : 0.f;
+    __syncthreads();
+    if (wave_on) bnn_rows<HP, FP, ACT, RR>(L, b2d, xs, ys, rows, s);
+  }
+}
+
+// beta^t for an integer t by squaring, in f64: a function of (beta, t) alone, so a run split over launches takes the same bias corrections
+PFN_DEV double bnn_ipow(double b, unsigned long long t) {
+  double r = 1.;
+  while (t) {
+    if (t & 1) r *= b;
+    b *= b;
+    t >>= 1;
+  }
+  return r;
+}
+
+// Adam (torch.optim.Adam, no weight decay) at the absolute step index t: the optimizer's step count is t + 1
+struct BnnAdam {
+  float lr, beta1, beta2, eps, bc1, bc2;
+};
+
+PFN_DEV BnnAdam bnn_adam_at(float lr, float beta1, float beta2, float eps, unsigned long long t) {
+  return {lr, beta1, beta2, eps, (float)(1. - bnn_ipow((double)beta1, t + 1)), (float)(1. - bnn_ipow((double)beta2, t + 1))};
+}
+
+struct BnnAdamOut {
+  float p, m, v;
+};
+
+// one coordinate: parameter p, moments m and v, gradient g -> the three after the step, all by value
+PFN_DEV BnnAdamOut bnn_adam(float p, float m, float v, float g, const BnnAdam h) {
+  const float m1 = h.beta1 * m + (1.f - h.beta1) * g, v1 = h.beta2 * v + (1.f - h.beta2) * g * g;
+  return {p - h.lr * (m1 / h.bc1) / (sqrtf(v1 / h.bc2) + h.eps), m1, v1};
+}
+
+// ---- host: one dispatch and one large-LDS launch for the three files ----
+
+template <int V> using BnnInt = std::integral_constant<int, V>;
+
+// fn(Hp, Fp, activation) with the three as integral constants: Hp = H rounded up to 8 / 16 / 32 / 64, Fp = F rounded up to 4 / 8 / 16
+template <class Fn> int bnn_dispatch(int H, int F, int activation, Fn&& fn) {
+  auto act = [&](auto hp, auto fp) { return activation ? fn(hp, fp, BnnInt<1>{}) : fn(hp, fp, BnnInt<0>{}); };
+  auto feat = [&](auto hp) { return F <= 4 ? act(hp, BnnInt<4>{}) : F <= 8 ? act(hp, BnnInt<8>{}) : act(hp, BnnInt<16>{}); };
+  return H <= 8 ? feat(BnnInt<8>{}) : H <= 16 ? feat(BnnInt<16>{}) : H <= 32 ? feat(BnnInt<32>{}) : feat(BnnInt<64>{});
+}
+
+// a launch with `bytes` of dynamic LDS, raising the kernel's allowance first when it is more than the 64 KB a kernel has by default
+template <class A, class C> int bnn_launch_lds(void (*kernel)(A, C), LdsAllowance& allow, dim3 grid, dim3 block, size_t bytes, hipStream_t s, const A& a, const C& c) {
+  if (bytes > 64 * 1024) allow.ensure(kernel, bytes);
+  kernel<<<grid, block, bytes, s>>>(a, c);
+  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 
 }  // namespace

@@ -4,7 +4,7 @@
 //
 // Mapping: one block of eight waves per problem (two per SIMD: a wave alone on its SIMD issues a vector instruction every four cycles, two share it at one
 // every two, and each covers the other's LDS latency), nothing crosses blocks.
-// Phase 1 is section 16's lane = hidden unit (bnn_device.h): a group of Hp lanes holds one PARTICLE, 64 / Hp particles share a wave, N beyond the block's
+// Phase 1 is section 16's lane = hidden unit (bnn_device.h, whose header lists the pieces shared with the other two kernels): a group of Hp lanes holds one PARTICLE, 64 / Hp particles share a wave, N beyond the block's
 // capacity runs in rounds; nothing is reduced over particles, each group writes grad U of its particle.
 // Phases 2-4 are independent per coordinate: a WAVE takes a coordinate and lane n is particle n (N <= 64), four coordinates at a time so that their dependent
 // LDS reads overlap.  (2) the lanes rank the coordinate's N values (ties by index) and scatter them sorted into the wave's scratch; the k-th smallest
@@ -34,17 +34,6 @@ struct SvgdLaunch {
   float log_n1;                              // log(N + 1)
 };
 
-// beta^t for an integer t by squaring, in f64: a function of (beta, t) alone, so a run split over launches takes the same bias corrections
-PFN_DEV double svgd_ipow(double b, unsigned long long t) {
-  double r = 1.;
-  while (t) {
-    if (t & 1) r *= b;
-    b *= b;
-    t >>= 1;
-  }
-  return r;
-}
-
 template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * SVGD_WAVES, 2) bnn_svgd_kernel(BnnSvgdArgs a, SvgdLaunch c) {
   extern __shared__ __attribute__((aligned(16))) float svgd_lds[];
   constexpr int RR = FP == 16 ? 2 : BNN_ROWS;      // rows in flight: four of 16 columns beside the particle's parameters do not fit 256 registers
@@ -62,8 +51,7 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * SVGD_W
   float* V = M + N * LW;                      // [N][LW]: Adam's v
   float* srt = V + N * LW;                    // [WAVES][CI][64]: a coordinate's values, sorted
   float* up = srt + WAVES * CI * 64;          // [64]: U(x_n)
-  int n = a.S;
-  if (a.n_of) n = min(max(a.n_of[p], 0), a.S);
+  const int n = bnn_n_rows(a.n_of, p, a.S);
   const float* xp = a.x + (long)p * a.S * F;
   const float* yp = a.y + (long)p * a.S;
   float* sp = a.state + (long)p * 3 * N * a.ld;      // rows [0, N) particles, [N, 2N) m, [2N, 3N) v
@@ -78,17 +66,10 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * SVGD_W
       V[r * LW + i] = src[2L * N * a.ld];
     }
   }
-  if (c.rows_resident) {
-    bnn_stage<FP>(xs, xp, 0, n, F, n);
-    for (int r = threadIdx.x; r < n; r += blockDim.x) ys[r] = yp[r] > 0.5f ? 1.f : 0.f;
-  }
+  if (c.rows_resident) bnn_stage_all<FP>(xs, ys, xp, yp, n, F);
   __syncthreads();
 
-  const int oB1 = H * F, oW2 = oB1 + H, oB2 = oW2 + 2 * H;
-  const bool unit = j < H;
-  auto index = [&](int s) { return s < FP ? j * F + s : s == FP ? oB1 + j : s == FP + 1 ? oW2 + j : s == FP + 2 ? oW2 + H + j : oB2 + (s - FP - 3); };
-  auto held = [&](int s) { return s < FP ? unit && s < F : s < FP + 3 ? unit : true; };      // the lane reads it (every lane of a group reads b2)
-  auto owned = [&](int s) { return s < FP + 3 ? held(s) : j == 0; };                       // the lane reports it
+  const BnnSlots<FP> sl(F, H, j);
   const unsigned kth = (unsigned)((N * (N - 1) / 2 - 1) / 2);      // torch.median: the lower middle of the N (N - 1) / 2 pairs, counted from 0
   const float inv_n = 1.f / (float)N;
 
@@ -100,41 +81,25 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * SVGD_W
       const int k0 = rd * cpb + wave * CPW, k = k0 + grp;
       const bool wave_on = k0 < N, part = k < N;      // wave_on is wave-uniform
       const int kc = part ? k : 0;
-      BnnLane<FP> L;
-      float th[NS];
+      float th[NS], b2d;
       if (c.resident) {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          const bool on = part && held(s);
-          th[s] = on ? X[kc * LW + index(s)] : 0.f;
+          const bool on = part && sl.held(s);
+          th[s] = on ? X[kc * LW + sl.index(s)] : 0.f;
         }
       } else {
         const float* row = sp + (long)kc * a.ld;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          const bool on = part && held(s);
-          th[s] = on ? row[index(s)] : 0.f;
+          const bool on = part && sl.held(s);
+          th[s] = on ? row[sl.index(s)] : 0.f;
         }
       }
-#pragma unroll
-      for (int f = 0; f < FP; ++f) L.w1[f] = th[f];
-      L.b1 = th[FP];
-      L.w2d = th[FP + 2] - th[FP + 1];
-      const float b2d = th[FP + 4] - th[FP + 3];
+      const BnnLane<FP> L = bnn_lane<FP>(th, b2d);
       BnnSums<FP> sm;
       sm.clear();
-      if (c.rows_resident) {
-        if (wave_on) bnn_rows<HP, FP, ACT, RR>(L, b2d, xs, ys, n, sm);
-      } else {
-        for (int r0 = 0; r0 < n; r0 += BNN_CHUNK) {
-          const int rows = min(BNN_CHUNK, n - r0);
-          __syncthreads();      // the previous chunk has been consumed
-          bnn_stage<FP>(xs, xp, r0, rows, F);
-          if (threadIdx.x < BNN_CHUNK) ys[threadIdx.x] = ((int)threadIdx.x < rows && yp[r0 + threadIdx.x] > 0.5f) ? 1.f : 0.f;
-          __syncthreads();
-          if (wave_on) bnn_rows<HP, FP, ACT, RR>(L, b2d, xs, ys, rows, sm);
-        }
-      }
+      bnn_data_rows<HP, FP, ACT, RR>(L, b2d, xs, ys, xp, yp, n, F, c.rows_resident, wave_on, sm);
       if (wave_on) {
         float g[NS];      // grad U(x_k) of the lane's parameters, prior included
 #pragma unroll
@@ -147,11 +112,11 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * SVGD_W
         float ql = 0.f;      // the lane's share of |theta|^2 / 2
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          const bool on = part && owned(s);
+          const bool on = part && sl.owned(s);
           ql += on ? 0.5f * th[s] * th[s] : 0.f;
           if (on) {
-            if (c.resident) G[kc * LW + index(s)] = g[s];
-            else gw[(long)kc * D + index(s)] = g[s];
+            if (c.resident) G[kc * LW + sl.index(s)] = g[s];
+            else gw[(long)kc * D + sl.index(s)] = g[s];
           }
         }
         ql = bnn_group_sum<HP>(ql) + sm.U + (float)D * HALF_LOG_2PI;
@@ -165,8 +130,8 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * SVGD_W
       a.potential[(long)p * a.num_steps + it] = u * inv_n;
     }
 
-    // ---- phases 2-4, coordinate by coordinate: bandwidth, Stein direction, Adam (torch.optim.Adam, no weight decay, t = absolute step index + 1) ----
-    const float bc1 = (float)(1. - svgd_ipow((double)a.beta1, t + 1)), bc2 = (float)(1. - svgd_ipow((double)a.beta2, t + 1));
+    // ---- phases 2-4, coordinate by coordinate: bandwidth, Stein direction, Adam ----
+    const BnnAdam ad = bnn_adam_at(a.lr, a.beta1, a.beta2, a.eps, t);
     const bool last = it == a.num_steps - 1;
     const int ntiles = c.resident ? 1 : (D + SVGD_TILE - 1) / SVGD_TILE;
     for (int tile = 0; tile < ntiles; ++tile) {
@@ -262,10 +227,8 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * SVGD_W
             if (cb + q < cw) {
               if (lane < N) {
                 const int o = lane * LW + dc[q];
-                const float s = acc[q] * inv_n;
-                const float m1 = a.beta1 * M[o] + (1.f - a.beta1) * s, v1 = a.beta2 * V[o] + (1.f - a.beta2) * s * s;
-                X[o] = xn[q] - a.lr * (m1 / bc1) / (sqrtf(v1 / bc2) + a.eps);
-                M[o] = m1, V[o] = v1;
+                const BnnAdamOut up1 = bnn_adam(xn[q], M[o], V[o], acc[q] * inv_n, ad);
+                X[o] = up1.p, M[o] = up1.m, V[o] = up1.v;
               }
               if (last && a.bandwidth && lane == 0) a.bandwidth[(long)p * a.ld + c0 + dc[q]] = hd[q];
             }
@@ -296,40 +259,23 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * SVGD_W
   }
 }
 
-template <int HP, int FP> int svgd_launch_hf(const BnnSvgdArgs& a, hipStream_t s) {
-  const int D = a.H * (a.F + 3) + 2;
-  SvgdLaunch c;
-  c.resident = bnn_svgd_resident(a.N, D);      // the rule pfn_bnn_svgd_workspace_bytes sizes the workspace by
-  c.LW = c.resident ? (D | 1) : SVGD_TILE + 1;
-  c.rows_resident = (long)a.S * (FP + 1) * 4 <= SVGD_ROWS_BUDGET;
-  c.cap = c.rows_resident ? a.S : BNN_CHUNK;
-  c.log_n1 = (float)std::log((double)(a.N + 1));
-  const size_t bytes = ((size_t)c.cap * FP + ((c.cap + 3) & ~3) + (size_t)4 * a.N * c.LW + SVGD_WAVES * SVGD_CI * 64 + 64) * sizeof(float);
-  static_assert(BNN_SVGD_STATE_BUDGET + SVGD_ROWS_BUDGET + 16 + BNN_CHUNK * (FP + 1) * 4 + (SVGD_WAVES * SVGD_CI * 64 + 64) * 4 <= 160 * 1024, "bnn_svgd: LDS");
-  const dim3 grid((unsigned)a.P), block(64 * SVGD_WAVES);
-  static LdsAllowance allow[2];
-  auto run = [&](auto kernel, LdsAllowance& al) {
-    if (bytes > 64 * 1024) al.ensure(kernel, bytes);
-    kernel<<<grid, block, bytes, s>>>(a, c);
-  };
-  if (a.activation) run(bnn_svgd_kernel<HP, FP, 1>, allow[1]);
-  else run(bnn_svgd_kernel<HP, FP, 0>, allow[0]);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-}
-
-template <int HP> int svgd_launch_h(const BnnSvgdArgs& a, hipStream_t s) {
-  if (a.F <= 4) return svgd_launch_hf<HP, 4>(a, s);
-  if (a.F <= 8) return svgd_launch_hf<HP, 8>(a, s);
-  return svgd_launch_hf<HP, 16>(a, s);
-}
-
 }  // namespace
 
 int launch_bnn_svgd_steps(const BnnSvgdArgs& a, hipStream_t s) {
-  if (a.H <= 8) return svgd_launch_h<8>(a, s);
-  if (a.H <= 16) return svgd_launch_h<16>(a, s);
-  if (a.H <= 32) return svgd_launch_h<32>(a, s);
-  return svgd_launch_h<64>(a, s);
+  return bnn_dispatch(a.H, a.F, a.activation, [&](auto hp, auto fp, auto act) {
+    constexpr int HP = decltype(hp)::value, FP = decltype(fp)::value, ACT = decltype(act)::value;
+    const int D = a.H * (a.F + 3) + 2;
+    SvgdLaunch c;
+    c.resident = bnn_svgd_resident(a.N, D);      // the rule pfn_bnn_svgd_workspace_bytes sizes the workspace by
+    c.LW = c.resident ? (D | 1) : SVGD_TILE + 1;
+    c.rows_resident = (long)a.S * (FP + 1) * 4 <= SVGD_ROWS_BUDGET;
+    c.cap = c.rows_resident ? a.S : BNN_CHUNK;
+    c.log_n1 = (float)std::log((double)(a.N + 1));
+    const size_t bytes = ((size_t)c.cap * FP + ((c.cap + 3) & ~3) + (size_t)4 * a.N * c.LW + SVGD_WAVES * SVGD_CI * 64 + 64) * sizeof(float);
+    static_assert(BNN_SVGD_STATE_BUDGET + SVGD_ROWS_BUDGET + 16 + BNN_CHUNK * (FP + 1) * 4 + (SVGD_WAVES * SVGD_CI * 64 + 64) * 4 <= 160 * 1024, "bnn_svgd: LDS");
+    static LdsAllowance allow;      // one per instantiation
+    return bnn_launch_lds(bnn_svgd_kernel<HP, FP, ACT>, allow, dim3((unsigned)a.P), dim3(64 * SVGD_WAVES), bytes, s, a, c);
+  });
 }
 
 }  // namespace pfn

@@ -2,7 +2,8 @@
 // AutoDiagonalNormal guide, Trace_ELBO(num_particles), Adam): ONE launch advances the guides of P problems by num_steps steps of
 // (draw noise -> ELBO gradient -> Adam).  DESIGN.md section 17 has the mapping; include/pfn_hip.h the contract.
 //
-// Mapping: one block per problem, nothing crosses blocks.  Section 16's lane = hidden unit (bnn_device.h): a group of Hp lanes holds one PARTICLE
+// Mapping: one block per problem, nothing crosses blocks.  Section 16's lane = hidden unit (bnn_device.h, whose header lists the pieces shared with the
+// other two kernels): a group of Hp lanes holds one PARTICLE
 // theta_k = loc + scale eps_k, 64 / Hp particles share a wave, up to four waves; K beyond the block's capacity runs in rounds.  The six state rows, scale
 // and log scale stay in LDS for the whole launch, and so do the problem's data rows when they fit (else they are staged in section 16's 64-row chunks in
 // every round).  Per step: (1) the lanes of a group draw their particle's noise, four normals per Philox block, into LDS; (2) every lane forms its own
@@ -23,17 +24,6 @@ struct SviLaunch {
   int waves, Dp, cap, resident;
 };
 
-// beta^t for an integer t by squaring, in f64: a function of (beta, t) alone, so a run split over launches takes the same bias corrections
-PFN_DEV double svi_ipow(double b, unsigned long long t) {
-  double r = 1.;
-  while (t) {
-    if (t & 1) r *= b;
-    b *= b;
-    t >>= 1;
-  }
-  return r;
-}
-
 PFN_DEV float svi_softplus(float u) { return fmaxf(u, 0.f) + log1pf(expf(-fabsf(u))); }
 
 template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MAX_WAVES, 2) bnn_svi_kernel(BnnSviArgs a, SviLaunch c) {
@@ -53,8 +43,7 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
   float* xs = lw + 4;                    // [cap][FP]
   float* ys = xs + c.cap * FP;           // [cap]
   const unsigned long long q = a.problem_ids ? (unsigned long long)a.problem_ids[p] : (unsigned long long)p;
-  int n = a.S;
-  if (a.n_of) n = min(max(a.n_of[p], 0), a.S);
+  const int n = bnn_n_rows(a.n_of, p, a.S);
   const float* xp = a.x + (long)p * a.S * F;
   const float* yp = a.y + (long)p * a.S;
   float* sp = a.state + (long)p * 6 * a.ld;
@@ -63,10 +52,7 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
     const int r = idx / D, i = idx - r * D;
     st[r * Dp + i] = sp[r * a.ld + i];
   }
-  if (c.resident) {
-    bnn_stage<FP>(xs, xp, 0, n, F, n);
-    for (int r = threadIdx.x; r < n; r += blockDim.x) ys[r] = yp[r] > 0.5f ? 1.f : 0.f;
-  }
+  if (c.resident) bnn_stage_all<FP>(xs, ys, xp, yp, n, F);
   __syncthreads();
   for (int i = threadIdx.x; i < D; i += blockDim.x) {
     const float s = svi_softplus(st[Dp + i]);
@@ -75,11 +61,7 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
   }
   __syncthreads();
 
-  const int oB1 = H * F, oW2 = oB1 + H, oB2 = oW2 + 2 * H;
-  const bool unit = j < H;
-  auto index = [&](int s) { return s < FP ? j * F + s : s == FP ? oB1 + j : s == FP + 1 ? oW2 + j : s == FP + 2 ? oW2 + H + j : oB2 + (s - FP - 3); };
-  auto held = [&](int s) { return s < FP ? unit && s < F : s < FP + 3 ? unit : true; };      // the lane reads it (every lane of a group reads b2)
-  auto owned = [&](int s) { return s < FP + 3 ? held(s) : j == 0; };                       // the lane reports it
+  const BnnSlots<FP> sl(F, H, j);
   const float inv_k = 1.f / (float)K;
 
   for (int it = 0; it < a.num_steps; ++it) {
@@ -97,34 +79,18 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
         }
       }
       __syncthreads();
-      BnnLane<FP> L;
-      float th[NS];
+      float th[NS], b2d;
       const float* e = ep + kk * Dp;
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        const bool on = part && held(s);
-        const int i = on ? index(s) : 0;
+        const bool on = part && sl.held(s);
+        const int i = on ? sl.index(s) : 0;
         th[s] = on ? __builtin_fmaf(sc[i], e[i], st[i]) : 0.f;
       }
-#pragma unroll
-      for (int f = 0; f < FP; ++f) L.w1[f] = th[f];
-      L.b1 = th[FP];
-      L.w2d = th[FP + 2] - th[FP + 1];
-      const float b2d = th[FP + 4] - th[FP + 3];
+      const BnnLane<FP> L = bnn_lane<FP>(th, b2d);
       BnnSums<FP> sm;
       sm.clear();
-      if (c.resident) {
-        if (wave_on) bnn_rows<HP, FP, ACT, RR>(L, b2d, xs, ys, n, sm);
-      } else {
-        for (int r0 = 0; r0 < n; r0 += BNN_CHUNK) {
-          const int rows = min(BNN_CHUNK, n - r0);
-          __syncthreads();      // the previous chunk has been consumed
-          bnn_stage<FP>(xs, xp, r0, rows, F);
-          if (threadIdx.x < BNN_CHUNK) ys[threadIdx.x] = ((int)threadIdx.x < rows && yp[r0 + threadIdx.x] > 0.5f) ? 1.f : 0.f;
-          __syncthreads();
-          if (wave_on) bnn_rows<HP, FP, ACT, RR>(L, b2d, xs, ys, rows, sm);
-        }
-      }
+      bnn_data_rows<HP, FP, ACT, RR>(L, b2d, xs, ys, xp, yp, n, F, c.resident, wave_on, sm);
       if (wave_on) {
         float g[NS];      // grad U(theta_k) of the lane's parameters, prior included
 #pragma unroll
@@ -137,8 +103,8 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
         float ql = 0.f;      // the lane's share of |theta|^2 / 2 - |eps|^2 / 2 - sum log scale; (D / 2) log 2 pi of U and of the entropy cancel
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          const bool on = part && owned(s);
-          const int i = on ? index(s) : 0;
+          const bool on = part && sl.owned(s);
+          const int i = on ? sl.index(s) : 0;
           const float ez = e[i];
           ql += on ? 0.5f * (th[s] * th[s] - ez * ez) - sc[Dp + i] : 0.f;
           float sg = on ? g[s] : 0.f, sge = on ? g[s] * ez : 0.f;
@@ -161,8 +127,7 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
     for (int o = HP; o < 64; o <<= 1) al += __shfl_xor(al, o, 64);
     if (lane == 0) lw[wave] = al;
     __syncthreads();
-    // Adam (torch.optim.Adam, no weight decay) on loc and on u, t = absolute step index + 1
-    const float bc1 = (float)(1. - svi_ipow((double)a.beta1, t + 1)), bc2 = (float)(1. - svi_ipow((double)a.beta2, t + 1));
+    const BnnAdam ad = bnn_adam_at(a.lr, a.beta1, a.beta2, a.eps, t);      // Adam on loc and on u
     for (int i = threadIdx.x; i < D; i += blockDim.x) {
       float sg = 0.f, sge = 0.f;
       for (int w = 0; w < waves; ++w) sg += gs[(w * 2) * Dp + i], sge += gs[(w * 2 + 1) * Dp + i];
@@ -171,13 +136,10 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
       const float g_scale = sge * inv_k - 1.f / sc[i];
       const float eu = expf(-fabsf(u));
       const float g_u = g_scale * bnn_sigmoid(u, eu);
-      const float m_loc = a.beta1 * st[2 * Dp + i] + (1.f - a.beta1) * g_loc, v_loc = a.beta2 * st[3 * Dp + i] + (1.f - a.beta2) * g_loc * g_loc;
-      const float m_u = a.beta1 * st[4 * Dp + i] + (1.f - a.beta1) * g_u, v_u = a.beta2 * st[5 * Dp + i] + (1.f - a.beta2) * g_u * g_u;
-      const float u_new = u - a.lr * (m_u / bc1) / (sqrtf(v_u / bc2) + a.eps);
-      st[i] -= a.lr * (m_loc / bc1) / (sqrtf(v_loc / bc2) + a.eps);
-      st[Dp + i] = u_new;
-      st[2 * Dp + i] = m_loc, st[3 * Dp + i] = v_loc, st[4 * Dp + i] = m_u, st[5 * Dp + i] = v_u;
-      const float s = svi_softplus(u_new);
+      const BnnAdamOut nl = bnn_adam(st[i], st[2 * Dp + i], st[3 * Dp + i], g_loc, ad), nu = bnn_adam(u, st[4 * Dp + i], st[5 * Dp + i], g_u, ad);
+      st[i] = nl.p, st[Dp + i] = nu.p;
+      st[2 * Dp + i] = nl.m, st[3 * Dp + i] = nl.v, st[4 * Dp + i] = nu.m, st[5 * Dp + i] = nu.v;
+      const float s = svi_softplus(nu.p);
       sc[i] = s;
       sc[Dp + i] = logf(s);
     }
@@ -194,39 +156,21 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
   }
 }
 
-template <int HP, int FP> int svi_launch_hf(const BnnSviArgs& a, hipStream_t s) {
-  constexpr int CPW = 64 / HP;
-  SviLaunch c;
-  c.waves = std::min(BNN_MAX_WAVES, (a.K + CPW - 1) / CPW);
-  c.Dp = (a.H * (a.F + 3) + 2 + 3) & ~3;
-  c.resident = (long)a.S * (FP + 1) * 4 <= SVI_ROWS_BUDGET;
-  c.cap = c.resident ? a.S : BNN_CHUNK;
-  const size_t bytes = ((size_t)(8 + c.waves * CPW + 2 * c.waves) * c.Dp + 4 + (size_t)c.cap * (FP + 1)) * sizeof(float);
-  static_assert((size_t)(8 + BNN_MAX_WAVES * CPW + 2 * BNN_MAX_WAVES) * (HP * (FP + 3) + 4) * 4 + 16 + SVI_ROWS_BUDGET + BNN_CHUNK * (FP + 1) * 4 <= 160 * 1024, "bnn_svi: LDS");
-  const dim3 grid((unsigned)a.P), block(64 * c.waves);
-  static LdsAllowance allow[2];
-  auto run = [&](auto kernel, LdsAllowance& al) {
-    if (bytes > 64 * 1024) al.ensure(kernel, bytes);
-    kernel<<<grid, block, bytes, s>>>(a, c);
-  };
-  if (a.activation) run(bnn_svi_kernel<HP, FP, 1>, allow[1]);
-  else run(bnn_svi_kernel<HP, FP, 0>, allow[0]);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-}
-
-template <int HP> int svi_launch_h(const BnnSviArgs& a, hipStream_t s) {
-  if (a.F <= 4) return svi_launch_hf<HP, 4>(a, s);
-  if (a.F <= 8) return svi_launch_hf<HP, 8>(a, s);
-  return svi_launch_hf<HP, 16>(a, s);
-}
-
 }  // namespace
 
 int launch_bnn_svi_steps(const BnnSviArgs& a, hipStream_t s) {
-  if (a.H <= 8) return svi_launch_h<8>(a, s);
-  if (a.H <= 16) return svi_launch_h<16>(a, s);
-  if (a.H <= 32) return svi_launch_h<32>(a, s);
-  return svi_launch_h<64>(a, s);
+  return bnn_dispatch(a.H, a.F, a.activation, [&](auto hp, auto fp, auto act) {
+    constexpr int HP = decltype(hp)::value, FP = decltype(fp)::value, ACT = decltype(act)::value, CPW = 64 / HP;
+    SviLaunch c;
+    c.waves = std::min(BNN_MAX_WAVES, (a.K + CPW - 1) / CPW);
+    c.Dp = (a.H * (a.F + 3) + 2 + 3) & ~3;
+    c.resident = (long)a.S * (FP + 1) * 4 <= SVI_ROWS_BUDGET;
+    c.cap = c.resident ? a.S : BNN_CHUNK;
+    const size_t bytes = ((size_t)(8 + c.waves * CPW + 2 * c.waves) * c.Dp + 4 + (size_t)c.cap * (FP + 1)) * sizeof(float);
+    static_assert((size_t)(8 + BNN_MAX_WAVES * CPW + 2 * BNN_MAX_WAVES) * (HP * (FP + 3) + 4) * 4 + 16 + SVI_ROWS_BUDGET + BNN_CHUNK * (FP + 1) * 4 <= 160 * 1024, "bnn_svi: LDS");
+    static LdsAllowance allow;      // one per instantiation
+    return bnn_launch_lds(bnn_svi_kernel<HP, FP, ACT>, allow, dim3((unsigned)a.P), dim3(64 * c.waves), bytes, s, a, c);
+  });
 }
 
 }  // namespace pfn

@@ -1578,12 +1578,29 @@ int pfn_nuts_advance(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int m
 }
 
 // ---- BNN posterior target (bnn_mcmc.hip; ABI 10, additive) ----
-static int bnn_check(int P, int K, int F, int H, int activation, int64_t ld) {      // shapes first: nothing here touches a pointer or HIP
+static int bnn_limits(int F, int H, int activation) {      // what the kernels are built for; the checks come shapes first: nothing here touches a pointer or HIP
   if (F < 1 || F > 16) return fail(PFN_ERR_UNSUPPORTED, "F %d outside 1 .. 16 (a lane keeps its row of W1 in registers)", F);
   if (H < 1 || H > 64) return fail(PFN_ERR_UNSUPPORTED, "H %d outside 1 .. 64 (lane = hidden unit, one wave per chain at most)", H);
   if (activation < 0 || activation > 1) return fail(PFN_ERR_UNSUPPORTED, "activation %d (0 identity, 1 tanh)", activation);
+  return PFN_OK;
+}
+static int bnn_batch(int P, int K, int F, int H, int64_t ld) {      // K parameter vectors of D numbers, ld apart, for each of P problems
   if (P < 1 || K < 1 || (int64_t)P * K > 0x7fffffff) return fail(PFN_ERR_ARGUMENT, "P %d x K %d chains: need P >= 1, K >= 1, P K < 2^31", P, K);
   if (ld < (int64_t)H * (F + 3) + 2) return fail(PFN_ERR_ARGUMENT, "ld %lld < D = H (F + 3) + 2 = %d", (long long)ld, H * (F + 3) + 2);
+  return PFN_OK;
+}
+static int bnn_check(int P, int K, int F, int H, int activation, int64_t ld) {
+  if (int rc = bnn_limits(F, H, activation)) return rc;
+  return bnn_batch(P, K, F, H, ld);
+}
+// what the two step loops (SVI, SVGD) ask of their common arguments, after the limits: the problem and step counts and the pointers, ld, Adam's numbers
+static int bnn_steps_check(const char* fn, int P, int S, int F, int H, int64_t ld, int64_t step0, int num_steps, const void* x, const void* y, const void* state, float lr,
+                           float beta1, float beta2, float eps) {
+  if (P < 1 || S < 1 || step0 < 0 || num_steps < 0 || !x || !y || !state)
+    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (P %d >= 1, S %d >= 1, step0 %lld >= 0, num_steps %d >= 0, x, y, state not NULL)", fn, P, S, (long long)step0, num_steps);
+  if (int rc = bnn_batch(P, 1, F, H, ld)) return rc;      // ld >= D
+  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
+    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (lr %g >= 0, beta1 %g and beta2 %g in [0, 1), eps %g >= 0)", fn, lr, beta1, beta2, eps);
   return PFN_OK;
 }
 int pfn_bnn_logp_grad(const float* x, const float* y, const int32_t* n_of, const float* theta, int64_t ld, int P, int K, int S, int F, int H, int activation,
@@ -1608,14 +1625,11 @@ int pfn_bnn_predict(const float* x_test, const float* theta, int64_t ld, int P, 
 // ---- SVI on the BNN (bnn_svi.hip; ABI 10, additive) ----
 int pfn_bnn_svi_steps(const float* x, const float* y, const int32_t* n_of, float* state, int64_t ld, int P, int S, int F, int H, int activation, int num_particles,
                       int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, uint64_t seed, const int64_t* problem_ids, float* loss, void* stream) {
-  if (int rc = bnn_check(P, 1, F, H, activation, ld)) return rc;      // F, H, activation, P >= 1 and ld >= D: nothing here touches a pointer or HIP
-  if (num_particles < 1 || step0 < 0 || num_steps < 0 || S < 1 || !x || !y || !state)
-    return fail(PFN_ERR_ARGUMENT, "bad bnn_svi_steps arguments (num_particles %d >= 1, step0 %lld >= 0, num_steps %d >= 0, S %d >= 1, x, y, state not NULL)", num_particles,
-                (long long)step0, num_steps, S);
+  if (int rc = bnn_limits(F, H, activation)) return rc;
+  if (int rc = bnn_steps_check("bnn_svi_steps", P, S, F, H, ld, step0, num_steps, x, y, state, lr, beta1, beta2, eps)) return rc;
+  if (num_particles < 1) return fail(PFN_ERR_ARGUMENT, "bad bnn_svi_steps arguments (num_particles %d >= 1)", num_particles);
   if (step0 > (int64_t)1 << 40 || (step0 + num_steps + 1) * (int64_t)num_particles >= (int64_t)1 << 53)
     return fail(PFN_ERR_ARGUMENT, "step0 %lld must not exceed 2^40 and (step0 + num_steps + 1) num_particles must stay below 2^53 (the Philox counter of a particle's noise)", (long long)step0);
-  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
-    return fail(PFN_ERR_ARGUMENT, "bad bnn_svi_steps arguments (lr %g >= 0, beta1 %g and beta2 %g in [0, 1), eps %g >= 0)", lr, beta1, beta2, eps);
   if (num_steps == 0) return PFN_OK;
   BnnSviArgs a{};
   a.x = x; a.y = y; a.n_of = n_of; a.state = state; a.ld = ld; a.P = P; a.S = S; a.F = F; a.H = H; a.activation = activation; a.K = num_particles; a.step0 = step0;
@@ -1626,7 +1640,7 @@ int pfn_bnn_svi_steps(const float* x, const float* y, const int32_t* n_of, float
 
 // ---- SVGD on the BNN (bnn_svgd.hip; ABI 10, additive) ----
 static int bnn_svgd_limits(int F, int H, int activation, int N) {      // what the kernel is built for: nothing here touches a pointer or HIP
-  if (int rc = bnn_check(1, 1, F, H, activation, (int64_t)1 << 40)) return rc;
+  if (int rc = bnn_limits(F, H, activation)) return rc;
   if (N < 2 || N > PFN_BNN_SVGD_MAX_PARTICLES)
     return fail(PFN_ERR_UNSUPPORTED, "num_particles %d outside 2 .. %d (lane = particle in the Stein step; the median needs a pair)", N, PFN_BNN_SVGD_MAX_PARTICLES);
   return PFN_OK;
@@ -1639,14 +1653,9 @@ int pfn_bnn_svgd_steps(const float* x, const float* y, const int32_t* n_of, floa
                        int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, float bandwidth_factor, void* workspace,
                        int64_t workspace_bytes, float* potential, float* bandwidth, void* stream) {
   if (int rc = bnn_svgd_limits(F, H, activation, num_particles)) return rc;
+  if (int rc = bnn_steps_check("bnn_svgd_steps", P, S, F, H, ld, step0, num_steps, x, y, state, lr, beta1, beta2, eps)) return rc;
+  if (!(lr <= 3.4e38f) || !(bandwidth_factor > 0.f)) return fail(PFN_ERR_ARGUMENT, "bad bnn_svgd_steps arguments (lr %g finite, bandwidth_factor %g > 0)", lr, bandwidth_factor);
   const int D = H * (F + 3) + 2;
-  if (P < 1 || S < 1 || step0 < 0 || num_steps < 0 || !x || !y || !state)
-    return fail(PFN_ERR_ARGUMENT, "bad bnn_svgd_steps arguments (P %d >= 1, S %d >= 1, step0 %lld >= 0, num_steps %d >= 0, x, y, state not NULL)", P, S, (long long)step0,
-                num_steps);
-  if (ld < D) return fail(PFN_ERR_ARGUMENT, "ld %lld < D = H (F + 3) + 2 = %d", (long long)ld, D);
-  if (!(lr >= 0.f && lr <= 3.4e38f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) || !(bandwidth_factor > 0.f))
-    return fail(PFN_ERR_ARGUMENT, "bad bnn_svgd_steps arguments (lr %g >= 0 and finite, beta1 %g and beta2 %g in [0, 1), eps %g >= 0, bandwidth_factor %g > 0)", lr, beta1,
-                beta2, eps, bandwidth_factor);
   const int64_t need = bnn_svgd_workspace_bytes(P, num_particles, D);
   if (workspace_bytes < need || (need > 0 && !workspace))
     return fail(PFN_ERR_ARGUMENT, "workspace_bytes %lld < pfn_bnn_svgd_workspace_bytes = %lld (or a NULL workspace)", (long long)workspace_bytes, (long long)need);

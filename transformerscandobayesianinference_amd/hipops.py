@@ -316,6 +316,16 @@ def bnn_num_params(F, H):
     return int(H) * (int(F) + 3) + 2
 
 
+def _bnn_f32(x, *tensors):
+    """The tensor checks of the bnn_* wrappers, written once: x and every given tensor is f32, contiguous and on x's device."""
+    for t in (x,) + tensors:
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
+
+
+def _bnn_n_of(n_of, P, x):
+    assert n_of is None or (n_of.dtype == torch.int32 and n_of.shape == (P,) and n_of.is_contiguous() and n_of.device == x.device), 'n_of [P] int32'
+
+
 def bnn_logp_grad(x, y, theta, H, K=None, n_of=None, activation=0, want_grad=True, value=None, grad=None):
     """Potential and gradient of the two-layer BNN for every chain (pfn_bnn_logp_grad).  x [P,S,F], y [P,S], theta [P K, ld >= D] contiguous f32 on the GPU,
     n_of [P] int32 or None; chain c belongs to problem c // K (K defaults to theta.shape[0] // P).  Returns (value [P K], grad [P K, ld] or None); only the
@@ -325,17 +335,15 @@ def bnn_logp_grad(x, y, theta, H, K=None, n_of=None, activation=0, want_grad=Tru
     C, ld = theta.shape
     K = C // P if K is None else int(K)
     assert C == P * K and y.shape == (P, S), 'theta [P K, ld], y [P, S]'
-    for t in (x, y, theta):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
-    if n_of is not None:
-        assert n_of.dtype == torch.int32 and n_of.shape == (P,) and n_of.is_contiguous() and n_of.device == x.device
+    _bnn_f32(x, y, theta)
+    _bnn_n_of(n_of, P, x)
     value = torch.empty(C, dtype=torch.float32, device=x.device) if value is None else value
     if want_grad and grad is None:
         grad = torch.zeros(C, ld, dtype=torch.float32, device=x.device)
     if not want_grad:
         grad = None
-    assert value.shape == (C,) and value.dtype == torch.float32 and value.is_contiguous() and value.device == x.device
-    assert grad is None or (grad.shape == (C, ld) and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == x.device)
+    assert value.shape == (C,) and (grad is None or grad.shape == (C, ld))
+    _bnn_f32(x, value, *(() if grad is None else (grad,)))
     _hip.check(_hip.lib().pfn_bnn_logp_grad(x.data_ptr(), y.data_ptr(), _hip.ptr(n_of), theta.data_ptr(), ld, P, K, S, F, int(H), BNN_ACTIVATIONS[activation],
                                             value.data_ptr(), _hip.ptr(grad), _hip.stream_ptr(x.device)), 'pfn_bnn_logp_grad')
     return value, grad
@@ -348,8 +356,7 @@ def bnn_predict(x_test, theta, H, K=None, activation=0):
     C, ld = theta.shape
     K = C // P if K is None else int(K)
     assert C == P * K, 'theta [P K, ld]'
-    for t in (x_test, theta):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x_test.device
+    _bnn_f32(x_test, theta)
     prob1 = torch.empty(C, m, dtype=torch.float32, device=x_test.device)
     _hip.check(_hip.lib().pfn_bnn_predict(x_test.data_ptr(), theta.data_ptr(), ld, P, K, m, F, int(H), BNN_ACTIVATIONS[activation], prob1.data_ptr(),
                                           _hip.stream_ptr(x_test.device)), 'pfn_bnn_predict')
@@ -384,15 +391,14 @@ def bnn_svi_steps(x, y, state, H, num_steps, step0=0, num_particles=1, lr=1e-3, 
     num_steps, step0, K = int(num_steps), int(step0), int(num_particles)
     assert state.dim() == 3 and state.shape[:2] == (P, 6) and y.shape == (P, S), 'state [P, 6, ld], y [P, S]'
     ld = state.shape[2]
-    for t in (x, y, state):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
-    if n_of is not None:
-        assert n_of.dtype == torch.int32 and n_of.shape == (P,) and n_of.is_contiguous() and n_of.device == x.device
+    _bnn_f32(x, y, state)
+    _bnn_n_of(n_of, P, x)
     if problem_ids is not None:
         assert problem_ids.dtype == torch.int64 and problem_ids.shape == (P,) and problem_ids.is_contiguous() and problem_ids.device == x.device
     if loss is None:
         loss = torch.empty(P, max(num_steps, 0), dtype=torch.float32, device=x.device)
-    assert loss.shape == (P, num_steps) and loss.dtype == torch.float32 and loss.is_contiguous() and loss.device == x.device
+    assert loss.shape == (P, num_steps)
+    _bnn_f32(x, loss)
     _hip.check(_hip.lib().pfn_bnn_svi_steps(x.data_ptr(), y.data_ptr(), _hip.ptr(n_of), state.data_ptr(), ld, P, S, F, int(H), BNN_ACTIVATIONS[activation], K, step0,
                                             num_steps, float(lr), float(betas[0]), float(betas[1]), float(eps), int(seed), _hip.ptr(problem_ids), loss.data_ptr(),
                                             _hip.stream_ptr(x.device)), 'pfn_bnn_svi_steps')
@@ -426,16 +432,14 @@ def bnn_svgd_steps(x, y, state, H, num_steps, step0=0, lr=1e-3, betas=(0.9, 0.99
     num_steps, step0 = int(num_steps), int(step0)
     assert state.dim() == 4 and state.shape[:2] == (P, 3) and y.shape == (P, S), 'state [P, 3, N, ld], y [P, S]'
     N, ld = state.shape[2], state.shape[3]
-    for t in (x, y, state):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device
-    if n_of is not None:
-        assert n_of.dtype == torch.int32 and n_of.shape == (P,) and n_of.is_contiguous() and n_of.device == x.device
+    _bnn_f32(x, y, state)
+    _bnn_n_of(n_of, P, x)
     if potential is None:
         potential = torch.empty(P, max(num_steps, 0), dtype=torch.float32, device=x.device)
     if bandwidth is None:
         bandwidth = torch.zeros(P, ld, dtype=torch.float32, device=x.device)
-    assert potential.shape == (P, num_steps) and potential.dtype == torch.float32 and potential.is_contiguous() and potential.device == x.device
-    assert bandwidth.shape == (P, ld) and bandwidth.dtype == torch.float32 and bandwidth.is_contiguous() and bandwidth.device == x.device
+    assert potential.shape == (P, num_steps) and bandwidth.shape == (P, ld)
+    _bnn_f32(x, potential, bandwidth)
     lib = _hip.lib()
     ws_bytes = int(lib.pfn_bnn_svgd_workspace_bytes(P, N, F, int(H)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes > 0 else None      # negative (bad shapes): the call below names what is wrong

@@ -175,6 +175,38 @@ def eval_transformer(X, y, device, model, training_samples_n):
     return acc, nll, elapsed
 
 
+def _bnn_problem(x, y, model_spec, n_of, activation, max_dim=None):
+    """The prologue of the three fits: x [P, S, F], y [P, S] as contiguous f32 on x's GPU, n_of as [P] int32 there (or None).  Returns
+    (activation name, F, H, D, x, y, P, n_of).  A D above `max_dim` is refused first, with the limit named."""
+    activation = _activation_name(activation)
+    F, H = int(model_spec['num_features']), int(model_spec['embed'])
+    D = hipops.bnn_num_params(F, H)
+    if max_dim is not None and D > max_dim:
+        raise ValueError(f'this BNN has D = H (F + 3) + 2 = {D} parameters; the batched sampler takes at most {max_dim} per chain '
+                         f'(mcmc.batched_nuts), i.e. embed <= {(max_dim - 2) // (F + 3)} for num_features = {F}')
+    hipops._hip.require_gpu_tensor(x, 'x')
+    x, y = x.float().contiguous(), y.to(x.device).float().contiguous()
+    P, S, _ = x.shape
+    assert x.shape[2] == F and y.shape == (P, S)
+    if n_of is not None:
+        n_of = torch.as_tensor(n_of, dtype=torch.int32, device=x.device).contiguous()
+    return activation, F, H, D, x, y, P, n_of
+
+
+def _split(X, y, device, n):
+    """X [P, T, F], y [P, T] on `device` as f32, split after the first n rows: (X_train, y_train, X_test, y_test), each contiguous."""
+    X, y, n = X.to(device).float(), y.to(device).float(), int(n)
+    return X[:, :n].contiguous(), y[:, :n].contiguous(), X[:, n:].contiguous(), y[:, n:].contiguous()
+
+
+def _predictive(theta, x_test, spec, activation):
+    """Class-1 probability of the parameter vectors theta [P, N, D] at x_test [P, m, F]: prob1 [P, N, m] (pfn_bnn_predict)."""
+    P, N, D = theta.shape
+    x_test = x_test.to(theta.device).float().contiguous()
+    assert x_test.shape[0] == P and x_test.shape[2] == spec['num_features']
+    return hipops.bnn_predict(x_test, theta.reshape(P * N, D).contiguous(), spec['embed'], K=N, activation=activation).view(P, N, x_test.shape[1])
+
+
 class BnnPosterior:
     """NUTS draws of the BNN's weights for P problems: samples [P, K, N, D] in the layout of BayesianModel.pack, stats [P, K, W+N, 8] (mcmc.batched_nuts)."""
 
@@ -184,29 +216,15 @@ class BnnPosterior:
     def predictive(self, x_test):
         """Class-1 probability of every draw at x_test [P, m, F]: prob1 [P, K N, m] (pfn_bnn_predict)."""
         P, K, N, D = self.samples.shape
-        x_test = x_test.to(self.samples.device).float().contiguous()
-        assert x_test.shape[0] == P and x_test.shape[2] == self.model_spec['num_features']
-        prob1 = hipops.bnn_predict(x_test, self.samples.reshape(P * K * N, D), self.model_spec['embed'], K=K * N, activation=self.activation)
-        return prob1.view(P, K * N, x_test.shape[1])
+        return _predictive(self.samples.reshape(P, K * N, D), x_test, self.model_spec, self.activation)
 
 
 def sample_bnn_posterior(x, y, model_spec, n_of=None, num_samples=100, warmup_steps=100, num_chains=1, seed=0, activation='identity', **nuts_kwargs):
     """NUTS on the weights of the BNN given x [P, S, F], y [P, S] (class = y > 0.5; problem p uses its first n_of[p] rows, all when None): every one of the
     P num_chains chains advances in the same pass of mcmc.batched_nuts, one pfn_bnn_logp_grad launch per pass.  Start points ~ N(0, I) from `seed`.
     Returns a BnnPosterior."""
-    activation = _activation_name(activation)
-    F, H = int(model_spec['num_features']), int(model_spec['embed'])
-    D = hipops.bnn_num_params(F, H)
-    if D > MAX_SAMPLED_DIM:
-        raise ValueError(f'this BNN has D = H (F + 3) + 2 = {D} parameters; the batched sampler takes at most {MAX_SAMPLED_DIM} per chain '
-                         f'(mcmc.batched_nuts), i.e. embed <= {(MAX_SAMPLED_DIM - 2) // (F + 3)} for num_features = {F}')
-    hipops._hip.require_gpu_tensor(x, 'x')
-    x, y = x.float().contiguous(), y.to(x.device).float().contiguous()
-    P, S, _ = x.shape
-    assert x.shape[2] == F and y.shape == (P, S)
+    activation, F, H, D, x, y, P, n_of = _bnn_problem(x, y, model_spec, n_of, activation, max_dim=MAX_SAMPLED_DIM)
     K = int(num_chains)
-    if n_of is not None:
-        n_of = torch.as_tensor(n_of, dtype=torch.int32, device=x.device).contiguous()
     theta0 = torch.randn(P * K, D, generator=torch.Generator(device=x.device).manual_seed(int(seed)), device=x.device)
     value = torch.empty(P * K, device=x.device)
     grad = torch.empty(P * K, D, device=x.device)
@@ -243,9 +261,7 @@ def eval_mcmc(X, y, device, model_spec, training_samples_n, warmup_steps, num_pr
     (nll [P], acc [P]) as numpy arrays (reference :249-267, one dataset at a time there).  By default the prediction is the mean class-1 probability over
     the draws (Rao-Blackwellised); sample_obs=True is the reference's estimator: Bernoulli observations per draw, the mean hard prediction, BCELoss."""
     spec, activation = _spec_of(model_spec)
-    X, y = X.to(device).float(), y.to(device).float()
-    n = int(training_samples_n)
-    X_train, y_train, X_test, y_test = X[:, :n].contiguous(), y[:, :n].contiguous(), X[:, n:].contiguous(), y[:, n:].contiguous()
+    X_train, y_train, X_test, y_test = _split(X, y, device, training_samples_n)
     post = sample_bnn_posterior(X_train, y_train, spec, num_samples=num_pred_samples, warmup_steps=warmup_steps, num_chains=1, seed=seed, activation=activation)
     prob1 = post.predictive(X_test)      # [P, N, m]
     return _score(prob1, y_test, sample_obs, seed)
@@ -267,12 +283,7 @@ class BnnGuide:
 
     def predictive(self, x_test, num_samples, seed=0):
         """Class-1 probability of `num_samples` draws from the guide at x_test [P, m, F]: prob1 [P, N, m] (pfn_bnn_predict)."""
-        P, D = self.loc.shape
-        N = int(num_samples)
-        x_test = x_test.to(self.loc.device).float().contiguous()
-        assert x_test.shape[0] == P and x_test.shape[2] == self.model_spec['num_features']
-        theta = self.sample(N, seed).reshape(P * N, D).contiguous()
-        return hipops.bnn_predict(x_test, theta, self.model_spec['embed'], K=N, activation=self.activation).view(P, N, x_test.shape[1])
+        return _predictive(self.sample(int(num_samples), seed), x_test, self.model_spec, self.activation)
 
 
 def fit_bnn_svi(x, y, model_spec, n_of=None, num_steps=1024, lr=1e-3, num_particles=1, seed=0, activation='identity', init_scale=0.1, steps_per_launch=256):
@@ -280,16 +291,8 @@ def fit_bnn_svi(x, y, model_spec, n_of=None, num_steps=1024, lr=1e-3, num_partic
     Gaussian guide per problem, `num_steps` Adam steps on the `num_particles`-particle ELBO, every problem in the same launches (hipops.bnn_svi_steps).
     The initial loc is the median of 15 N(0, 1) draws per coordinate from `seed` (pyro's init_to_median for this prior), the initial scale `init_scale`.
     `steps_per_launch` only bounds the length of one launch: the result does not depend on it, bit for bit.  Returns a BnnGuide."""
-    activation = _activation_name(activation)
-    F, H = int(model_spec['num_features']), int(model_spec['embed'])
-    D = hipops.bnn_num_params(F, H)
-    hipops._hip.require_gpu_tensor(x, 'x')
-    x, y = x.float().contiguous(), y.to(x.device).float().contiguous()
-    P, S, _ = x.shape
-    assert x.shape[2] == F and y.shape == (P, S)
+    activation, F, H, D, x, y, P, n_of = _bnn_problem(x, y, model_spec, n_of, activation)
     num_steps, per = int(num_steps), max(int(steps_per_launch), 1)
-    if n_of is not None:
-        n_of = torch.as_tensor(n_of, dtype=torch.int32, device=x.device).contiguous()
     loc0 = torch.randn(15, P, D, generator=torch.Generator(device=x.device).manual_seed(int(seed)), device=x.device).median(0).values
     state = hipops.bnn_svi_state(P, F, H, x.device, loc0=loc0, init_scale=init_scale)
     losses = torch.empty(P, num_steps, device=x.device)
@@ -314,9 +317,7 @@ def eval_svi(X, y, device, model_sampler, training_samples_n, num_train_steps, n
                                   'training_samples_n, num_train_steps)')
     _require_gpu(device, 'eval_svi')
     spec, activation = _spec_of(model_sampler)
-    X, y = X.to(device).float(), y.to(device).float()
-    n = int(training_samples_n)
-    X_train, y_train, X_test, y_test = X[:, :n].contiguous(), y[:, :n].contiguous(), X[:, n:].contiguous(), y[:, n:].contiguous()
+    X_train, y_train, X_test, y_test = _split(X, y, device, training_samples_n)
     guide = fit_bnn_svi(X_train, y_train, spec, num_steps=num_train_steps, lr=lr, num_particles=num_particles, seed=seed, activation=activation)
     prob1 = guide.predictive(X_test, num_pred_samples, seed=seed)      # [P, N, m]
     return _score(prob1, y_test, sample_obs, seed)
@@ -332,11 +333,7 @@ class BnnParticles:
 
     def predictive(self, x_test):
         """Class-1 probability of every particle at x_test [P, m, F]: prob1 [P, N, m] (pfn_bnn_predict)."""
-        P, N, D = self.particles.shape
-        x_test = x_test.to(self.particles.device).float().contiguous()
-        assert x_test.shape[0] == P and x_test.shape[2] == self.model_spec['num_features']
-        theta = self.particles.reshape(P * N, D).contiguous()
-        return hipops.bnn_predict(x_test, theta, self.model_spec['embed'], K=N, activation=self.activation).view(P, N, x_test.shape[1])
+        return _predictive(self.particles, x_test, self.model_spec, self.activation)
 
 
 def fit_bnn_svgd(x, y, model_spec, n_of=None, num_steps=1024, lr=1e-3, num_particles=50, seed=0, activation='identity', bandwidth_factor=1.0, steps_per_launch=256):
@@ -344,16 +341,8 @@ def fit_bnn_svgd(x, y, model_spec, n_of=None, num_steps=1024, lr=1e-3, num_parti
     particles per problem, `num_steps` Stein steps with Adam, every problem in the same launches (hipops.bnn_svgd_steps).  Every coordinate of every initial
     particle is the median of 15 N(0, 1) draws from `seed` (pyro's init_to_median under the particle plate).  `steps_per_launch` only bounds the length of one
     launch: the result does not depend on it, bit for bit.  Returns BnnParticles."""
-    activation = _activation_name(activation)
-    F, H = int(model_spec['num_features']), int(model_spec['embed'])
-    D = hipops.bnn_num_params(F, H)
-    hipops._hip.require_gpu_tensor(x, 'x')
-    x, y = x.float().contiguous(), y.to(x.device).float().contiguous()
-    P, S, _ = x.shape
-    assert x.shape[2] == F and y.shape == (P, S)
+    activation, F, H, D, x, y, P, n_of = _bnn_problem(x, y, model_spec, n_of, activation)
     N, num_steps, per = int(num_particles), int(num_steps), max(int(steps_per_launch), 1)
-    if n_of is not None:
-        n_of = torch.as_tensor(n_of, dtype=torch.int32, device=x.device).contiguous()
     draws = torch.randn(15, P, N, D, generator=torch.Generator().manual_seed(int(seed)))      # on the host: the start does not depend on the device
     state = hipops.bnn_svgd_state(P, N, F, H, x.device, particles0=draws.median(0).values)
     potentials = torch.empty(P, num_steps, device=x.device)
@@ -370,9 +359,7 @@ def eval_svgd(X, y, device, model_sampler, training_samples_n, num_train_steps, 
     eval_mcmc's: the mean class-1 probability by default, sample_obs=True for the reference's sampled observations."""
     _require_gpu(device, 'eval_svgd', 'the Stein step kernel (pfn_bnn_svgd_steps) runs on the GPU only, like the ELBO step kernel; no CPU fallback')
     spec, activation = _spec_of(model_sampler)
-    X, y = X.to(device).float(), y.to(device).float()
-    n = int(training_samples_n)
-    X_train, y_train, X_test, y_test = X[:, :n].contiguous(), y[:, :n].contiguous(), X[:, n:].contiguous(), y[:, n:].contiguous()
+    X_train, y_train, X_test, y_test = _split(X, y, device, training_samples_n)
     fit = fit_bnn_svgd(X_train, y_train, spec, num_steps=num_train_steps, lr=lr, num_particles=num_particles, seed=seed, activation=activation)
     return _score(fit.predictive(X_test), y_test, sample_obs, seed)
 

@@ -74,29 +74,224 @@ def dropout_keep_mask(site_seed, rows, cols, p):
     return torch.from_numpy(h >= np.uint64(thr))
 
 
-def forward(sd, x, y, sep, nhead, dtype=torch.float64, return_hidden=False, dropout=None):
+# ---- operand rounding of the 16-bit HIP stack, emulated on the f64 graph (forward(..., rounding=Rounding(...))) ----------------------
+# pfn_model_desc.schedule bits (include/pfn_hip.h; the values of transformerscandobayesianinference_amd/_hip.py, pinned by tests/test_host_rounded_oracle.py)
+SCHED_TOP_LAYER_ALL_ROWS, SCHED_FUSE_LN_WIDE, SCHED_SEPARATE_LNBWD, SCHED_DETERMINISTIC, SCHED_NO_KEY_CENTERING, SCHED_FUSE_Q_PROJECTION, SCHED_KEY_CENTERING, SCHED_F32_RESIDUAL = 1, 2, 4, 8, 16, 32, 64, 128
+UNIT_ROUNDOFF = {'bf16': 2.0 ** -9, 'fp16': 2.0 ** -12}
+
+# Where the HIP stack stores a tensor in operand precision.  kind: 'R' = the value in the forward AND the incoming gradient in the backward are stored rounded;
+# 'Rg' = the forward value stays f32 (or is never stored), the gradient is stored rounded; 'Rv' = the value is rounded, its gradient is never stored in 16 bits
+# (weights: f32 out of the weight-gradient GEMMs; operand copies: the gradient is rounded at another site).  when: the plan predicate (Rounding.plan) that
+# switches the site, None = every 16-bit pass.  Lines: transformerscandobayesianinference_amd/csrc/pfn_api.hip unless a file is named.
+ROUNDING_SITES = {
+    # name        kind  when           what is stored, and where
+    'W':         ('Rv', None,          'the operand copies of every weight matrix: pfn_prepare_params launch_cast_params :696 (biases, LayerNorm weights: f32 `params + ...`)'),
+    'X':         ('Rv', None,          'GEMM A operands cut from f32 rows: x0_t embed_fwd :769, x1_t / x2_t layer_tail_forward :399 :411 :427 :440, xt_t :859-861'),
+    'xaug':      ('Rv', 'emb_t',       'the embedding weight gradient reads x | y from xaug_t :770-771 -> launch_gemm_tn :1328 (the forward embeds the f32 inputs)'),
+    'emb_grad':  ('Rg', 'emb_t',       'd(src) leaves layer 0 in gA_t: layer_backward_dx out_f32 = (l == 0 && !emb_t) :1313'),
+    'qkv':       ('R',  None,          'q|k|v projection out_t = a.qkv :799 (keys after the f32 shift, EPI_ROWSHIFT :807); gradient at.dqkv = a.dqkv_t :1303'),
+    'P':         ('Rv', None,          'softmax numerators enter P.V and dO^T.P as MFMA operands: attention.hip :13-14 ("P and dS go from the accumulator straight into the operand slots" :791)'),
+    'dS':        ('Rg', None,          'dS = P (dP - delta) in operand precision, the values dK, dQ consume: attention.hip :790-792'),
+    'ctx':       ('R',  None,          'attention output at.ctx = a.ctx :821; its gradient d(ctx) out_t = dctx_t / top_dctx_t :1270-1271'),
+    'y_grad':    ('Rg', None,          'LayerNorm-input gradients dy2_t :551 :534, dy1_t :530 :570 (launch_layernorm_bwd dx_t / GemmLNB::dx_t)'),
+    'Y':         ('Rv', 'y16',         'pre-LayerNorm sums in fp16 inside the fused GEMMs, g.y16 :399 :427: the next residual add and the LayerNorm backward read the rounded sum'),
+    'Yu':        ('Rv', 'y16u',        'fp16 sums ahead of a separate LayerNorm: EPI_RESID_T | EPI_OUT_T :407 :435 -- residual from the operand copy, the rounded sum is what is normalised'),
+    'x1_grad':   ('Rg', 'not fuse_lnb', 'dx1 = dh . W1 + dy2 out_t = dx1_t :566-567 (fused: the sum stays in the epilogue of gemm_nt_lnbwd_kernel :563)'),
+    'out_grad':  ('Rg', 'per layer',   'gradient of a layer output in gA_t: the top layer by launch_scatter_test_rows :1208-1209 unless it runs on the test rows (dxt f32 :1225), '
+                                       'lower layers by layer_backward_dx EPI_OUT_T :584-585 unless fuse_lnb (:582)'),
+    'act':       ('Rv', None,          'GELU output u.h :416, decoder dt :450'),
+    'dgelu':     ('Rv', None,          'the stored GELU derivative out2_t = u.hpre :416, dpre :450, multiplied in EPI_GELU_BWD :557 :462'),
+    'pre_grad':  ('Rg', None,          'd(pre-activation) dh_t :558, dd_t :463'),
+    'dlog':      ('Rg', None,          'dlogits cast to dlog_t: launch_cast_rows :1190 (times the loss scale in fp16)'),
+    'drop_grad': ('Rg', 'dropout',     'masked copies of the LayerNorm-input gradients dy2m_t :554, dy1m_t :1267 (launch_dropout_scale writes operand precision)'),
+    'center':    (None, 'center',      'not a rounding, but it decides what K rounds: the keys leave the projection centred per dataset, launch_key_shift :805-807 (key_centering :161)'),
+    'drop_act':  ('Rv', 'dropout',    'the FFN dropout rescales h and hpre in place in operand precision: launch_dropout_scale :419'),
+}
+
+
+class _StraightThrough(torch.autograd.Function):
+    """value -> rnd(value) if fwd else value; gradient -> rnd(gradient) if bwd else gradient"""
+    @staticmethod
+    def forward(ctx, t, rnd, fwd, bwd):
+        ctx.rnd = rnd if bwd else None
+        return rnd(t) if fwd else t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.rnd(g) if ctx.rnd is not None else g), None, None, None
+
+
+class _GeluStoredDerivative(torch.autograd.Function):
+    """_gelu as the stack keeps it: the output rounded (site 'act'), the backward a product with the STORED derivative (site 'dgelu'); keep = the FFN dropout's
+    mask times 1 / (1 - p), which rescales both in place in operand precision (site 'drop_act')"""
+    @staticmethod
+    def forward(ctx, x, rnd, keep):
+        with torch.enable_grad():
+            xd = x.detach().requires_grad_(True)
+            out = _gelu(xd)
+            d, = torch.autograd.grad(out.sum(), xd)
+        out, d = rnd(out.detach()), rnd(d)
+        if keep is not None:
+            out, d = rnd(out * keep), rnd(d * keep)
+        ctx.save_for_backward(d)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.saved_tensors[0], None, None
+
+
+class Rounding:
+    """The rounding hook of `forward` / `loss_and_grads`: fmt 'bf16' | 'fp16' | None (None: every site is the identity, but the graph is the hooked one --
+    tests/test_host_rounded_oracle.py compares it with the plain oracle), schedule = the model's PFN_SCHED_* bits.  top_rows overrides the top-layer rule
+    (a ragged batch decides it from its smallest eval position, pfn_api.hip top_layer_on_test_rows_ragged)."""
+    def __init__(self, fmt, schedule=0, top_rows=None):
+        assert fmt in (None, 'bf16', 'fp16')
+        self.fmt, self.schedule, self.top_rows = fmt, schedule, top_rows
+
+    def round(self, t):
+        if self.fmt is None:
+            return t
+        if self.fmt == 'bf16':
+            return t.to(torch.bfloat16).to(t.dtype)
+        return t.clamp(-65504.0, 65504.0).to(torch.float16).to(t.dtype)      # (saturating stores: pfn_device.h operand_store_mode)
+
+    def R(self, t):
+        return _StraightThrough.apply(t, self.round, True, True)
+
+    def Rg(self, t):
+        return _StraightThrough.apply(t, self.round, False, True)
+
+    def Rv(self, t):
+        return _StraightThrough.apply(t, self.round, True, False)
+
+    def plan(self, E, nhead, nhid, nlayers, T, sep, pdrop):
+        """The predicates of pfn_api.hip make_plan / residual16 / residual16_separate_ln / lnbwd_fusable / top_layer_on_test_rows / key_centering / emb_gemm for a
+        16-bit descriptor whose buffers are 16-byte aligned (the workspace's are: carve() aligns to 256) and num_features + 2 <= 128 (emb_aug_width > 0)."""
+        sch, fp16 = self.schedule, self.fmt == 'fp16'
+        width_ok = E <= 512 or bool(sch & SCHED_FUSE_LN_WIDE)
+        ln_ok = E in (128, 256, 512, 1024)                                   # gemm_ln_supported (gemm.hip) on the probe's K = E
+        ln_fusable = ln_ok and nhid % 32 == 0 and width_ok
+        pl = dict(fuse_ln=ln_fusable and pdrop == 0)
+        pl['y16'] = (fp16 and not sch & SCHED_F32_RESIDUAL and nlayers > 0 and pdrop == 0 and nhid % 32 == 0 and
+                     (E in (128, 256, 512) or (E == 1024 and bool(sch & SCHED_FUSE_LN_WIDE))) and ln_ok)
+        pl['y16u'] = fp16 and not sch & SCHED_F32_RESIDUAL and nlayers > 0 and pdrop == 0 and E >= 1024 and not ln_fusable
+        pl['fuse_lnb'] = (not sch & SCHED_DETERMINISTIC and not sch & SCHED_SEPARATE_LNBWD and nlayers > 0 and pdrop == 0 and width_ok and
+                          ln_ok and nhid % 32 == 0)                          # gemm_lnbwd_supported: N = E, K = nhid and 3 E
+        top = not sch & SCHED_TOP_LAYER_ALL_ROWS and nlayers > 0 and pdrop == 0 and sep < T and 4 * sep >= T
+        pl['top_rows'] = top if self.top_rows is None else (self.top_rows and nlayers > 0)
+        pl['center'] = ((fp16 and not sch & SCHED_NO_KEY_CENTERING) or (self.fmt == 'bf16' and bool(sch & SCHED_KEY_CENTERING))) and E % 64 == 0
+        pl['emb_t'] = nlayers > 0
+        pl['dropout'] = pdrop > 0
+        pl['nlayers'] = nlayers
+        return pl
+
+
+class _NoSites:
+    """the plain oracle: every site is the identity, every helper the plain function"""
+    def on(self, name, layer=None):
+        return False
+
+    def __call__(self, name, t, layer=None):
+        return t
+
+    def linear_grad_operand(self, x, w, b):
+        return _linear(x, w, b)
+
+    def softmax(self, scores):
+        return torch.softmax(scores, -1)
+
+    def gelu(self, x, keep=None):
+        return _gelu(x) if keep is None else _gelu(x) * keep
+
+    def layer_norm(self, v, w, b, grad_site, layer=None):
+        o = _layer_norm(v, w, b)
+        return o, o
+
+
+class _Sites(_NoSites):
+    """ROUNDING_SITES applied under one plan"""
+    def __init__(self, rnd, pl):
+        self.rnd, self.pl = rnd, pl
+        self.fn = {'R': rnd.R, 'Rg': rnd.Rg, 'Rv': rnd.Rv}
+
+    def on(self, name, layer=None):
+        when, pl = ROUNDING_SITES[name][1], self.pl
+        if when is None:
+            return True
+        if when == 'not fuse_lnb':
+            return not pl['fuse_lnb']
+        if when == 'per layer':      # layer: the one whose OUTPUT gradient this is
+            return (not pl['top_rows']) if layer == pl['nlayers'] - 1 else not pl['fuse_lnb']
+        return bool(pl[when])
+
+    def __call__(self, name, t, layer=None):
+        return self.fn[ROUNDING_SITES[name][0]](t) if self.on(name, layer) else t
+
+    def linear_grad_operand(self, x, w, b):
+        """_linear(x, w, b) whose WEIGHT gradient contracts the rounded x (site 'xaug'): value, d/dx and d/db of the plain product"""
+        if not self.on('xaug'):
+            return _linear(x, w, b)
+        shadow = self('xaug', x) @ w.t()
+        return _linear(x, w.detach(), b) + (shadow - shadow.detach())
+
+    def softmax(self, scores):
+        """the flash kernel's form: the numerators are the MFMA operand (site 'P'), the division by their f32 sum comes last; the scores' gradient is dS"""
+        scores = self('dS', scores)
+        pu = torch.exp(scores - scores.amax(-1, keepdim=True))
+        return self('P', pu) / pu.sum(-1, keepdim=True)
+
+    def gelu(self, x, keep=None):
+        return _GeluStoredDerivative.apply(self('pre_grad', x), self.rnd.round, keep)
+
+    def layer_norm(self, v, w, b, grad_site, layer=None):
+        """(the LayerNorm output the next GEMM operand is cut from, the same rows as the next residual add reads them) of the pre-LayerNorm sum v"""
+        v = self('y_grad', v)
+        if self.on('Yu'):
+            o = self(grad_site, _layer_norm(self('Yu', v), w, b), layer)
+            return o, self('X', o)
+        if self.on('Y'):      # gemm_nt_ln_kernel<..., Y16>: statistics and operand copy from the f32 sum; the residual and the backward's xhat from the rounded one
+            mu = v.mean(-1, keepdim=True)
+            rstd = 1.0 / torch.sqrt(((v - mu) ** 2).mean(-1, keepdim=True) + 1e-5)
+            o = self(grad_site, (self('Y', v) - mu) * rstd * w + b, layer)
+            return o + (_layer_norm(v, w, b) - o).detach(), o
+        o = self(grad_site, _layer_norm(v, w, b), layer)
+        return o, o
+
+
+def forward(sd, x, y, sep, nhead, dtype=torch.float64, return_hidden=False, dropout=None, rounding=None):
     """logits[T-sep, B, n_out] from a reference-format state dict `sd` (keys as in SURVEY.md 8(b)).
     dropout = (p, seed): TransformerEncoderLayer's four dropout sites (attention probabilities; after out_proj; after the FFN
     activation; after linear2 -- torch nn/modules/transformer.py, functional.py multi_head_attention_forward) with the masks the HIP
-    stack generates from `seed` (element-wise sites: row = b * T + t, column = feature; attention: (query, key) per (dataset, head))."""
+    stack generates from `seed` (element-wise sites: row = b * T + t, column = feature; attention: (query, key) per (dataset, head)).
+    rounding = Rounding(...): the 16-bit stack's operand roundings at ROUNDING_SITES, straight-through on this graph (S below); None = the plain oracle,
+    where S(name, t) is t and S's helpers are the plain functions."""
     p = {k: v.detach().to(dtype) if not v.requires_grad else v.to(dtype) for k, v in sd.items()}
     x, y = x.to(dtype), y.to(dtype)
     T, B, _ = x.shape
     if sep < 0:
         sep += T
-    x_emb = _linear(x, p['encoder.weight'], p['encoder.bias'])                    # transformer.py:68
-    y_emb = _linear(y.unsqueeze(-1), p['y_encoder.weight'], p['y_encoder.bias'])  # :69
-    h = torch.cat([x_emb[:sep] + y_emb[:sep], x_emb[sep:]], 0)                    # :73-74
-    E = h.shape[-1]
+    E = p['encoder.weight'].shape[0]
     D = E // nhead
+    nlayers = 1 + max((int(k.split('.')[2]) for k in p if k.startswith('transformer_encoder.layers.')), default=-1)
+    S = _NoSites() if rounding is None else _Sites(rounding, rounding.plan(E, nhead, p['decoder.0.weight'].shape[0], nlayers, T, sep, 0.0 if dropout is None else dropout[0]))
+    W = lambda name: S('W', p[name])
+    x_emb = S.linear_grad_operand(x, p['encoder.weight'], p['encoder.bias'])                    # transformer.py:68
+    y_emb = S.linear_grad_operand(y.unsqueeze(-1), p['y_encoder.weight'], p['y_encoder.bias'])  # :69
+    h = S('emb_grad', torch.cat([x_emb[:sep] + y_emb[:sep], x_emb[sep:]], 0))                   # :73-74
+    res = h                                                                                     # (h: what GEMM operands are cut from; res: the same rows as a residual add reads them)
     mask = d_q_mask(T, sep, dtype, h.device)
-    nlayers = 1 + max(int(k.split('.')[2]) for k in p if k.startswith('transformer_encoder.layers.'))
     for l in range(nlayers):
         pre = f'transformer_encoder.layers.{l}.'
-        qkv = _linear(h, p[pre + 'self_attn.in_proj_weight'], p[pre + 'self_attn.in_proj_bias'])   # [T,B,3E]
-        q, k, v = [t.reshape(T, B, nhead, D).permute(1, 2, 0, 3) for t in qkv.split(E, -1)]        # [B,H,T,D]
+        xr, w_in = S('X', h), W(pre + 'self_attn.in_proj_weight')
+        qkv = _linear(xr, w_in, p[pre + 'self_attn.in_proj_bias'])   # [T,B,3E]
+        if S.on('center') and sep > 0:      # launch_key_shift (rowwise.hip): k' = k - W_k xbar, xbar the mean of <= 64 evenly spaced train rows of the operand copy; a constant of the backward
+            ns = min(64, sep)
+            shift = (xr[0:ns * (sep // ns):sep // ns].mean(0, keepdim=True) @ w_in[E:2 * E].t()).detach()
+            qkv = qkv - torch.cat([torch.zeros_like(shift), shift, torch.zeros_like(shift)], -1)
+        q, k, v = [t.reshape(T, B, nhead, D).permute(1, 2, 0, 3) for t in S('qkv', qkv).split(E, -1)]        # [B,H,T,D]
         scores = q @ k.transpose(-1, -2) / math.sqrt(D) + mask
-        probs = torch.softmax(scores, -1)
+        probs = S.softmax(scores)
         if dropout is not None:
             pd, seed = dropout
             import numpy as np
@@ -107,22 +302,21 @@ def forward(sd, x, y, sep, nhead, dtype=torch.float64, return_hidden=False, drop
             probs = probs * pm.to(dtype) * keep_scale
             rows = [bb * T + t for t in range(T) for bb in range(B)]                                        # token row of element [t, b]
             elem = lambda site, width: dropout_keep_mask(dropout_site_seed(seed, l, site), rows, range(width), pd).reshape(T, B, width).to(dtype) * keep_scale
-        ctx = (probs @ v).permute(2, 0, 1, 3).reshape(T, B, E)
-        att = _linear(ctx, p[pre + 'self_attn.out_proj.weight'], p[pre + 'self_attn.out_proj.bias'])
+        ctx = S('ctx', (probs @ v).permute(2, 0, 1, 3).reshape(T, B, E))
+        att = _linear(ctx, W(pre + 'self_attn.out_proj.weight'), p[pre + 'self_attn.out_proj.bias'])
         if dropout is not None:
-            att = att * elem(1, E)
-        h = _layer_norm(h + att, p[pre + 'norm1.weight'], p[pre + 'norm1.bias'])
-        act = _gelu(_linear(h, p[pre + 'linear1.weight'], p[pre + 'linear1.bias']))
+            att = S('drop_grad', att) * elem(1, E)
+        h, res = S.layer_norm(res + att, p[pre + 'norm1.weight'], p[pre + 'norm1.bias'], 'x1_grad')
+        w1 = W(pre + 'linear1.weight')
+        act = S.gelu(_linear(S('X', h), w1, p[pre + 'linear1.bias']), None if dropout is None else elem(2, w1.shape[0]))
+        ff = _linear(act, W(pre + 'linear2.weight'), p[pre + 'linear2.bias'])
         if dropout is not None:
-            act = act * elem(2, act.shape[-1])
-        ff = _linear(act, p[pre + 'linear2.weight'], p[pre + 'linear2.bias'])
-        if dropout is not None:
-            ff = ff * elem(3, E)
-        h = _layer_norm(h + ff, p[pre + 'norm2.weight'], p[pre + 'norm2.bias'])
+            ff = S('drop_grad', ff) * elem(3, E)
+        h, res = S.layer_norm(res + ff, p[pre + 'norm2.weight'], p[pre + 'norm2.bias'], 'out_grad', l)
     if return_hidden:
         return h
-    out = _linear(_gelu(_linear(h, p['decoder.0.weight'], p['decoder.0.bias'])), p['decoder.2.weight'], p['decoder.2.bias'])  # :85
-    return out[sep:]                                                                                                          # :91
+    out = _linear(S.gelu(_linear(S('X', h), W('decoder.0.weight'), p['decoder.0.bias'])), W('decoder.2.weight'), p['decoder.2.bias'])  # :85
+    return S('dlog', out)[sep:]                                                                                                             # :91
 
 
 # ---- bar distribution -----------------------------------------------------------------------------
@@ -170,15 +364,21 @@ def bar_mean(logits, borders, full_support=True):
 
 
 # ---- one training step ------------------------------------------------------------------------------
-def loss_and_grads(sd, x, y, target_y, sep, nhead, borders, full_support=True, dtype=torch.float64, dropout=None):
+def loss_and_grads(sd, x, y, target_y, sep, nhead, borders, full_support=True, dtype=torch.float64, dropout=None, rounding=None):
     """mean bar-NLL over the test rows and d loss / d parameter for every state-dict tensor
-    (train.py:70-93 with criterion = FullSupportBarDistribution)."""
+    (train.py:70-93 with criterion = FullSupportBarDistribution).  rounding: as `forward`; fp16 runs the backward on loss * 2^k and divides it out."""
     leaves = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in sd.items() if not k.startswith('criterion.')}
-    logits = forward(leaves, x, y, sep, nhead, dtype, dropout=dropout)
+    logits = forward(leaves, x, y, sep, nhead, dtype, dropout=dropout, rounding=rounding)
     T = x.shape[0]
     s = sep if sep >= 0 else sep + T
     losses = bar_nll(logits.reshape(-1, logits.shape[-1]), target_y[s:].reshape(-1), borders, full_support).view(logits.shape[:2])
     loss = losses.mean()
+    if rounding is not None and rounding.fmt == 'fp16':
+        # pfn_device.h loss_scale_exp: max|dlogits| 2^k lands in [2^t, 2^(t+1)), t = 2 (rowwise.hip g_loss_scale_target); every gradient leaves times 2^-k
+        amax = torch.autograd.grad(loss, logits, retain_graph=True)[0].abs().max().item()
+        k = 2 - math.floor(math.log2(amax)) if 0 < amax < float('inf') else 0
+        (loss * 2.0 ** k).backward()
+        return loss.detach(), logits.detach(), {n: v.grad * 2.0 ** -k for n, v in leaves.items()}
     loss.backward()
     return loss.detach(), logits.detach(), {k: v.grad for k, v in leaves.items()}
 

@@ -17,6 +17,7 @@ import ctypes
 import math
 import os
 import random
+import re
 
 import pytest
 import torch
@@ -173,6 +174,11 @@ def test_config1_vs_oracle(precision):
         tot_err = math.sqrt(sum(((p.grad.double().cpu() - grads_o[k]) ** 2).sum().item() for k, p in model.named_parameters()))
         tot = math.sqrt(sum((g ** 2).sum().item() for g in grads_o.values()))
         within(f'{precision} global gradient rel l2', tot_err / tot, tol3(precision, 2e-4, 1.2e-2, 1.3e-3))
+        if tight:
+            # every tensor by itself, at the bound rule of tests/test_gpu_stack_grads.py for the exact-f32 mode: 4 x max(e, 2^-23), e = the oracle in f32 against f64
+            _, _, grads_32 = pfn_oracle.loss_and_grads(sd, x, y, y, sep, cfg['H'], sd['criterion.borders'], dtype=torch.float32)
+            for k, p in model.named_parameters():
+                within('f32 ' + re.sub(r'layers\.\d+\.', 'layers.*.', k) + ' grad rel l2 / bound', relerr(p.grad, grads_o[k]) / (4 * max(relerr(grads_32[k], grads_o[k]), 2.0 ** -23)), 1.0)
 
 
 @pytest.mark.parametrize('E,H', [(128, 4), (512, 4), (1024, 4)])      # LayerNorm-fused GEMMs (128, 512) / the LayerNorm as its own kernel (1024 = configs[4])

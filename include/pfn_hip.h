@@ -553,6 +553,42 @@ int pfn_bnn_svgd_steps(const float* x, const float* y, const int32_t* n_of, floa
                        int num_particles, int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, float bandwidth_factor,
                        void* workspace, int64_t workspace_bytes, float* potential, float* bandwidth, void* stream);
 
+/* ---- Tabular study (ABI 10, additive; csrc/tabular.hip): the evaluation protocol of the reference's tabular.py:160-370 on the device.  f32 data, int32
+ * indices, caller-owned buffers, stream-ordered, no allocation, no workspace, no host synchronisation; every result is a bitwise function of its own
+ * window / column / problem, wherever it sits in the call.  The shapes are checked first, before any pointer is looked at and before any HIP call.
+ *
+ * pfn_tabular_windows: X [N,F] the table, y [N], starts [W] int32 ON THE DEVICE (the first row of each window; a window with start < 0 or start + bptt > N
+ *   is never read and comes out as NaN), T = bptt - sep.
+ *   mode PFN_TAB_NORM_WITH_TEST (evaluate_position:288-296, the PFN arm): x_out [sep+1, W T, F_out], y_out [sep, W T]; column w T + t holds the sep train
+ *     rows of window w followed by its test row t; every feature is normalised by the mean and the unbiased std (+ 1e-6) of those sep + 1 values, then
+ *     divided by `rescale`.  1 <= sep < bptt.
+ *   mode PFN_TAB_NORM_TRAIN_ONLY (batch_pred:315-317, the baselines): x_out [bptt, W, F_out], y_out [bptt, W]; the statistics of the sep train rows are
+ *     applied to all bptt rows; `rescale` is not used.  1 <= sep <= bptt.
+ *   Columns F .. F_out - 1 are zeros (the reference's extend_features).  y_out may be NULL.  The train rows' mean m0 (a sum, then a centred correction) and
+ *   their second moment about m0 are formed once per (window, feature) in f64 and never as a sum of squares of raw values; WITH_TEST folds the one test value in
+ *   by the one-step Welford update.  A feature whose values (sep + 1, respectively sep) are all bit-equal is written as exactly 0 -- the padding columns, and
+ *   constant columns too, where the reference writes (x - mean) / 1e-6 noise.
+ *   1 <= F <= 1024, F <= F_out: else PFN_ERR_UNSUPPORTED; N, W >= 1, the sep ranges above, rescale > 0, a known mode, non-NULL X, y, starts, x_out, x_out
+ *   16-byte aligned: else PFN_ERR_ARGUMENT / PFN_ERR_ALIGNMENT.
+ *
+ * pfn_auc_counts: scores [T,C], labels [T,C] (positive = label > 0.5) -> counts [C,4] int64 = (P positives, Nn negatives, gt = pairs (pos, neg) with
+ *   s_pos > s_neg, eq = pairs with s_pos == s_neg).  AUC = (2 gt + eq) / (2 P Nn), formed by the caller in f64; a NaN score wins and ties nothing.
+ *   1 <= T <= 4096 else PFN_ERR_UNSUPPORTED; C >= 1 and non-NULL buffers else PFN_ERR_ARGUMENT.
+ *
+ * pfn_knn_cv: P problems; train [P,n,F], labels [P,n] (class = label > 0.5), test [P,T,F], fold [P,n] int32 in 0 .. 4 (the CV test fold of each train row;
+ *   a value outside takes no part in cv_correct).  Squared Euclidean distances in f32, an fma chain in ascending feature order; neighbours ordered by
+ *   (d^2, train index), the lower index first at equal distance.  cv_correct [P,5,5] int32: [p][k-1][f] = rows of fold f whose class the majority of their k
+ *   nearest train rows OUTSIDE fold f predicts (a split vote at even k predicts class 0); a row with fewer than k such neighbours counts as wrong.
+ *   test_pos [P,T,5]: positives among the k nearest of all n train rows; test_nbr [P,T,5]: those neighbours' indices (-1 where n < k).
+ *   4 <= n <= 128, 1 <= T <= 128, 1 <= F <= 128 else PFN_ERR_UNSUPPORTED; P >= 1 and non-NULL buffers else PFN_ERR_ARGUMENT. */
+#define PFN_TAB_NORM_WITH_TEST 0
+#define PFN_TAB_NORM_TRAIN_ONLY 1
+int pfn_tabular_windows(const float* X, const float* y, const int32_t* starts, int64_t N, int F, int F_out, int W, int bptt, int sep, float rescale, int mode,
+                        float* x_out, float* y_out, void* stream);
+int pfn_auc_counts(const float* scores, const float* labels, int T, int C, int64_t* counts, void* stream);
+int pfn_knn_cv(const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F,
+               int32_t* cv_correct, int32_t* test_pos, int32_t* test_nbr, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

@@ -129,6 +129,12 @@ SIGNATURES = {
     # (x, y, n_of, state, ld, P, S, F, H, activation, num_particles, step0, num_steps, lr, beta1, beta2, eps, bandwidth_factor, workspace, workspace_bytes, potential,
     #  bandwidth, stream)
     'pfn_bnn_svgd_steps': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _I, _F, _F, _F, _F, _F, _P, _L, _P, _P, _P]),
+    # tabular study (ABI 10, additive).  (X, y, starts, N, F, F_out, W, bptt, sep, rescale, mode, x_out, y_out, stream)
+    'pfn_tabular_windows': (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P]),
+    # (scores, labels, T, C, counts, stream)
+    'pfn_auc_counts': (_I, [_P, _P, _I, _I, _P, _P]),
+    # (train, labels, test, fold, P, n, T, F, cv_correct, test_pos, test_nbr, stream)
+    'pfn_knn_cv': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

@@ -1668,6 +1668,41 @@ int pfn_bnn_svgd_steps(const float* x, const float* y, const int32_t* n_of, floa
   return PFN_OK;
 }
 
+// ---- Tabular study (tabular.hip; ABI 10, additive) ----
+int pfn_tabular_windows(const float* X, const float* y, const int32_t* starts, int64_t N, int F, int F_out, int W, int bptt, int sep, float rescale, int mode,
+                        float* x_out, float* y_out, void* stream) {
+  if (F < 1 || F > TAB_MAX_FEATURES || F_out < F)
+    return fail(PFN_ERR_UNSUPPORTED, "F %d outside 1 .. %d or F_out %d < F (a block keeps one window's per-feature statistics in LDS)", F, TAB_MAX_FEATURES, F_out);
+  if (mode != PFN_TAB_NORM_WITH_TEST && mode != PFN_TAB_NORM_TRAIN_ONLY) return fail(PFN_ERR_ARGUMENT, "unknown tabular_windows mode %d", mode);
+  if (N < 1 || W < 1 || sep < 1 || sep > bptt || (mode == PFN_TAB_NORM_WITH_TEST && sep == bptt) || bptt > 65536 || !(rescale > 0.f))
+    return fail(PFN_ERR_ARGUMENT, "bad tabular_windows arguments (N %lld >= 1, W %d >= 1, 1 <= sep %d <%s bptt %d <= 65536, rescale %g > 0)", (long long)N, W, sep,
+                mode == PFN_TAB_NORM_WITH_TEST ? "" : "=", bptt, (double)rescale);
+  if (!X || !y || !starts || !x_out) return fail(PFN_ERR_ARGUMENT, "bad tabular_windows arguments (X, y, starts, x_out not NULL)");
+  if ((uintptr_t)x_out % 16) return fail(PFN_ERR_ALIGNMENT, "tabular_windows: x_out must be 16-byte aligned");
+  TabWindowsArgs a{};
+  a.X = X; a.y = y; a.starts = starts; a.N = N; a.F = F; a.F_out = F_out; a.W = W; a.bptt = bptt; a.sep = sep; a.mode = mode; a.rescale = rescale;
+  a.x_out = x_out; a.y_out = y_out;
+  PFN_TRY(launch_tab_windows(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_auc_counts(const float* scores, const float* labels, int T, int C, int64_t* counts, void* stream) {
+  if (T < 1 || T > 4096) return fail(PFN_ERR_UNSUPPORTED, "auc_counts: T %d outside 1 .. 4096 (a block stages one column in LDS)", T);
+  if (C < 1 || !scores || !labels || !counts) return fail(PFN_ERR_ARGUMENT, "bad auc_counts arguments (C %d >= 1, scores, labels, counts not NULL)", C);
+  PFN_TRY(launch_auc_counts(scores, labels, T, C, counts, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_knn_cv(const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F, int32_t* cv_correct, int32_t* test_pos,
+               int32_t* test_nbr, void* stream) {
+  if (n < 4 || n > 128 || T < 1 || T > 128 || F < 1 || F > 128)
+    return fail(PFN_ERR_UNSUPPORTED, "knn_cv: n %d outside 4 .. 128, T %d outside 1 .. 128 or F %d outside 1 .. 128 (one thread per query, every row in LDS)", n, T, F);
+  if (P < 1 || !train || !labels || !test || !fold || !cv_correct || !test_pos || !test_nbr)
+    return fail(PFN_ERR_ARGUMENT, "bad knn_cv arguments (P %d >= 1, train, labels, test, fold, cv_correct, test_pos, test_nbr not NULL)", P);
+  KnnCvArgs a{};
+  a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.P = P; a.n = n; a.T = T; a.F = F; a.cv_correct = cv_correct; a.test_pos = test_pos; a.test_nbr = test_nbr;
+  PFN_TRY(launch_knn_cv(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
 int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
                           float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
                           uint64_t seed, uint64_t offset, void* stream) {

@@ -571,6 +571,34 @@ inline bool bnn_svgd_resident(int N, int D) { return 16L * N * (D | 1) <= BNN_SV
 inline int64_t bnn_svgd_workspace_bytes(int P, int N, int D) { return bnn_svgd_resident(N, D) ? 0 : (int64_t)P * N * D * 4; }
 int launch_bnn_svgd_steps(const BnnSvgdArgs& a, hipStream_t s);
 
+// ---- Tabular study (tabular.hip): the windows of an eval position, ROC-AUC pair counts, kNN with its grid search -----
+constexpr int TAB_MAX_FEATURES = 1024;      // table columns whose statistics one block keeps in LDS
+struct TabWindowsArgs {
+  const float* X;          // [N,F] the table
+  const float* y;          // [N]
+  const int32_t* starts;   // [W] first row of each window (device); a window that leaves the table is written as NaN, never read
+  long N;
+  int F, F_out, W, bptt, sep, mode;
+  float rescale;
+  float* x_out;            // WITH_TEST [sep+1, W T, F_out], TRAIN_ONLY [bptt, W, F_out]
+  float* y_out;            // WITH_TEST [sep, W T], TRAIN_ONLY [bptt, W]; or null
+};
+int launch_tab_windows(const TabWindowsArgs& a, hipStream_t s);
+int launch_auc_counts(const float* scores, const float* labels, int T, int C, int64_t* counts, hipStream_t s);
+struct KnnCvArgs {
+  const float* train;      // [P,n,F]
+  const float* labels;     // [P,n]: class = label > 0.5
+  const float* test;       // [P,T,F]
+  const int32_t* fold;     // [P,n] in 0 .. 4
+  int P, n, T, F;
+  int32_t* cv_correct;     // [P,5,5]
+  int32_t* test_pos;       // [P,T,5]
+  int32_t* test_nbr;       // [P,T,5]
+};
+// rows of both kinds at an odd stride, then the labels and folds of the train rows: 133,120 bytes at n = T = F = 128
+inline size_t knn_cv_lds_bytes(int n, int T, int F) { return (size_t)(n + T) * (F | 1) * 4 + (size_t)n * 8; }
+int launch_knn_cv(const KnnCvArgs& a, hipStream_t s);
+
 // ---- BNN prior sampler (mlp_prior.hip) -----------------------------------------------------------
 struct MlpPriorArgs {
   const float* weights;   // [num_models][Lmax][HP][HP]: layer l transposed ([in][out]), zero padded

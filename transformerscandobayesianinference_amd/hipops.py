@@ -447,3 +447,103 @@ def bnn_svgd_steps(x, y, state, H, num_steps, step0=0, lr=1e-3, betas=(0.9, 0.99
                                       num_steps, float(lr), float(betas[0]), float(betas[1]), float(eps), float(bandwidth_factor), _hip.ptr(ws), max(ws_bytes, 0),
                                       potential.data_ptr(), bandwidth.data_ptr(), _hip.stream_ptr(x.device)), 'pfn_bnn_svgd_steps')
     return potential, bandwidth
+
+
+# ---- Tabular study (csrc/tabular.hip; include/pfn_hip.h "Tabular study") ----
+TAB_NORM_WITH_TEST, TAB_NORM_TRAIN_ONLY = 0, 1      # PFN_TAB_NORM_*
+TAB_MAX_FEATURES = 1024
+AUC_MAX_ROWS = 4096
+KNN_MAX_K, KNN_MAX_FOLDS = 5, 5
+KNN_LIMITS = dict(n=(4, 128), T=(1, 128), F=(1, 128))
+
+
+def tabular_windows_check(N, F, F_out, W, bptt, sep, rescale, mode, starts):
+    """The shape rules of pfn_tabular_windows plus the one the kernel can only answer with NaN columns: every window lies inside the table.  Host only."""
+    if mode not in (TAB_NORM_WITH_TEST, TAB_NORM_TRAIN_ONLY):
+        raise ValueError(f'unknown mode {mode!r} (TAB_NORM_WITH_TEST, TAB_NORM_TRAIN_ONLY)')
+    if not (1 <= F <= TAB_MAX_FEATURES and F_out >= F):
+        raise ValueError(f'F {F} outside 1 .. {TAB_MAX_FEATURES} or F_out {F_out} < F')
+    if not (N >= 1 and W >= 1 and 1 <= sep <= bptt and (sep < bptt or mode == TAB_NORM_TRAIN_ONLY) and rescale > 0):
+        raise ValueError(f'need N {N} >= 1, W {W} >= 1, 1 <= sep {sep} {"<" if mode == TAB_NORM_WITH_TEST else "<="} bptt {bptt}, rescale {rescale} > 0')
+    if min(starts) < 0 or max(starts) + bptt > N:
+        raise ValueError(f'a window of {bptt} rows starting at {min(starts)} .. {max(starts)} leaves the table of {N} rows')
+
+
+def tabular_windows(X, y, starts, bptt, sep, F_out=None, rescale=1.0, mode=TAB_NORM_WITH_TEST):
+    """Every window of an eval position gathered from the table X [N,F], y [N] and normalised, in one launch (pfn_tabular_windows).  `starts`: the windows'
+    first rows, a host sequence or CPU tensor (checked against the table here).  WITH_TEST returns x [sep+1, W T, F_out], y [sep, W T] -- column w T + t is
+    window w's train rows and its test row t, normalised over those sep + 1 rows and divided by `rescale`; TRAIN_ONLY returns x [bptt, W, F_out], y [bptt, W]
+    normalised by the train rows' statistics."""
+    starts = [int(s) for s in (starts.tolist() if torch.is_tensor(starts) else starts)]
+    if X.dim() != 2 or y.shape != X.shape[:1]:
+        raise ValueError('X [N, F], y [N]')
+    N, F = X.shape
+    F_out = F if F_out is None else int(F_out)
+    bptt, sep, W = int(bptt), int(sep), len(starts)
+    tabular_windows_check(N, F, F_out, W, bptt, sep, float(rescale), mode, starts or [0])
+    _hip.require_gpu_tensor(X, 'X')
+    _bnn_f32(X, y)
+    T = bptt - sep
+    dev = X.device
+    st = torch.tensor(starts, dtype=torch.int32).to(dev)
+    if mode == TAB_NORM_WITH_TEST:
+        x_out = torch.empty(sep + 1, W * T, F_out, dtype=torch.float32, device=dev)
+        y_out = torch.empty(sep, W * T, dtype=torch.float32, device=dev)
+    else:
+        x_out = torch.empty(bptt, W, F_out, dtype=torch.float32, device=dev)
+        y_out = torch.empty(bptt, W, dtype=torch.float32, device=dev)
+    _hip.check(_hip.lib().pfn_tabular_windows(X.data_ptr(), y.data_ptr(), st.data_ptr(), N, F, F_out, W, bptt, sep, float(rescale), int(mode), x_out.data_ptr(),
+                                              y_out.data_ptr(), _hip.stream_ptr(dev)), 'pfn_tabular_windows')
+    return x_out, y_out
+
+
+def auc_counts(scores, labels):
+    """Per column of scores [T,C] / labels [T,C] (positive = label > 0.5): int64 [C,4] = (positives, negatives, pairs won, pairs tied) (pfn_auc_counts)."""
+    if scores.dim() != 2 or labels.shape != scores.shape:
+        raise ValueError('scores [T, C], labels [T, C]')
+    T, C = scores.shape
+    if not (1 <= T <= AUC_MAX_ROWS and C >= 1):
+        raise ValueError(f'T {T} outside 1 .. {AUC_MAX_ROWS} or C {C} < 1')
+    _hip.require_gpu_tensor(scores, 'scores')
+    _bnn_f32(scores, labels)
+    counts = torch.empty(C, 4, dtype=torch.int64, device=scores.device)
+    _hip.check(_hip.lib().pfn_auc_counts(scores.data_ptr(), labels.data_ptr(), T, C, counts.data_ptr(), _hip.stream_ptr(scores.device)), 'pfn_auc_counts')
+    return counts
+
+
+def auc_from_counts(counts):
+    """AUC = (2 gt + eq) / (2 P Nn) in f64 on the host, NaN where a column has one class only.  counts [C,4] -> numpy [C]."""
+    import numpy as np
+    c = counts.cpu().numpy().astype(np.int64).reshape(-1, 4)
+    pairs = (c[:, 0] * c[:, 1]).astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(pairs > 0, (2 * c[:, 2] + c[:, 3]).astype(np.float64) / (2. * pairs), np.nan)
+
+
+def knn_cv_check(n, T, F):
+    for name, v in (('n', n), ('T', T), ('F', F)):
+        lo, hi = KNN_LIMITS[name]
+        if not lo <= v <= hi:
+            raise ValueError(f'knn_cv: {name} = {v} outside {lo} .. {hi}')
+
+
+def knn_cv(train, labels, test, fold):
+    """Neighbour lists for the kNN grid search of every problem in one launch (pfn_knn_cv): train [P,n,F], labels [P,n], test [P,T,F] f32 and fold [P,n] int32
+    (the CV test fold of each train row, 0 .. 4) on the GPU.  Returns int32 (cv_correct [P,5,5], test_pos [P,T,5], test_nbr [P,T,5])."""
+    if train.dim() != 3 or test.dim() != 3 or test.shape[0] != train.shape[0] or test.shape[2] != train.shape[2] or labels.shape != train.shape[:2] or fold.shape != train.shape[:2]:
+        raise ValueError('train [P, n, F], labels [P, n], test [P, T, F], fold [P, n]')
+    P, n, F = train.shape
+    T = test.shape[1]
+    knn_cv_check(n, T, F)
+    if P < 1:
+        raise ValueError('P >= 1')
+    _hip.require_gpu_tensor(train, 'train')
+    _bnn_f32(train, labels, test)
+    assert fold.dtype == torch.int32 and fold.is_contiguous() and fold.device == train.device, 'fold [P, n] int32'
+    dev = train.device
+    cv_correct = torch.empty(P, KNN_MAX_K, KNN_MAX_FOLDS, dtype=torch.int32, device=dev)
+    test_pos = torch.empty(P, T, KNN_MAX_K, dtype=torch.int32, device=dev)
+    test_nbr = torch.empty(P, T, KNN_MAX_K, dtype=torch.int32, device=dev)
+    _hip.check(_hip.lib().pfn_knn_cv(train.data_ptr(), labels.data_ptr(), test.data_ptr(), fold.data_ptr(), P, n, T, F, cv_correct.data_ptr(), test_pos.data_ptr(),
+                                     test_nbr.data_ptr(), _hip.stream_ptr(dev)), 'pfn_knn_cv')
+    return cv_correct, test_pos, test_nbr

@@ -7,16 +7,31 @@ Mirror of the model-building part of the reference `tabular.py`:
     get_model                             :109-155
 plus `save_checkpoint` / `load_checkpoint` for the `(state_dict, optimizer_state)` tuples of
 `BayesianModels_And_Custom_Pyro_Modules.ipynb` cells 14 / 16 and `TabularEvalSimple.ipynb` cell 12.
-The evaluation half of the reference file (OpenML datasets, XGBoost / CatBoost / sklearn / pyro baselines,
-:160-677) needs network access and libraries this stack does not carry; it is out of scope.
+
+The evaluation protocol of the reference file runs on the device:
+    evaluate / evaluate_dataset / evaluate_position / batch_pred     :160-323
+    knn_metric (with its 5-fold grid search over k)                  :350-369
+    load_svmlight_table                                              datasets/__init__.py:8-16
+`evaluate_position` gathers and normalises every (window, test row) column in one launch (pfn_tabular_windows), runs the PFN once
+at batch windows x test rows, and counts ROC-AUC pairs on the device (pfn_auc_counts); the kNN baseline finds the neighbour lists of
+every CV fold and every test row of every window in one launch (pfn_knn_cv) and does the grid-search arithmetic on the host in f64.
+The other baselines of the reference (logistic regression, GP / BNN classifiers, XGBoost, CatBoost: :325-677) and the OpenML loaders
+stay out: they need libraries and network access this stack does not carry.  Any callable with the reference's metric-function
+signature still runs through `batch_pred`, one window at a time, as the reference loops.
 
 `get_model` trains through this package's `train()` -- HIP encoder stack, fused optimizer, HIP prior samplers --
 so a PFN trained here loads into the reference's `TransformerModel` and vice versa: the state-dict keys are the
 reference's (INTEGRATION.md).
 """
-import torch
+import os
+import time
+import warnings
 
-from transformerscandobayesianinference_amd import encoders, priors
+import numpy as np
+import torch
+from torch import nn
+
+from transformerscandobayesianinference_amd import encoders, hipops, priors
 from transformerscandobayesianinference_amd.priors.utils import gamma_sampler_f, trunc_norm_sampler_f
 from transformerscandobayesianinference_amd.train import Losses, train
 from transformerscandobayesianinference_amd.utils import get_uniform_single_eval_pos_sampler  # noqa: F401  (reference tabular.py:39-44 defines it here)
@@ -131,3 +146,275 @@ def load_checkpoint(model, path, strict=True):
     model_state, optimizer_state = torch.load(path, map_location='cpu')
     model.load_state_dict(model_state, strict=strict)
     return optimizer_state
+
+
+## General eval (reference tabular.py:158-323)
+
+CV = 5                      # the reference's module constant: folds of every grid search
+MAX_TOKENS_PER_FORWARD = 1 << 20
+
+
+def load_svmlight_table(path):
+    """The class-balancing, interleaving loader of the reference's datasets/__init__.py:8-16 (`get_svmlight`) for a local svmlight / libsvm text file with
+    labels -1 / +1: keep all rows of the rarer class and as many of the other (the LAST ones in file order), alternate the two classes, reverse.  Returns
+    (X [2 m, F] f32, y [2 m] f32 in {0, 1}).  Rows of equal label keep their file order (a stable sort; the reference's `np.argsort` default is not stable, so
+    its order there depends on the numpy build -- INTEGRATION.md)."""
+    labels, rows, width = [], [], 0
+    with open(path) as f:
+        for line in f:
+            line = line.split('#', 1)[0].split()
+            if not line:
+                continue
+            labels.append(float(line[0]))
+            pairs = [(int(k), float(v)) for k, v in (item.split(':') for item in line[1:] if not item.startswith('qid:'))]
+            rows.append(pairs)
+            width = max([width] + [k for k, _ in pairs])
+    one_based = all(k >= 1 for pairs in rows for k, _ in pairs)      # sklearn's zero_based='auto'
+    width = width if one_based else width + 1
+    X = np.zeros((len(rows), width), dtype=np.float64)
+    for i, pairs in enumerate(rows):
+        for k, v in pairs:
+            X[i, k - 1 if one_based else k] = v
+    y = (np.asarray(labels, dtype=np.float64) + 1) / 2
+    minority_is_one = y.mean() < 0.5
+    order = np.argsort(y if minority_is_one else -y, kind='stable')
+    m = int(y.sum()) if minority_is_one else int((1 - y).sum())
+    X, y = X[order][-2 * m:], y[order][-2 * m:]
+    y = torch.tensor(y).reshape(2, -1).transpose(0, 1).reshape(-1).flip([0]).float()
+    X = torch.tensor(X).reshape(2, -1, X.shape[1]).transpose(0, 1).reshape(-1, X.shape[1]).flip([0]).float()
+    return X, y
+
+
+def roc_auc_columns(scores, labels):
+    """ROC-AUC of every column of scores [T, C] against labels [T, C] in {0, 1} (both on the GPU): the device counts pairs (pfn_auc_counts), the host forms
+    (2 gt + eq) / (2 P Nn) in f64 -- sklearn's `roc_auc_score` as a ratio of integers.  Returns (auc [C] numpy f64, columns left NaN because they hold one
+    class only; the reference raises there)."""
+    auc = hipops.auc_from_counts(hipops.auc_counts(scores.float().contiguous(), labels.float().contiguous()))
+    return auc, int(np.isnan(auc).sum())
+
+
+def _report_undefined(undefined, what):
+    if undefined:
+        warnings.warn(f'{undefined} {what} hold one class only: their ROC-AUC is NaN')
+
+
+def evaluate(datasets, model, method, bptt, eval_position_range, device, max_features=0, plot=False, extend_features=False, save=True, rescale_features=False,
+             overwrite=False, max_samples=40, path_interfix='', save_dir=None):
+    """Reference tabular.py:160-213: `datasets` = [[name, X, y, categorical_feats], ...]; `model` a PFN (nn.Module) or a metric function of this module (or
+    any callable with that signature); returns the reference's result dict.  The reference's hard-coded results folder is `save_dir`: with None nothing is read
+    or written; otherwise a dataset's results are loaded from `{save_dir}/{path_interfix}/results_{method}_{name}.npy` when that file exists (and not
+    `overwrite`), and written there when `save`.  `plot` is accepted and ignored.  `extend_features` pads the table to `max_features` columns of zeros inside
+    the window kernel (no padded copy of the table is made); `rescale_features` divides by num_features / max_features as the reference does."""
+    result = {'metric': 'auc'}
+    eval_position_range = list(eval_position_range)
+    for [name, X, y, categorical_feats] in datasets:
+        result_ds = {}
+        path = None if save_dir is None else os.path.join(str(save_dir), path_interfix, f'results_{method}_{name}.npy')
+        if path is not None and os.path.isfile(path) and not overwrite:
+            with open(path, 'rb') as f:
+                result_ds = np.load(f, allow_pickle=True).tolist()
+            if 'time' in result_ds:
+                result_ds[name + '_time'] = result_ds.pop('time')
+            result.update(result_ds)
+            continue
+        rescale_features_factor = X.shape[1] / max_features if rescale_features and extend_features else 1.0
+        extend_to = max(int(max_features), X.shape[1]) if extend_features else None
+        start_time = time.time()
+        ds_result = evaluate_dataset(X.to(device), y.to(device), categorical_feats, model, bptt, eval_position_range, rescale_features=rescale_features_factor,
+                                     max_samples=max_samples, extend_to=extend_to)
+        elapsed = time.time() - start_time
+        for pos, (metric, outputs, ys) in zip(eval_position_range, ds_result):
+            if save:
+                result_ds[f'{name}_per_ds_metric_at_{pos}'] = metric
+                result_ds[f'{name}_outputs_at_{pos}'] = outputs
+                result_ds[f'{name}_ys_at_{pos}'] = ys.detach().cpu()
+            flat = torch.as_tensor(outputs, dtype=torch.float32).reshape(-1, 1)
+            if flat.shape[0] > hipops.AUC_MAX_ROWS:
+                raise ValueError(f'{flat.shape[0]} pooled predictions at eval position {pos}: pfn_auc_counts takes up to {hipops.AUC_MAX_ROWS} rows per column; '
+                                 f'lower max_samples')
+            pooled, undefined = roc_auc_columns(flat.to(ys.device), ys.reshape(-1, 1))
+            _report_undefined(undefined, f'pooled predictions of {name} at eval position {pos}')
+            result_ds[f'{name}_mean_metric_at_{pos}'] = float(pooled[0])
+            result_ds[name + '_time'] = elapsed
+        if save and path is not None:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, 'wb') as f:
+                np.save(f, result_ds)
+        result.update(result_ds)
+    for pos in eval_position_range:
+        result[f'mean_metric_at_{pos}'] = np.array([result[f'{d[0]}_mean_metric_at_{pos}'] for d in datasets]).mean()
+    result['mean_metric'] = np.array([result[f'mean_metric_at_{pos}'] for pos in eval_position_range]).mean()
+    return result
+
+
+def evaluate_dataset(X, y, categorical_feats, model, bptt, eval_position_range, plot=False, rescale_features=1.0, max_samples=40, extend_to=None):
+    """Reference tabular.py:216-228: `evaluate_position` at every eval position; a list of its 3-tuples."""
+    return [evaluate_position(X, y, categorical_feats, model, bptt, eval_position, rescale_features=rescale_features, max_samples=max_samples, extend_to=extend_to)
+            for eval_position in eval_position_range]
+
+
+def select_windows(num_rows, bptt, max_samples):
+    """The reference's choice of windows (tabular.py:273-277): of the num_rows - bptt windows of bptt consecutive rows, the first `max_samples` of
+    `torch.randperm` under seed 13, drawn on the CPU inside `fork_rng` so that the draw is the reference's and the caller's generator is left alone."""
+    num_evals = num_rows - bptt
+    if num_evals < 1:
+        raise ValueError(f'a table of {num_rows} rows has no window of bptt = {bptt} rows (the reference takes len(X) - bptt windows)')
+    with torch.random.fork_rng(devices=[]):
+        torch.random.manual_seed(13)
+        sel = torch.randperm(num_evals)
+    return sel[:max_samples]
+
+
+def pfn_window_logits(X, y, starts, model, bptt, eval_position, rescale_features=1.0, extend_to=None):
+    """The PFN's logit for every test row of every window, [T, W] f32 on the GPU: window w is the table rows starts[w] .. starts[w] + bptt - 1, its first
+    `eval_position` rows the training set.  One window launch and one forward in eval mode (`evaluate_position` says when it is more than one)."""
+    sep = int(eval_position)
+    T = int(bptt) - sep
+    model.eval()
+    F_out = X.shape[1] if extend_to is None else int(extend_to)
+    per_call = max(1, MAX_TOKENS_PER_FORWARD // (T * (sep + 1)))
+    logits = []
+    with torch.no_grad():
+        for w0 in range(0, len(starts), per_call):
+            x_w, y_w = hipops.tabular_windows(X, y, starts[w0:w0 + per_call], bptt, sep, F_out=F_out, rescale=rescale_features, mode=hipops.TAB_NORM_WITH_TEST)
+            logits.append(model((x_w, y_w), single_eval_pos=sep).reshape(-1, T))
+    return torch.cat(logits, 0).t().contiguous()
+
+
+def evaluate_position(X, y, categorical_feats, model, bptt, eval_position, rescale_features=1.0, max_samples=40, extend_to=None):
+    """Reference tabular.py:231-306 for one eval position: returns (ROC-AUC per window [W] numpy, outputs [T, W] numpy f64, ys [T, W]) with T = bptt -
+    eval_position test rows per window.  X [N, F], y [N] f32 on the GPU.
+    PFN arm (`model` is an nn.Module): ONE pfn_tabular_windows launch builds all W T columns (train rows + one test row, normalised over those rows), ONE
+    forward at batch W T in eval mode gives every logit, ONE pfn_auc_counts launch the metric.  The batch is split over several forwards only where it holds
+    more than MAX_TOKENS_PER_FORWARD tokens, since the stack's workspace grows with the token count; the split is between windows and changes no number.
+    Baseline arm (any other callable): `batch_pred`."""
+    bptt, sep = int(bptt), int(eval_position)
+    if not 1 <= sep < bptt:
+        raise ValueError(f'eval position {sep} outside 1 .. bptt - 1 = {bptt - 1}')
+    if X.dim() != 2 or y.shape != X.shape[:1]:
+        raise ValueError('X [N, F], y [N]')
+    starts = select_windows(X.shape[0], bptt, max_samples)
+    W, T = len(starts), bptt - sep
+    rows = (starts[:, None] + torch.arange(bptt)[None, :]).t().to(X.device)      # [bptt, W] table rows of every window
+    X, y = X.float().contiguous(), y.float().contiguous()
+    ys = y[rows[sep:]]
+    if isinstance(model, nn.Module):
+        scores = torch.sigmoid(pfn_window_logits(X, y, starts, model, bptt, sep, rescale_features=rescale_features, extend_to=extend_to))      # [T, W]
+        metric, undefined = roc_auc_columns(scores, ys)
+        _report_undefined(undefined, f'of {W} windows at eval position {sep}')
+        return metric, scores.double().cpu().numpy(), ys
+    eval_xs = X[rows]
+    if extend_to is not None and extend_to > X.shape[1]:
+        eval_xs = torch.cat([eval_xs, eval_xs.new_zeros(bptt, W, int(extend_to) - X.shape[1])], -1)
+    metric, outputs = batch_pred(model, eval_xs, y[rows], categorical_feats, start=sep, table=(X, y, starts, extend_to))
+    return metric, outputs, ys
+
+
+def batch_pred(metric_function, eval_xs, eval_ys, categorical_feats, start=2, table=None):
+    """Reference tabular.py:309-323: normalise every window eval_xs[:, w] [bptt, F] by the mean and std of its first `start` rows and hand
+    (train x, train y, test x, test y, categorical_feats) to the metric function; returns (metrics [W], outputs [T, W]).  A metric function with a `batched`
+    form (`knn_metric`) gets all windows at once; any other callable is looped window by window as the reference loops, on torch's normalisation.  `table` =
+    (X, y, starts, extend_to), when the windows are slices of one table, lets the batched form gather and normalise them in one pfn_tabular_windows launch."""
+    batched = getattr(metric_function, 'batched', None)
+    if batched is not None and eval_xs.is_cuda:
+        if table is not None:
+            X, y, starts, extend_to = table
+            x, _ = hipops.tabular_windows(X, y, starts, eval_xs.shape[0], start, F_out=X.shape[1] if extend_to is None else int(extend_to),
+                                          mode=hipops.TAB_NORM_TRAIN_ONLY)
+        else:      # windows that are no slices of a table: window w is the table's rows w bptt .. (w + 1) bptt - 1
+            bptt, W, F = eval_xs.shape
+            flat = eval_xs.float().transpose(0, 1).reshape(W * bptt, F).contiguous()
+            x, _ = hipops.tabular_windows(flat, eval_ys.float().t().reshape(-1).contiguous(), [w * bptt for w in range(W)], bptt, start, mode=hipops.TAB_NORM_TRAIN_ONLY)
+        return batched(x[:start], eval_ys[:start], x[start:], eval_ys[start:])
+    metrics, outputs = [], []
+    for eval_x, eval_y in zip(eval_xs.transpose(0, 1), eval_ys.transpose(0, 1)):
+        mean = eval_x[:start].mean(0)
+        std = eval_x[:start].std(0) + .000001
+        eval_x = (eval_x - mean) / std
+        metric, output = metric_function(eval_x[:start], eval_y[:start], eval_x[start:], eval_y[start:], categorical_feats)
+        metrics += [metric]
+        outputs += [output]
+    return np.array(metrics), np.array(outputs).T
+
+
+## KNN (reference tabular.py:349-369)
+
+def _stratified_folds(y, n_splits):
+    """The test fold of every sample under sklearn's `StratifiedKFold(n_splits, shuffle=False)` (its `_make_test_folds`): classes numbered by first
+    appearance, the sorted labels dealt round-robin over the folds to fix how many samples of each class a fold gets, then each class's samples assigned to
+    the folds in blocks, in data order.  Raises ValueError where sklearn does (fewer than 2 splits, more splits than samples, more splits than members in
+    EVERY class); where sklearn only warns (more splits than members in SOME class) it goes on, silently.  Returns int32 [n]."""
+    y = np.asarray(y).reshape(-1)
+    n_splits = int(n_splits)
+    if n_splits < 2:
+        raise ValueError(f'k-fold cross-validation requires at least one train/test split: n_splits={n_splits}')
+    if n_splits > len(y):
+        raise ValueError(f'Cannot have number of splits n_splits={n_splits} greater than the number of samples: n_samples={len(y)}.')
+    _, first, inverse = np.unique(y, return_index=True, return_inverse=True)
+    _, by_appearance = np.unique(first, return_inverse=True)
+    encoded = by_appearance[inverse.reshape(-1)]
+    n_classes = len(first)
+    counts = np.bincount(encoded)
+    if np.all(n_splits > counts):
+        raise ValueError(f'n_splits={n_splits} cannot be greater than the number of members in each class.')
+    ordered = np.sort(encoded)
+    allocation = np.asarray([np.bincount(ordered[i::n_splits], minlength=n_classes) for i in range(n_splits)])
+    folds = np.empty(len(y), dtype=np.int32)
+    for k in range(n_classes):
+        folds[encoded == k] = np.arange(n_splits).repeat(allocation[:, k])
+    return folds
+
+
+def _knn_grid(n):
+    """(candidate k values, number of folds) of the reference's grid search on n train rows: k = 1 .. min(5, n - 2), cv = min(CV, n // 2)."""
+    return np.arange(1, min(6, n - 1)), min(CV, n // 2)
+
+
+def _knn_select(cv_correct, folds, n_splits, ks, test_pos):
+    """The host half of one problem's grid search, from the kernel's integer counts: cv_correct [5, 5] (k - 1, fold), folds [n] the rows' test folds,
+    test_pos [T, 5].  As GridSearchCV(KNeighborsClassifier(), {'n_neighbors': ks}, cv=n_splits) scores it: a fold's score is its accuracy correct / size in
+    f64 -- NaN where k exceeds the fold's training rows (the fit fails, error_score = nan) --, a candidate's score the mean over folds, the best candidate the
+    FIRST maximum (NaN ranks last), the refit on all rows gives predict_proba[:, 1] = positives among the k* nearest / k*.
+    Returns (mean_test_score [len(ks)] f64, best k, proba [T] f64)."""
+    sizes = np.bincount(np.asarray(folds), minlength=n_splits)[:n_splits].astype(np.float64)
+    correct = np.asarray(cv_correct, dtype=np.float64)
+    scores = np.empty((len(ks), n_splits), dtype=np.float64)
+    for i, k in enumerate(ks):
+        scores[i] = correct[k - 1, :n_splits] / sizes
+        scores[i, sizes.sum() - sizes < k] = np.nan
+    mean = scores.mean(axis=1)
+    ranked = np.where(np.isnan(mean), -np.inf, mean)
+    best = int(ks[int(np.argmax(ranked))])
+    proba = np.asarray(test_pos, dtype=np.float64)[:, best - 1] / float(best)
+    return mean, best, proba
+
+
+def _knn_batched(x, y, test_x, test_y, return_k=False):
+    """kNN with its grid search for W problems at once: x [n, W, F] normalised train rows, y [n, W], test_x [T, W, F], test_y [T, W] on the GPU.  One
+    pfn_knn_cv launch finds every neighbour list; the folds (before) and the scores (after) are host arithmetic.  Returns (ROC-AUC [W], proba [T, W]) numpy,
+    and with return_k the chosen k of every problem as a third entry."""
+    n, W, F = x.shape
+    T = test_x.shape[0]
+    hipops.knn_cv_check(n, T, F)
+    ks, n_splits = _knn_grid(n)
+    y_host = y.detach().cpu().numpy()
+    folds = np.stack([_stratified_folds(y_host[:, w] > 0.5, n_splits) for w in range(W)])      # [W, n]
+    cv_correct, test_pos, _ = hipops.knn_cv(x.float().transpose(0, 1).contiguous(), y.float().t().contiguous(), test_x.float().transpose(0, 1).contiguous(),
+                                            torch.from_numpy(folds).to(x.device))
+    cv_correct, test_pos = cv_correct.cpu().numpy(), test_pos.cpu().numpy()
+    chosen = [_knn_select(cv_correct[w], folds[w], n_splits, ks, test_pos[w]) for w in range(W)]
+    proba = np.stack([c[2] for c in chosen], 1)      # [T, W]
+    metric, undefined = roc_auc_columns(torch.from_numpy(proba).float().to(x.device), test_y)
+    _report_undefined(undefined, f'of {W} windows')
+    return (metric, proba, [c[1] for c in chosen]) if return_k else (metric, proba)
+
+
+def knn_metric(x, y, test_x, test_y, cat_features):
+    """Reference tabular.py:351-369 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (ROC-AUC, proba [T]) of
+    a KNeighborsClassifier whose k is grid-searched over 1 .. min(5, n - 2) by min(5, n // 2)-fold stratified cross-validation.  `knn_metric.batched` is the
+    same for many problems in one launch; `batch_pred` uses it."""
+    metric, proba = _knn_batched(x[:, None], y[:, None], test_x[:, None], test_y[:, None])
+    return metric[0], proba[:, 0]
+
+
+knn_metric.batched = _knn_batched

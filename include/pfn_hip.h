@@ -589,6 +589,42 @@ int pfn_auc_counts(const float* scores, const float* labels, int T, int C, int64
 int pfn_knn_cv(const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F,
                int32_t* cv_correct, int32_t* test_pos, int32_t* test_nbr, void* stream);
 
+/* ---- Logistic regression with its grid search (ABI 10, additive; csrc/logistic.hip): the reference's logistic_metric (tabular.py:325-346) as a batch of
+ * independent convex fits.  f32 data, caller-owned buffers, stream-ordered, no allocation, no workspace, no host synchronisation, no global atomics.
+ *
+ * pfn_logistic_cv: P problems; train [P,n,F], labels [P,n] (class = label > 0.5, y~ = +1 / -1), test [P,T,F], fold [P,n] int32 (the CV test fold of each
+ *   train row), NC candidates: cand_C [NC] f32 and cand_kind [NC] int32 = penalty code (PFN_LOGIT_NONE / L1 / L2) | PFN_LOGIT_FIT_INTERCEPT.  All on the device.
+ *   One block per fit (problem p, candidate c, slot s): slot s < n_splits trains on the rows with fold[p,i] != s, slot s = n_splits on all rows (the refit),
+ *   slots beyond are unused (status PFN_LOGIT_UNUSED, zeros).  A fit is a bitwise function of its own problem and candidate, wherever it sits in the call.
+ *   Objective (scikit-learn's): C sum_i softplus(-y~_i z_i) + r(w), z = x w + b; r = 1/2 |w|^2 (l2), |w|_1 (l1), 0 (none: C is ignored, 1 is used); the
+ *   intercept is never penalised; the start is w = 0.  Solver: proximal Newton -- H = C X^T D X (+ I on the penalised coordinates for l2) plus a damping of
+ *   2^-16 trace(H) / d on the diagonal, the direction by Cholesky (l2, none) or by cyclic coordinate descent with soft-thresholding on the quadratic model (l1,
+ *   at most 50 sweeps), Armijo backtracking (1e-4, at most 30 halvings) on the true objective's difference, at most 48 iterations.
+ *   It stops with status PFN_LOGIT_CONVERGED when KKT_inf <= 64 2^-23 C max_j sum_i m_i |x_ij| (KKT: the minimum-norm subgradient; m_i = 1 on the fit's
+ *   training rows; j over the features and, with an intercept, the column of ones), PFN_LOGIT_STALLED when backtracking finds no decrease, PFN_LOGIT_CAPPED at
+ *   the iteration cap (e.g. 'none' on separable rows, which has no finite optimum), PFN_LOGIT_NONFINITE when a NaN reached the residual.  A fit whose training
+ *   rows hold one class is not run: PFN_LOGIT_ONE_CLASS, zero coefficients, a zero count, NaN decision values.  A feature that is zero on all training rows of
+ *   a fit has a coefficient of exactly 0 under every penalty.
+ *   cv_correct [P,NC,5] int32: held-out rows of fold s with (z > 0) == class (z == 0 predicts class 0); test_z [P,NC,T]: the refit's decision values;
+ *   status [P,NC,6,2] int32 = (exit reason, iterations); coef [P,NC,6,F+1] (may be NULL): the F weights, then the intercept (0 without one).
+ *   4 <= n <= 128, 1 <= T <= 128, 1 <= F <= 128, 1 <= NC <= 64 else PFN_ERR_UNSUPPORTED; P >= 1, 2 <= n_splits <= 5 and non-NULL buffers else
+ *   PFN_ERR_ARGUMENT; all of it before any launch. */
+#define PFN_LOGIT_NONE 0
+#define PFN_LOGIT_L1 1
+#define PFN_LOGIT_L2 2
+#define PFN_LOGIT_FIT_INTERCEPT 4
+#define PFN_LOGIT_FOLDS 5
+#define PFN_LOGIT_SLOTS 6
+#define PFN_LOGIT_MAX_CANDIDATES 64
+#define PFN_LOGIT_UNUSED 0
+#define PFN_LOGIT_CONVERGED 1
+#define PFN_LOGIT_STALLED 2
+#define PFN_LOGIT_CAPPED 3
+#define PFN_LOGIT_ONE_CLASS 4
+#define PFN_LOGIT_NONFINITE 5
+int pfn_logistic_cv(const float* train, const float* labels, const float* test, const int32_t* fold, const float* cand_C, const int32_t* cand_kind, int P, int n,
+                    int T, int F, int NC, int n_splits, int32_t* cv_correct, float* test_z, int32_t* status, float* coef, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

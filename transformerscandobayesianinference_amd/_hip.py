@@ -135,6 +135,9 @@ SIGNATURES = {
     'pfn_auc_counts': (_I, [_P, _P, _I, _I, _P, _P]),
     # (train, labels, test, fold, P, n, T, F, cv_correct, test_pos, test_nbr, stream)
     'pfn_knn_cv': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    # logistic regression with its grid search (ABI 10, additive).  (train, labels, test, fold, cand_C, cand_kind, P, n, T, F, NC, n_splits, cv_correct, test_z, status,
+    #  coef, stream)
+    'pfn_logistic_cv': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

@@ -1703,6 +1703,22 @@ int pfn_knn_cv(const float* train, const float* labels, const float* test, const
   return PFN_OK;
 }
 
+// ---- Logistic regression with its grid search (logistic.hip; ABI 10, additive) ----
+int pfn_logistic_cv(const float* train, const float* labels, const float* test, const int32_t* fold, const float* cand_C, const int32_t* cand_kind, int P, int n, int T,
+                    int F, int NC, int n_splits, int32_t* cv_correct, float* test_z, int32_t* status, float* coef, void* stream) {
+  if (n < 4 || n > 128 || T < 1 || T > 128 || F < 1 || F > 128 || NC < 1 || NC > PFN_LOGIT_MAX_CANDIDATES)
+    return fail(PFN_ERR_UNSUPPORTED, "logistic_cv: n %d outside 4 .. 128, T %d outside 1 .. 128, F %d outside 1 .. 128 or NC %d outside 1 .. %d (one block per fit, its rows "
+                "and its Hessian in LDS)", n, T, F, NC, PFN_LOGIT_MAX_CANDIDATES);
+  if (P < 1 || n_splits < 2 || n_splits > PFN_LOGIT_FOLDS || !train || !labels || !test || !fold || !cand_C || !cand_kind || !cv_correct || !test_z || !status)
+    return fail(PFN_ERR_ARGUMENT, "bad logistic_cv arguments (P %d >= 1, 2 <= n_splits %d <= %d, train, labels, test, fold, cand_C, cand_kind, cv_correct, test_z, status "
+                "not NULL)", P, n_splits, PFN_LOGIT_FOLDS);
+  LogitCvArgs a{};
+  a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.cand_C = cand_C; a.cand_kind = cand_kind; a.P = P; a.n = n; a.T = T; a.F = F; a.NC = NC;
+  a.n_splits = n_splits; a.cv_correct = cv_correct; a.test_z = test_z; a.status = status; a.coef = coef;
+  PFN_TRY(launch_logit_cv(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
 int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
                           float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
                           uint64_t seed, uint64_t offset, void* stream) {

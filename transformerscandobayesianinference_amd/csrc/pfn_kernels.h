@@ -599,6 +599,25 @@ struct KnnCvArgs {
 inline size_t knn_cv_lds_bytes(int n, int T, int F) { return (size_t)(n + T) * (F | 1) * 4 + (size_t)n * 8; }
 int launch_knn_cv(const KnnCvArgs& a, hipStream_t s);
 
+// ---- Logistic regression with its grid search (logistic.hip): every (problem, candidate, fold slot) fit of a call in one launch -----
+struct LogitCvArgs {
+  const float* train;        // [P,n,F]
+  const float* labels;       // [P,n]: class = label > 0.5
+  const float* test;         // [P,T,F]
+  const int32_t* fold;       // [P,n]: the CV test fold of each train row
+  const float* cand_C;       // [NC]
+  const int32_t* cand_kind;  // [NC]: penalty code | PFN_LOGIT_FIT_INTERCEPT
+  int P, n, T, F, NC, n_splits;
+  int32_t* cv_correct;       // [P,NC,5]
+  float* test_z;             // [P,NC,T]
+  int32_t* status;           // [P,NC,6,2] = (exit reason, iterations)
+  float* coef;               // [P,NC,6,F+1] or null
+};
+// the n rows at an odd stride of (F + 1) | 1 floats (features, then a column of ones), H [F+1] rows at the same stride, six vectors over the rows, five over
+// the coordinates, eight words of reduction space: 138,296 bytes at n = F = 128, 37,576 at the study's n = 80, F = 60
+inline size_t logit_cv_lds_bytes(int n, int F) { return ((size_t)(n + F + 1) * ((F + 1) | 1) + 6 * (size_t)n + 5 * (size_t)(F + 1) + 8) * 4; }
+int launch_logit_cv(const LogitCvArgs& a, hipStream_t s);
+
 // ---- BNN prior sampler (mlp_prior.hip) -----------------------------------------------------------
 struct MlpPriorArgs {
   const float* weights;   // [num_models][Lmax][HP][HP]: layer l transposed ([in][out]), zero padded

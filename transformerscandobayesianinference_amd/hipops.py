@@ -547,3 +547,50 @@ def knn_cv(train, labels, test, fold):
     _hip.check(_hip.lib().pfn_knn_cv(train.data_ptr(), labels.data_ptr(), test.data_ptr(), fold.data_ptr(), P, n, T, F, cv_correct.data_ptr(), test_pos.data_ptr(),
                                      test_nbr.data_ptr(), _hip.stream_ptr(dev)), 'pfn_knn_cv')
     return cv_correct, test_pos, test_nbr
+
+
+# ---- Logistic regression with its grid search (csrc/logistic.hip; include/pfn_hip.h "Logistic regression") ----
+LOGIT_NONE, LOGIT_L1, LOGIT_L2, LOGIT_FIT_INTERCEPT = 0, 1, 2, 4      # PFN_LOGIT_*: cand_kind = penalty code | fit-intercept bit
+LOGIT_PENALTIES = {'none': LOGIT_NONE, None: LOGIT_NONE, 'l1': LOGIT_L1, 'l2': LOGIT_L2}
+LOGIT_FOLDS, LOGIT_SLOTS, LOGIT_MAX_CANDIDATES = 5, 6, 64
+LOGIT_UNUSED, LOGIT_CONVERGED, LOGIT_STALLED, LOGIT_CAPPED, LOGIT_ONE_CLASS, LOGIT_NONFINITE = 0, 1, 2, 3, 4, 5      # status[..., 0]
+LOGIT_LIMITS = dict(n=(4, 128), T=(1, 128), F=(1, 128), NC=(1, LOGIT_MAX_CANDIDATES))
+
+
+def logistic_cv_check(n, T, F, NC=1):
+    for name, v in (('n', n), ('T', T), ('F', F), ('NC', NC)):
+        lo, hi = LOGIT_LIMITS[name]
+        if not lo <= v <= hi:
+            raise ValueError(f'logistic_cv: {name} = {v} outside {lo} .. {hi}')
+
+
+def logistic_cv(train, labels, test, fold, n_splits, cand_C, cand_kind, return_coef=False):
+    """Every fit of a logistic-regression grid search in one launch (pfn_logistic_cv): train [P,n,F], labels [P,n], test [P,T,F] f32 and fold [P,n] int32 (the
+    CV test fold of each train row) on the GPU; cand_C / cand_kind: the NC candidates' C and penalty code | LOGIT_FIT_INTERCEPT (host sequences).  Slot
+    s < n_splits of a candidate is the fit without fold s, slot n_splits the refit on all rows.  Returns (cv_correct [P,NC,5] int32, test_z [P,NC,T] f32,
+    status [P,NC,6,2] int32 = (LOGIT_* exit reason, iterations), coef [P,NC,6,F+1] f32 or None)."""
+    if train.dim() != 3 or test.dim() != 3 or test.shape[0] != train.shape[0] or test.shape[2] != train.shape[2] or labels.shape != train.shape[:2] or fold.shape != train.shape[:2]:
+        raise ValueError('train [P, n, F], labels [P, n], test [P, T, F], fold [P, n]')
+    P, n, F = train.shape
+    T = test.shape[1]
+    cand_C, cand_kind = [float(v) for v in cand_C], [int(v) for v in cand_kind]
+    NC = len(cand_C)
+    logistic_cv_check(n, T, F, NC)
+    if len(cand_kind) != NC or any((k & 3) == 3 or not 0 <= k < 8 for k in cand_kind) or not all(v > 0 for v in cand_C):
+        raise ValueError('cand_C [NC] > 0, cand_kind [NC] = LOGIT_NONE / LOGIT_L1 / LOGIT_L2, optionally | LOGIT_FIT_INTERCEPT')
+    if P < 1 or not 2 <= int(n_splits) <= LOGIT_FOLDS:
+        raise ValueError(f'P >= 1, 2 <= n_splits = {n_splits} <= {LOGIT_FOLDS}')
+    _hip.require_gpu_tensor(train, 'train')
+    _bnn_f32(train, labels, test)
+    assert fold.dtype == torch.int32 and fold.is_contiguous() and fold.device == train.device, 'fold [P, n] int32'
+    dev = train.device
+    c_dev = torch.tensor(cand_C, dtype=torch.float32).to(dev)
+    k_dev = torch.tensor(cand_kind, dtype=torch.int32).to(dev)
+    cv_correct = torch.empty(P, NC, LOGIT_FOLDS, dtype=torch.int32, device=dev)
+    test_z = torch.empty(P, NC, T, dtype=torch.float32, device=dev)
+    status = torch.empty(P, NC, LOGIT_SLOTS, 2, dtype=torch.int32, device=dev)
+    coef = torch.empty(P, NC, LOGIT_SLOTS, F + 1, dtype=torch.float32, device=dev) if return_coef else None
+    _hip.check(_hip.lib().pfn_logistic_cv(train.data_ptr(), labels.data_ptr(), test.data_ptr(), fold.data_ptr(), c_dev.data_ptr(), k_dev.data_ptr(), P, n, T, F, NC,
+                                          int(n_splits), cv_correct.data_ptr(), test_z.data_ptr(), status.data_ptr(), _hip.ptr(coef), _hip.stream_ptr(dev)),
+               'pfn_logistic_cv')
+    return cv_correct, test_z, status, coef

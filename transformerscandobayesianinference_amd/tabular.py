@@ -15,7 +15,10 @@ The evaluation protocol of the reference file runs on the device:
 `evaluate_position` gathers and normalises every (window, test row) column in one launch (pfn_tabular_windows), runs the PFN once
 at batch windows x test rows, and counts ROC-AUC pairs on the device (pfn_auc_counts); the kNN baseline finds the neighbour lists of
 every CV fold and every test row of every window in one launch (pfn_knn_cv) and does the grid-search arithmetic on the host in f64.
-The other baselines of the reference (logistic regression, GP / BNN classifiers, XGBoost, CatBoost: :325-677) and the OpenML loaders
+    logistic_metric (with its grid search over 108 parameter sets)   :325-346
+solves every candidate and fold of every window to its optimum in one launch (pfn_logistic_cv); the grid, the folds and the scores are host
+arithmetic in f64.
+The other baselines of the reference (GP / BNN classifiers, XGBoost, CatBoost: :372-677) and the OpenML loaders
 stay out: they need libraries and network access this stack does not carry.  Any callable with the reference's metric-function
 signature still runs through `batch_pred`, one window at a time, as the reference loops.
 
@@ -418,3 +421,86 @@ def knn_metric(x, y, test_x, test_y, cat_features):
 
 
 knn_metric.batched = _knn_batched
+
+
+## Logistic regression (reference tabular.py:325-346)
+
+param_grid = {}
+param_grid['logistic'] = {'solver': ['saga'], 'penalty': ['l1', 'l2', 'none'], 'tol': [1e-2, 1e-4, 1e-10], 'max_iter': [500], 'fit_intercept': [True, False],
+                          'C': [1e-5, 0.001, 0.01, 0.1, 1.0, 2.0]}
+
+
+def _logistic_grid(grid=None):
+    """The reference's grid as the device solves it: (entries, cands, entry_fit).  `entries` are the parameter dicts in sklearn's ParameterGrid order (keys
+    sorted, the last key varying fastest: 108 of them); `cands` the distinct fits [(C, penalty code | fit-intercept bit)] in order of first appearance -- tol,
+    max_iter and solver do not change a fit that is solved to its optimum, and 'none' ignores C (1 stands in): 26 --; entry_fit [entries] indexes `cands`."""
+    import itertools
+    grid = param_grid['logistic'] if grid is None else grid
+    keys = sorted(grid)
+    entries = [dict(zip(keys, values)) for values in itertools.product(*(grid[k] for k in keys))]
+    cands, entry_fit, where = [], [], {}
+    for e in entries:
+        penalty = hipops.LOGIT_PENALTIES[e['penalty']]
+        key = (1.0 if penalty == hipops.LOGIT_NONE else float(e['C']), penalty | (hipops.LOGIT_FIT_INTERCEPT if e['fit_intercept'] else 0))
+        if key not in where:
+            where[key] = len(cands)
+            cands.append(key)
+        entry_fit.append(where[key])
+    return entries, cands, np.asarray(entry_fit)
+
+
+def _logistic_select(cv_correct, status, folds, n_splits, entry_fit, test_z):
+    """The host half of one problem's grid search, from the kernel's results: cv_correct [NC, 5] counts, status [NC, 6, 2], folds [n] the rows' test folds,
+    entry_fit [entries] the fit of every grid entry, test_z [NC, T] the refits' decision values.  As GridSearchCV scores it: a fold's score is its accuracy
+    correct / size in f64 -- NaN where the fold's training part holds one class (the fit fails, error_score = nan) --, a candidate's score the mean over folds,
+    the best entry the FIRST maximum over the full entry order (NaN ranks last; where a failed fold leaves every mean NaN that is entry 0, as in sklearn),
+    predict_proba[:, 1] = sigmoid(decision value of its refit) in f64.
+    Returns (mean_test_score [entries] f64, best entry index, proba [T] f64); raises ValueError when every fit of every candidate failed."""
+    sizes = np.bincount(np.asarray(folds), minlength=n_splits)[:n_splits].astype(np.float64)
+    scores = np.asarray(cv_correct, dtype=np.float64)[:, :n_splits] / sizes
+    failed = np.asarray(status)[:, :n_splits, 0] == hipops.LOGIT_ONE_CLASS
+    if failed.all():
+        raise ValueError('logistic_metric: every fit of every candidate failed (each fold\'s training part holds one class)')
+    scores[failed] = np.nan
+    mean = scores.mean(axis=1)[np.asarray(entry_fit)]
+    best = int(np.argmax(np.where(np.isnan(mean), -np.inf, mean)))
+    z = np.asarray(test_z, dtype=np.float64)[entry_fit[best]]
+    e = np.exp(-np.abs(z))
+    proba = np.where(z >= 0, 1 / (1 + e), e / (1 + e))
+    return mean, best, proba
+
+
+def _logistic_batched(x, y, test_x, test_y, return_params=False):
+    """Logistic regression with the reference's grid search for W problems at once: x [n, W, F] normalised train rows, y [n, W], test_x [T, W, F], test_y [T, W]
+    on the GPU.  One pfn_logistic_cv launch solves all W x 26 x (folds + 1) fits; the folds (before) and the scores (after) are host arithmetic.  Returns
+    (ROC-AUC [W], proba [T, W]) numpy, and with return_params the chosen parameter dict of every problem as a third entry.  Raises ValueError, as sklearn's fit
+    does, for a window whose train rows hold one class."""
+    n, W, F = x.shape
+    T = test_x.shape[0]
+    entries, cands, entry_fit = _logistic_grid()
+    hipops.logistic_cv_check(n, T, F, len(cands))
+    n_splits = min(CV, n // 2)
+    y_host = y.detach().cpu().numpy() > 0.5
+    for w in range(W):
+        if y_host[:, w].all() or not y_host[:, w].any():
+            raise ValueError(f'logistic_metric: the train rows of window {w} hold one class only')
+    folds = np.stack([_stratified_folds(y_host[:, w], n_splits) for w in range(W)])      # [W, n]
+    cv_correct, test_z, status, _ = hipops.logistic_cv(x.float().transpose(0, 1).contiguous(), y.float().t().contiguous(), test_x.float().transpose(0, 1).contiguous(),
+                                                       torch.from_numpy(folds).to(x.device), n_splits, [c for c, _ in cands], [k for _, k in cands])
+    cv_correct, test_z, status = cv_correct.cpu().numpy(), test_z.cpu().numpy(), status.cpu().numpy()
+    chosen = [_logistic_select(cv_correct[w], status[w], folds[w], n_splits, entry_fit, test_z[w]) for w in range(W)]
+    proba = np.stack([c[2] for c in chosen], 1)      # [T, W]
+    metric, undefined = roc_auc_columns(torch.from_numpy(proba).float().to(x.device), test_y)
+    _report_undefined(undefined, f'of {W} windows')
+    return (metric, proba, [entries[c[1]] for c in chosen]) if return_params else (metric, proba)
+
+
+def logistic_metric(x, y, test_x, test_y, cat_features):
+    """Reference tabular.py:326-346 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (ROC-AUC, proba [T]) of
+    the LogisticRegression that GridSearchCV picks from param_grid['logistic'] by min(5, n // 2)-fold stratified cross-validation, every candidate solved to its
+    optimum.  `logistic_metric.batched` is the same for many problems in one launch; `batch_pred` uses it."""
+    metric, proba = _logistic_batched(x[:, None], y[:, None], test_x[:, None], test_y[:, None])
+    return metric[0], proba[:, 0]
+
+
+logistic_metric.batched = _logistic_batched

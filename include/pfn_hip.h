@@ -625,6 +625,47 @@ int pfn_knn_cv(const float* train, const float* labels, const float* test, const
 int pfn_logistic_cv(const float* train, const float* labels, const float* test, const int32_t* fold, const float* cand_C, const int32_t* cand_kind, int P, int n,
                     int T, int F, int NC, int n_splits, int32_t* cv_correct, float* test_z, int32_t* status, float* coef, void* stream);
 
+/* ---- GP classifier with its grid search (ABI 10, additive; csrc/gpc.hip): the reference's gp_metric (tabular.py:480-503), i.e. scikit-learn's binary
+ * GaussianProcessClassifier under the kernel c * RBF(l), as a batch of independent Laplace fits.  f32 data and arithmetic, caller-owned buffers, stream-ordered, no
+ * allocation, no workspace, no host synchronisation, no global atomics.  The optimiser over theta is the caller's.
+ *
+ * Both calls: P problems; theta [P,NC,6,2] = (log c, log l) of every fit; train [P,n,F], labels [P,n] (class = label > 0.5), fold [P,n] int32 (the CV test fold
+ *   of each train row).  One block per fit (problem p, candidate c, slot s): slot s < n_splits trains on the rows with fold[p,i] != s (compacted: held-out rows
+ *   are not in K), slot s = n_splits on all rows (the refit), slots beyond are unused (status PFN_GPC_UNUSED).  A result is a bitwise function of its own
+ *   (problem, theta, slot), wherever it sits in the call.
+ *   Model: K = c exp(-d^2 / 2 l^2), no jitter.  Posterior mode by GPML algorithm 3.1 from f = 0 on every call (no warm start): pi = sigma(f), W = pi (1 - pi),
+ *   B = I + W^1/2 K W^1/2 = L L^T, b = W f + (y - pi), a = b - W^1/2 B^-1 W^1/2 K b, f = K a, Z = -1/2 a.f - sum softplus(-(2y - 1) f) - sum log L_ii; as in
+ *   scikit-learn, pi, W and L are those of the last iteration, one step behind f.  Newton stops PFN_GPC_CONVERGED two iterations after the first whose change
+ *   of Z -- summed from the rows' term differences, not a difference of two totals -- is below 2^-20 max(1, |Z|) (scikit-learn: below 1e-10, in f64; the two
+ *   further iterations bring the one-step-behind pi to f32's floor), or PFN_GPC_CAPPED after PFN_GPC_MAX_NEWTON = 100 iterations (scikit-learn's max_iter_predict).
+ *   A non-positive pivot of B (PFN_GPC_NONPOSITIVE) or a non-finite Z or gradient (PFN_GPC_NONFINITE) fails that fit only.  A fit whose training rows hold one
+ *   class is not run: PFN_GPC_ONE_CLASS.
+ *   status [P,NC,6,2] int32 = (exit reason, Newton iterations).
+ * pfn_gpc_lml_grad: value [P,NC,6] = -Z, grad [P,NC,6,2] = -dZ/dtheta by GPML algorithm 5.1 (K_0 = K, K_1 = K * d^2 / l^2), with tr(R K) = n - tr(B^-1) and
+ *   s_2 = -1/2 (1 - diag(B^-1)) (1 - 2 pi) taken through B^-1 = L^-T L^-1 (the same numbers; they do not cancel in f32 where K is near rank one).  A failed fit
+ *   gives +inf and a zero gradient, a one-class fit NaN and a zero gradient, an unused slot zeros.
+ * pfn_gpc_predict: finds the mode at theta once more; test [P,T,F].  A decision value f* = k*^T (y - pi) is written as a pair (m, e) with f* = m exp(-e): e the
+ *   smallest exponent argument d^2 / 2 l^2 over the fit's training rows, m = sum_i c exp(e - d_i^2 / 2 l^2) (y_i - pi_i) -- the sign of f* survives where exp
+ *   underflows in f32; the caller forms f* in f64.  Slot s < n_splits writes cv_f [P,NC,n,2] at its held-out rows (fold == s) only; a row in no fold is never
+ *   written.  The refit slot writes test_f [P,NC,T,2] and test_var [P,NC,T] = max(c - |L^-1 W^1/2 k*|^2, 0).  A failed or one-class fit writes NaN there.
+ *   4 <= n <= PFN_GPC_MAX_N = 112 (three n x n matrices in 160 KB of LDS), 1 <= T <= 128, 1 <= F <= 128, 1 <= NC <= 64 else PFN_ERR_UNSUPPORTED; P >= 1,
+ *   2 <= n_splits <= 5 and non-NULL buffers else PFN_ERR_ARGUMENT; all of it before any launch. */
+#define PFN_GPC_FOLDS 5
+#define PFN_GPC_SLOTS 6
+#define PFN_GPC_MAX_CANDIDATES 64
+#define PFN_GPC_MAX_N 112
+#define PFN_GPC_MAX_NEWTON 100
+#define PFN_GPC_UNUSED 0
+#define PFN_GPC_CONVERGED 1
+#define PFN_GPC_CAPPED 2
+#define PFN_GPC_ONE_CLASS 3
+#define PFN_GPC_NONPOSITIVE 4
+#define PFN_GPC_NONFINITE 5
+int pfn_gpc_lml_grad(const float* theta, const float* train, const float* labels, const int32_t* fold, int P, int n, int F, int NC, int n_splits, float* value,
+                     float* grad, int32_t* status, void* stream);
+int pfn_gpc_predict(const float* theta, const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F, int NC,
+                    int n_splits, float* cv_f, float* test_f, float* test_var, int32_t* status, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

@@ -1,0 +1,213 @@
+"""Record the fixture of the GP-classifier tests (CPU only; scikit-learn is the oracle that the f64 restatement tests/gpc_f64.py is checked against):
+
+    python tools/record_gpc_fixtures.py
+
+tests/golden/tabular_gpc.pt   per shape of tests/gpc_f64.SHAPES one seeded problem (its seed and labels; the rows are drawn again from the seed), and one window of the diabetes rows at n = 30 (float32 inputs, normalised as
+                              batch_pred normalises), each with StratifiedKFold's fold assignment and, from the f64 restatement:
+  thetas [32, 2]              the 24 starts of the grid and 8 further theta (log c <= 5); Z and dZ/dtheta of every slot's fit at each of them
+  gs                          the decision values (m, e), their masses, the variances and the status of every slot's fit at each of the 32 theta
+  mean_test_score, best, proba   the optimize=False grid search over the 24 candidates
+  pipeline                    the optimising pipeline in f64 (batched_lbfgs on the restatement, the box applied as tabular._gp_objective applies it): final theta and
+                              Z of all 24 x (folds + 1) fits, the scores and the best kernel; beside them scikit-learn's own end values of Z and theta, its
+                              mean_test_score and best_index_
+Asserted here (and again by tests/test_host_gpc.py from the file, where scikit-learn is installed):
+  * Z and dZ/dtheta equal GaussianProcessClassifier.log_marginal_likelihood(theta, eval_gradient=True) to 1e-9 of |Z| on every slot's training rows;
+  * predict and predict_proba of the refits equal scikit-learn's with optimizer=None to 1e-10;
+  * the optimize=False grid search equals GridSearchCV(GaussianProcessClassifier(optimizer=None), ...) in mean_test_score, best_index_ and probabilities.
+Condition on a problem (the next seed, + 100, is tried until it holds): the GPU decides (f* > 0) from f32 pairs, so the recorder runs the restatement in f32,
+takes 8 x its worst error of m (a share of the mass sum_i |term_i|) as the window in which a held-out row may flip, and wants at most 1 % of the problem's
+(held-out row, fit) pairs inside it or with e in [700, 760], where exp(-e) leaves f64's range."""
+import os
+import sys
+import tempfile
+import warnings
+from multiprocessing import Pool
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import gpc_f64 as gf      # noqa: E402
+from transformerscandobayesianinference_amd import tabular      # noqa: E402
+from transformerscandobayesianinference_amd.priors.fast_gp_mix import batched_lbfgs      # noqa: E402
+
+LBFGS_F64 = dict(gtol=1e-5, ftol=1e-9, max_iter=100)
+
+
+def sk_kernel(theta):
+    from sklearn.gaussian_process.kernels import RBF, ConstantKernel
+    return ConstantKernel(float(np.exp(theta[0]))) * RBF(float(np.exp(theta[1])))
+
+
+def _lml(args):
+    return gf.lml_grad(*args)
+
+
+def left_out(gs, folds, n_splits, window):
+    """(pairs left out, pairs) over the 24 grid candidates: held-out rows whose f64 |m| lies within `window` of its mass, or whose e lies in [700, 760]."""
+    out = total = 0
+    for c in range(24):
+        for s in range(n_splits):
+            held = folds == s
+            if gs['status'][c, s, 0] not in (gf.CONVERGED, gf.CAPPED):
+                continue
+            m, e, mass = gs['cv_f'][c, held, 0], gs['cv_f'][c, held, 1], gs['cv_mass'][c, held]
+            total += int(held.sum())
+            out += int(((np.abs(m) <= window * mass) | ((e >= 700) & (e <= 760))).sum())
+    return out, total
+
+
+def check_values_against_sklearn(x, y, folds, n_splits, thetas, Z, dZ):
+    from sklearn.gaussian_process import GaussianProcessClassifier
+    worst = 0.
+    for s in range(n_splits + 1):
+        rows = gf.slot_rows(folds, n_splits, s)
+        if gf.one_class(y[rows]):
+            assert np.isnan(Z[:, s]).all()
+            continue
+        gp = GaussianProcessClassifier(kernel=sk_kernel(thetas[0]), optimizer=None).fit(x[rows].astype(np.float64), y[rows])
+        for k, th in enumerate(thetas):
+            Zs, gs_ = gp.log_marginal_likelihood(th, eval_gradient=True)
+            err = max(abs(Z[k, s] - Zs), np.abs(dZ[k, s] - gs_).max()) / abs(Zs)
+            assert err <= 1e-9, (s, th, err)
+            worst = max(worst, err)
+    return worst
+
+
+def check_fixed_grid_against_sklearn(x, y, test_x, folds, n_splits, gs, mean, best, proba):
+    from sklearn.gaussian_process import GaussianProcessClassifier
+    from sklearn.model_selection import GridSearchCV
+    x64, t64 = x.astype(np.float64), test_x.astype(np.float64)
+    thetas = gf.grid_theta()
+    worst = 0.
+    for c, th in enumerate(thetas):      # every refit: predict and predict_proba
+        gp = GaussianProcessClassifier(kernel=sk_kernel(th), optimizer=None).fit(x64, y)
+        fs = gf.f_star(gs['test_f'][c, :, 0], gs['test_f'][c, :, 1])
+        assert np.array_equal(gp.predict(t64) > 0.5, fs > 0), c
+        err = float(np.abs(gp.predict_proba(t64)[:, 1] - gf.proba(fs, gs['test_var'][c])).max())
+        assert err <= 1e-10, (c, err)
+        worst = max(worst, err)
+    search = GridSearchCV(GaussianProcessClassifier(optimizer=None), {'kernel': [sk_kernel(th) for th in thetas]}, cv=n_splits).fit(x64, y.astype(np.int64))
+    assert search.cv_results_['mean_test_score'].tobytes() == mean.tobytes(), (search.cv_results_['mean_test_score'], mean)
+    assert search.best_index_ == best
+    assert np.abs(search.predict_proba(t64)[:, 1] - proba).max() <= 1e-10
+    return worst
+
+
+def pipeline_f64(x, y, test_x, folds, n_splits, pool):
+    """batched_lbfgs in f64 on the restatement from the 24 starts, every slot its own fit; then the grid search at the final thetas."""
+    starts = np.repeat(gf.grid_theta()[:, None, :], n_splits + 1, 1).reshape(-1, 2)
+    rows = [gf.slot_rows(folds, n_splits, s) for s in range(n_splits + 1)]
+    data = [(x[r], y[r]) for r in rows]
+    cache = {}
+    passes = [0]
+
+    def fun(theta):
+        passes[0] += 1
+        th = theta.numpy()
+        inside = np.clip(th, *gf.BOX)
+        todo = [(k, tuple(inside[k])) for k in range(len(th)) if (k, tuple(inside[k])) not in cache]
+        for (k, key), (Z, g, _) in zip(todo, pool.map(_lml, [(*data[k % (n_splits + 1)], np.array(key)) for k, key in todo])):
+            cache[k, key] = (-Z, gf.project(th[k], -g) if np.isfinite(Z) else np.zeros(2))
+        got = [cache[k, tuple(inside[k])] for k in range(len(th))]
+        return torch.tensor([v for v, _ in got], dtype=torch.float64), torch.tensor(np.stack([g for _, g in got]), dtype=torch.float64)
+    res = batched_lbfgs(fun, torch.from_numpy(starts), **LBFGS_F64)
+    theta = np.clip(res['theta'].numpy(), *gf.BOX).reshape(24, n_splits + 1, 2)
+    Z = -res['objective'].numpy().reshape(24, n_splits + 1)
+    gs = gf.grid_search(x, y, test_x, folds, n_splits, theta)
+    mean, best, _ = gf.select(gs['cv_f'], gs['status'], folds, y, n_splits)
+    return dict(theta=theta, Z=Z, converged=res['converged'].numpy().reshape(24, n_splits + 1), passes=passes[0], mean_test_score=mean, best=best,
+                proba=gf.proba(gf.f_star(gs['test_f'][best, :, 0], gs['test_f'][best, :, 1]), gs['test_var'][best]))
+
+
+def sklearn_pipeline(x, y, test_x, folds, n_splits):
+    """scikit-learn's own optimised fits: end value of Z and theta of all 24 x (folds + 1) fits, and its grid search."""
+    from sklearn.gaussian_process import GaussianProcessClassifier
+    from sklearn.model_selection import GridSearchCV
+    x64 = x.astype(np.float64)
+    Z, theta = np.full((24, n_splits + 1), np.nan), np.full((24, n_splits + 1, 2), np.nan)
+    for c, th in enumerate(gf.grid_theta()):
+        for s in range(n_splits + 1):
+            rows = gf.slot_rows(folds, n_splits, s)
+            if gf.one_class(y[rows]):
+                continue
+            gp = GaussianProcessClassifier(kernel=sk_kernel(th)).fit(x64[rows], y[rows])
+            Z[c, s], theta[c, s] = gp.log_marginal_likelihood_value_, gp.kernel_.theta
+    search = GridSearchCV(GaussianProcessClassifier(), {'kernel': [sk_kernel(th) for th in gf.grid_theta()]}, cv=n_splits).fit(x64, y.astype(np.int64))
+    return dict(Z=Z, theta=theta, mean_test_score=search.cv_results_['mean_test_score'], best=int(search.best_index_),
+                proba=search.predict_proba(test_x.astype(np.float64))[:, 1])
+
+
+def diabetes_window(start, n=30, T=10):
+    d = torch.load(os.path.join(ROOT, 'tests', 'golden', 'tabular_diabetes.pt'))
+    X, y = d['X'][start:start + n + T].double(), d['y'][start:start + n + T]
+    X = ((X - X[:n].mean(0)) / (X[:n].std(0) + .000001)).float().numpy()
+    y = y.float().numpy()
+    return X[:n], y[:n], X[n:], y[n:]
+
+
+def record(name, draw, first_seed, pool):
+    for seed in range(first_seed, first_seed + 5000, 100):
+        x, y, test_x, test_y = draw(seed)
+        n, F, T = len(x), x.shape[1], len(test_x)
+        n_splits = min(tabular.CV, n // 2)
+        try:
+            folds = tabular._stratified_folds(y > 0.5, n_splits)
+        except ValueError:
+            continue
+        thetas = np.concatenate([gf.grid_theta(), gf.extra_thetas(seed)])
+        per_slot = np.repeat(thetas[:, None, :], n_splits + 1, 1)
+        gs = gf.grid_search(x, y, test_x, folds, n_splits, per_slot)
+        gs32 = gf.grid_search(x, y, test_x, folds, n_splits, per_slot, dtype=np.float32)
+        ok = np.isfinite(gs['cv_f'][:24, :, 0]) & np.isfinite(gs32['cv_f'][:24, :, 0])
+        est = float((np.abs(gs32['cv_f'][:24, :, 0] - gs['cv_f'][:24, :, 0])[ok] / gs['cv_mass'][:24][ok]).max()) if ok.any() else 0.
+        window = 8 * est
+        out, total = left_out(gs, folds, n_splits, window)
+        mean, best, _ = gf.select(gs['cv_f'][:24], gs['status'][:24], folds, y, n_splits)
+        if out > 0.01 * max(total, 1) or np.isnan(mean).all():
+            print(f'  {name} seed {seed}: {out} of {total} held-out pairs within {window:.1e} of their mass or at the edge of f64: next seed')
+            continue
+        proba = gf.proba(gf.f_star(gs['test_f'][best, :, 0], gs['test_f'][best, :, 1]), gs['test_var'][best])
+        values = pool.map(_lml, [(x[gf.slot_rows(folds, n_splits, s)], y[gf.slot_rows(folds, n_splits, s)], th) for th in thetas for s in range(n_splits + 1)])
+        Z = np.array([v[0] for v in values]).reshape(len(thetas), n_splits + 1)
+        dZ = np.stack([v[1] for v in values]).reshape(len(thetas), n_splits + 1, 2)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            worst_z = check_values_against_sklearn(x, y, folds, n_splits, thetas, Z, dZ)
+            worst_p = check_fixed_grid_against_sklearn(x, y, test_x, folds, n_splits, gs, mean, best, proba)
+            pipe = pipeline_f64(x, y, test_x, folds, n_splits, pool)
+            sk = sklearn_pipeline(x, y, test_x, folds, n_splits)
+        both = np.isfinite(sk['Z']) & np.isfinite(pipe['Z'])
+        close = np.abs(pipe['Z'] - sk['Z'])[both] <= 1e-3 * np.maximum(1, np.abs(sk['Z'][both]))
+        print(f'{name} {(n, F, T)} seed {seed}: scikit-learn agrees on Z, dZ to {worst_z:.1e} and on predict_proba to {worst_p:.1e}; f32 restatement {est:.1e} of the '
+              f'mass away, {out} of {total} pairs left out; best {best} score {mean[best]:.4f}; f64 pipeline: {pipe["passes"]} passes, '
+              f'{int(pipe["converged"].sum())} of {pipe["converged"].size} converged, {int(close.sum())} of {int(both.sum())} fits within 1e-3 of scikit-learn\'s Z, best '
+              f'{pipe["best"]} vs scikit-learn\'s {sk["best"]}')
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+        gs = {k: (v.astype(np.float32) if k.endswith('mass') else v) for k, v in gs.items()}      # a mass only scales a bound
+        rows = dict(x=t(x), test_x=t(test_x)) if name.startswith('diabetes') else {}      # a seeded problem's rows are drawn again from its seed (gpc_f64.attach_rows)
+        return dict(name=name, n=n, F=F, T=T, seed=seed, y=t(y), test_y=t(test_y), folds=t(folds), n_splits=n_splits, thetas=t(thetas), Z=t(Z), **rows,
+                    dZ=t(dZ), gs={k: t(v) for k, v in gs.items()}, mean_test_score=t(mean), best=best, proba=t(proba), flip_window=window, f32_restatement_distance=est,
+                    left_out=(out, total), pipeline={k: (t(v) if isinstance(v, np.ndarray) else v) for k, v in pipe.items()},
+                    sklearn={k: (t(v) if isinstance(v, np.ndarray) else v) for k, v in sk.items()})
+    raise SystemExit(f'no seed meets the conditions for problem {name}')
+
+
+def main():
+    only = sys.argv[1:]
+    with Pool(min(16, os.cpu_count() or 1)) as pool:
+        problems = []
+        for n, F, T in gf.SHAPES:
+            if not only or str(n) in only:
+                problems.append(record(f'n{n}_F{F}_T{T}', lambda seed, n=n, F=F, T=T: gf.problem(n, F, T, seed), n, pool))
+        if not only or 'diabetes' in only:
+            problems.append(record('diabetes_n30', lambda seed: diabetes_window(seed // 100 * 7), 0, pool))
+    path = os.path.join(ROOT, 'tests', 'golden', 'tabular_gpc.pt') if not only else os.path.join(tempfile.gettempdir(), 'tabular_gpc_partial.pt')
+    torch.save({'problems': problems, 'grid': gf.grid()}, path)
+    print('recorded', len(problems), 'problems,', os.path.getsize(path), 'bytes')
+
+
+if __name__ == '__main__':
+    main()

@@ -138,6 +138,10 @@ SIGNATURES = {
     # logistic regression with its grid search (ABI 10, additive).  (train, labels, test, fold, cand_C, cand_kind, P, n, T, F, NC, n_splits, cv_correct, test_z, status,
     #  coef, stream)
     'pfn_logistic_cv': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    # GP classifier with its grid search (ABI 10, additive).  (theta, train, labels, fold, P, n, F, NC, n_splits, value, grad, status, stream)
+    'pfn_gpc_lml_grad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    # (theta, train, labels, test, fold, P, n, T, F, NC, n_splits, cv_f, test_f, test_var, status, stream)
+    'pfn_gpc_predict': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

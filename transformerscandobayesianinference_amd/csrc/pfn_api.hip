@@ -1719,6 +1719,34 @@ int pfn_logistic_cv(const float* train, const float* labels, const float* test, 
   return PFN_OK;
 }
 
+// ---- GP classifier with its grid search (gpc.hip; ABI 10, additive) ----
+static int gpc_shapes(const char* what, int P, int n, int T, int F, int NC, int n_splits, bool pointers) {
+  if (n < 4 || n > PFN_GPC_MAX_N || T < 1 || T > 128 || F < 1 || F > 128 || NC < 1 || NC > PFN_GPC_MAX_CANDIDATES)
+    return fail(PFN_ERR_UNSUPPORTED, "%s: n %d outside 4 .. %d, T %d outside 1 .. 128, F %d outside 1 .. 128 or NC %d outside 1 .. %d (one block per fit, three n x n "
+                "matrices in LDS)", what, n, PFN_GPC_MAX_N, T, F, NC, PFN_GPC_MAX_CANDIDATES);
+  if (P < 1 || n_splits < 2 || n_splits > PFN_GPC_FOLDS || !pointers)
+    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (P %d >= 1, 2 <= n_splits %d <= %d, no NULL buffer)", what, P, n_splits, PFN_GPC_FOLDS);
+  return PFN_OK;
+}
+int pfn_gpc_lml_grad(const float* theta, const float* train, const float* labels, const int32_t* fold, int P, int n, int F, int NC, int n_splits, float* value,
+                     float* grad, int32_t* status, void* stream) {
+  if (const int rc = gpc_shapes("gpc_lml_grad", P, n, 1, F, NC, n_splits, theta && train && labels && fold && value && grad && status)) return rc;
+  GpcArgs a{};
+  a.theta = theta; a.train = train; a.labels = labels; a.fold = fold; a.P = P; a.n = n; a.T = 1; a.F = F; a.NC = NC; a.n_splits = n_splits; a.value = value; a.grad = grad;
+  a.status = status;
+  PFN_TRY(launch_gpc_lml_grad(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_gpc_predict(const float* theta, const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F, int NC, int n_splits,
+                    float* cv_f, float* test_f, float* test_var, int32_t* status, void* stream) {
+  if (const int rc = gpc_shapes("gpc_predict", P, n, T, F, NC, n_splits, theta && train && labels && test && fold && cv_f && test_f && test_var && status)) return rc;
+  GpcArgs a{};
+  a.theta = theta; a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.P = P; a.n = n; a.T = T; a.F = F; a.NC = NC; a.n_splits = n_splits; a.cv_f = cv_f;
+  a.test_f = test_f; a.test_var = test_var; a.status = status;
+  PFN_TRY(launch_gpc_predict(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
 int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
                           float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
                           uint64_t seed, uint64_t offset, void* stream) {

@@ -618,6 +618,27 @@ struct LogitCvArgs {
 inline size_t logit_cv_lds_bytes(int n, int F) { return ((size_t)(n + F + 1) * ((F + 1) | 1) + 6 * (size_t)n + 5 * (size_t)(F + 1) + 8) * 4; }
 int launch_logit_cv(const LogitCvArgs& a, hipStream_t s);
 
+// ---- GP classifier with its grid search (gpc.hip): the Laplace fit of every (problem, candidate, fold slot) of a call in one launch -----
+struct GpcArgs {
+  const float* theta;        // [P,NC,6,2] = (log c, log l) of every fit
+  const float* train;        // [P,n,F]
+  const float* labels;       // [P,n]: class = label > 0.5
+  const float* test;         // [P,T,F] (predict)
+  const int32_t* fold;       // [P,n]: the CV test fold of each train row
+  int P, n, T, F, NC, n_splits;
+  float* value;              // [P,NC,6] = -Z (lml_grad)
+  float* grad;               // [P,NC,6,2] = -dZ/dtheta (lml_grad)
+  int32_t* status;           // [P,NC,6,2] = (exit reason, Newton iterations)
+  float* cv_f;               // [P,NC,n,2] (predict): (m, e) of every held-out row
+  float* test_f;             // [P,NC,T,2] (predict)
+  float* test_var;           // [P,NC,T] (predict)
+};
+// K, the exponent arguments and the factor (inverted in place for the gradient) at the odd stride n | 1, sixteen vectors over the rows, eight words of reduction space:
+// 159,072 bytes at n = 112, 82,912 at the study's n = 80
+inline size_t gpc_lds_bytes(int n) { return ((size_t)3 * n * (n | 1) + 16 * (size_t)n + 8) * 4; }
+int launch_gpc_lml_grad(const GpcArgs& a, hipStream_t s);
+int launch_gpc_predict(const GpcArgs& a, hipStream_t s);
+
 // ---- BNN prior sampler (mlp_prior.hip) -----------------------------------------------------------
 struct MlpPriorArgs {
   const float* weights;   // [num_models][Lmax][HP][HP]: layer l transposed ([in][out]), zero padded

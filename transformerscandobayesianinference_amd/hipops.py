@@ -594,3 +594,61 @@ def logistic_cv(train, labels, test, fold, n_splits, cand_C, cand_kind, return_c
                                           int(n_splits), cv_correct.data_ptr(), test_z.data_ptr(), status.data_ptr(), _hip.ptr(coef), _hip.stream_ptr(dev)),
                'pfn_logistic_cv')
     return cv_correct, test_z, status, coef
+
+
+# ---- GP classifier with its grid search (csrc/gpc.hip; include/pfn_hip.h "GP classifier") ----
+GPC_FOLDS, GPC_SLOTS, GPC_MAX_CANDIDATES, GPC_MAX_N, GPC_MAX_NEWTON = 5, 6, 64, 112, 100
+GPC_UNUSED, GPC_CONVERGED, GPC_CAPPED, GPC_ONE_CLASS, GPC_NONPOSITIVE, GPC_NONFINITE = 0, 1, 2, 3, 4, 5      # status[..., 0]
+GPC_LIMITS = dict(n=(4, GPC_MAX_N), T=(1, 128), F=(1, 128), NC=(1, GPC_MAX_CANDIDATES))
+
+
+def gpc_check(n, T, F, NC=1):
+    for name, v in (('n', n), ('T', T), ('F', F), ('NC', NC)):
+        lo, hi = GPC_LIMITS[name]
+        if not lo <= v <= hi:
+            raise ValueError(f'gpc: {name} = {v} outside {lo} .. {hi}')
+
+
+def _gpc_args(theta, train, labels, fold, n_splits, test=None):
+    if train.dim() != 3 or labels.shape != train.shape[:2] or fold.shape != train.shape[:2] or theta.dim() != 4 or theta.shape[0] != train.shape[0] or \
+            tuple(theta.shape[2:]) != (GPC_SLOTS, 2) or (test is not None and (test.dim() != 3 or test.shape[0] != train.shape[0] or test.shape[2] != train.shape[2])):
+        raise ValueError('theta [P, NC, 6, 2], train [P, n, F], labels [P, n], fold [P, n], test [P, T, F]')
+    P, n, F = train.shape
+    NC = theta.shape[1]
+    gpc_check(n, 1 if test is None else test.shape[1], F, NC)
+    if P < 1 or not 2 <= int(n_splits) <= GPC_FOLDS:
+        raise ValueError(f'P >= 1, 2 <= n_splits = {n_splits} <= {GPC_FOLDS}')
+    _hip.require_gpu_tensor(train, 'train')
+    _bnn_f32(train, labels, theta, *(() if test is None else (test,)))
+    assert fold.dtype == torch.int32 and fold.is_contiguous() and fold.device == train.device, 'fold [P, n] int32'
+    return P, n, F, NC
+
+
+def gpc_lml_grad(theta, train, labels, fold, n_splits):
+    """-Z and -dZ/dtheta of the Laplace approximation of every fit of a GP-classifier grid search in one launch (pfn_gpc_lml_grad): theta [P,NC,6,2] f32 =
+    (log c, log l) per (problem, candidate, slot), train [P,n,F], labels [P,n] f32, fold [P,n] int32 on the GPU.  Slot s < n_splits is the fit without fold s,
+    slot n_splits the refit on all rows.  Returns (value [P,NC,6], grad [P,NC,6,2], status [P,NC,6,2] int32 = (GPC_* exit reason, Newton iterations))."""
+    P, n, F, NC = _gpc_args(theta, train, labels, fold, n_splits)
+    dev = train.device
+    value = torch.empty(P, NC, GPC_SLOTS, dtype=torch.float32, device=dev)
+    grad = torch.empty(P, NC, GPC_SLOTS, 2, dtype=torch.float32, device=dev)
+    status = torch.empty(P, NC, GPC_SLOTS, 2, dtype=torch.int32, device=dev)
+    _hip.check(_hip.lib().pfn_gpc_lml_grad(theta.data_ptr(), train.data_ptr(), labels.data_ptr(), fold.data_ptr(), P, n, F, NC, int(n_splits), value.data_ptr(),
+                                           grad.data_ptr(), status.data_ptr(), _hip.stream_ptr(dev)), 'pfn_gpc_lml_grad')
+    return value, grad, status
+
+
+def gpc_predict(theta, train, labels, test, fold, n_splits):
+    """The decision values of every fit of a GP-classifier grid search at its theta in one launch (pfn_gpc_predict); arguments as gpc_lml_grad plus test
+    [P,T,F].  Returns (cv_f [P,NC,n,2], test_f [P,NC,T,2], test_var [P,NC,T], status [P,NC,6,2]): a decision value is the pair (m, e), f* = m exp(-e), to be
+    formed in f64; cv_f holds row i's pair from the fit that held it out (NaN-filled where no fit did), test_f / test_var are the refit's."""
+    P, n, F, NC = _gpc_args(theta, train, labels, fold, n_splits, test)
+    T = test.shape[1]
+    dev = train.device
+    cv_f = torch.full((P, NC, n, 2), float('nan'), dtype=torch.float32, device=dev)
+    test_f = torch.empty(P, NC, T, 2, dtype=torch.float32, device=dev)
+    test_var = torch.empty(P, NC, T, dtype=torch.float32, device=dev)
+    status = torch.empty(P, NC, GPC_SLOTS, 2, dtype=torch.int32, device=dev)
+    _hip.check(_hip.lib().pfn_gpc_predict(theta.data_ptr(), train.data_ptr(), labels.data_ptr(), test.data_ptr(), fold.data_ptr(), P, n, T, F, NC, int(n_splits),
+                                          cv_f.data_ptr(), test_f.data_ptr(), test_var.data_ptr(), status.data_ptr(), _hip.stream_ptr(dev)), 'pfn_gpc_predict')
+    return cv_f, test_f, test_var, status

@@ -18,7 +18,11 @@ every CV fold and every test row of every window in one launch (pfn_knn_cv) and 
     logistic_metric (with its grid search over 108 parameter sets)   :325-346
 solves every candidate and fold of every window to its optimum in one launch (pfn_logistic_cv); the grid, the folds and the scores are host
 arithmetic in f64.
-The other baselines of the reference (GP / BNN classifiers, XGBoost, CatBoost: :372-677) and the OpenML loaders
+    gp_metric (with its grid search over 24 kernels c * RBF(l))      :480-503
+restates scikit-learn's binary Laplace GaussianProcessClassifier: pfn_gpc_lml_grad gives the log marginal likelihood and its gradient of every candidate and fold
+of every window in one launch per L-BFGS pass (`priors.fast_gp_mix.batched_lbfgs` on the host drives it), pfn_gpc_predict the decision values and variances
+(DESIGN.md 21); folds, scores, selection and the erf-mixture probabilities are host arithmetic in f64.  It needs no library beyond this stack.
+The other baselines of the reference (the BNN classifier, whose grid cannot run in the reference either, XGBoost, CatBoost: :372-677) and the OpenML loaders
 stay out: they need libraries and network access this stack does not carry.  Any callable with the reference's metric-function
 signature still runs through `batch_pred`, one window at a time, as the reference loops.
 
@@ -504,3 +508,129 @@ def logistic_metric(x, y, test_x, test_y, cat_features):
 
 
 logistic_metric.batched = _logistic_batched
+
+
+## GP classifier (reference tabular.py:480-503)
+
+param_grid['gp'] = {'params_y_scale': [0.05, 0.1, 0.5, 1.0, 5.0, 10.0], 'params_length_scale': [0.1, 0.5, 1.0, 2.0]}      # the kernels are c * RBF(l) over their product
+GP_BOX = (float(np.log(1e-5)), float(np.log(1e5)))      # scikit-learn's default bounds of both hyper-parameters, in theta = log
+GP_LBFGS = dict(gtol=1e-3, ftol=1e-6, max_iter=100)     # sized to the f32 objective (INTEGRATION.md has scikit-learn's beside them)
+# Williams & Barber's five-term erf approximation of the logistic sigmoid, as scikit-learn's predict_proba uses it
+_GP_LAMBDAS = (0.41, 0.4, 0.37, 0.44, 0.39)
+_GP_COEFS = (-1854.8214151, 3516.89893646, 221.29346712, 128.12323805, -2010.49422654)
+
+
+def _gp_grid(grid=None):
+    """The reference's 24 candidate kernels c * RBF(l) as (c, l) pairs in its order, `itertools.product` over (c values, l values)."""
+    import itertools
+    grid = param_grid['gp'] if grid is None else grid
+    return [(float(c), float(l)) for c, l in itertools.product(grid['params_y_scale'], grid['params_length_scale'])]
+
+
+def _gp_proba(f_star, var):
+    """scikit-learn's predict_proba[:, 1] from the latent mean and variance, in f64: sum_k coef_k 1/2 erf(lambda_k f* / sqrt(1 + 2 var lambda_k^2)) + 1/2 sum_k
+    coef_k -- its expression with alpha = 1 / (2 var) multiplied out, so that the var = 0 the kernel clamps to is an ordinary argument."""
+    f_star, var = torch.as_tensor(f_star, dtype=torch.float64), torch.as_tensor(var, dtype=torch.float64).clamp_min(0)
+    lam, coef = torch.tensor(_GP_LAMBDAS, dtype=torch.float64)[:, None], torch.tensor(_GP_COEFS, dtype=torch.float64)[:, None]
+    integrals = 0.5 * torch.erf(lam * f_star / torch.sqrt(1 + 2 * var * lam ** 2))
+    return ((coef * integrals).sum(0) + 0.5 * coef.sum()).numpy()
+
+
+def _gp_f_star(pairs):
+    """The decision values of the kernel's (m, e) pairs [..., 2], formed in f64: f* = m exp(-e)."""
+    pairs = np.asarray(pairs, dtype=np.float64)
+    return pairs[..., 0] * np.exp(-pairs[..., 1])
+
+
+def _gp_select(cv_f, status, folds, y, n_splits, test_f, test_var):
+    """The host half of one problem's grid search, in f64, from the kernel's results: cv_f [NC, n, 2] the (m, e) pair of every row from the fit that held it
+    out, status [NC, 6, 2], folds [n] the rows' test folds, y [n] the labels, test_f [NC, T, 2] and test_var [NC, T] of the refits.  As GridSearchCV scores it:
+    a fold's score is the accuracy of (f* > 0) on its rows -- NaN where the fit did not run or failed (a one-class training part: the fit raises, error_score =
+    nan) --, a candidate's score the mean over folds, the best candidate the FIRST maximum (NaN ranks last), predict_proba[:, 1] the erf mixture of its refit.
+    Returns (mean_test_score [NC] f64, best index, proba [T] f64); raises ValueError when every fit of every candidate failed."""
+    folds, cls = np.asarray(folds), np.asarray(y) > 0.5
+    reasons = np.asarray(status)[:, :n_splits, 0]
+    ran = (reasons == hipops.GPC_CONVERGED) | (reasons == hipops.GPC_CAPPED)
+    if not ran.any():
+        raise ValueError('gp_metric: every fit of every candidate failed (each fold\'s training part holds one class)')
+    right = (_gp_f_star(cv_f) > 0) == cls[None, :]      # [NC, n]
+    scores = np.full(ran.shape, np.nan)
+    for s in range(n_splits):
+        held = folds == s
+        scores[:, s] = np.where(ran[:, s], right[:, held].sum(1) / float(held.sum()), np.nan)
+    mean = scores.mean(axis=1)
+    best = int(np.argmax(np.where(np.isnan(mean), -np.inf, mean)))
+    return mean, best, _gp_proba(_gp_f_star(np.asarray(test_f)[best]), np.asarray(test_var)[best])
+
+
+def _gp_objective(x, y, folds, n_splits, shape, counters=None):
+    """-Z and its gradient for batched_lbfgs, all fits of the call in one pfn_gpc_lml_grad launch.  The box is applied here: the kernel sees the clipped theta,
+    and a gradient component that points out of the box at a bound is zero."""
+    lo, hi = GP_BOX
+
+    def fun(theta):
+        inside = theta.clamp(lo, hi)
+        value, grad, _ = hipops.gpc_lml_grad(inside.reshape(shape).contiguous(), x, y, folds, n_splits)
+        grad = grad.reshape(-1, 2)
+        out = ((theta <= lo) & (grad > 0)) | ((theta >= hi) & (grad < 0))
+        if counters is not None:
+            counters['passes'] = counters.get('passes', 0) + 1
+        return value.reshape(-1), torch.where(out, torch.zeros_like(grad), grad)
+    return fun
+
+
+def _gp_batched(x, y, test_x, test_y, optimize=True, return_params=False, counters=None):
+    """The GP classifier with the reference's grid search for W problems at once: x [n, W, F] normalised train rows, y [n, W], test_x [T, W, F], test_y [T, W] on
+    the GPU.  Every one of the W x 24 x (folds + 1) fits starts at its candidate's theta = (log c, log l) and maximises its own Laplace log marginal likelihood
+    by `batched_lbfgs` inside the box GP_BOX, every pass ONE pfn_gpc_lml_grad launch; one pfn_gpc_predict launch at the final thetas gives the decision values;
+    the folds (before) and the scores, the selection and the probabilities (after) are host arithmetic in f64.  `optimize=False` skips the optimiser: every
+    candidate is fitted at its own theta (scikit-learn's optimizer=None).  Returns (ROC-AUC [W], proba [T, W]) numpy, and with return_params a third entry: per
+    problem dict(kernel=(c, l) of the chosen refit after optimisation, start=(c, l) of its candidate, index).  `counters`, a dict, receives the L-BFGS pass
+    count and the fits' exit reasons.  Raises ValueError, as scikit-learn's fit does, for a window whose train rows hold one class."""
+    n, W, F = x.shape
+    T = test_x.shape[0]
+    cands = _gp_grid()
+    NC = len(cands)
+    hipops.gpc_check(n, T, F, NC)
+    n_splits = min(CV, n // 2)
+    y_host = y.detach().cpu().numpy() > 0.5
+    for w in range(W):
+        if y_host[:, w].all() or not y_host[:, w].any():
+            raise ValueError(f'gp_metric: the train rows of window {w} hold one class only')
+    folds = np.stack([_stratified_folds(y_host[:, w], n_splits) for w in range(W)])      # [W, n]
+    xs, ys, ts = x.float().transpose(0, 1).contiguous(), y.float().t().contiguous(), test_x.float().transpose(0, 1).contiguous()
+    folds_dev = torch.from_numpy(folds).to(x.device)
+    shape = (W, NC, hipops.GPC_SLOTS, 2)
+    theta = torch.tensor(cands, dtype=torch.float64).log().float().to(x.device)[None, :, None, :].expand(shape).contiguous()
+    if optimize:
+        res = priors.fast_gp_mix.batched_lbfgs(_gp_objective(xs, ys, folds_dev, n_splits, shape, counters), theta.reshape(-1, 2), **GP_LBFGS)
+        theta = res['theta'].clamp(*GP_BOX).reshape(shape).contiguous()
+        if counters is not None:
+            counters['converged'] = res['converged'].reshape(shape[:3])[:, :, :n_splits + 1].cpu().numpy()
+            counters['objective'] = res['objective'].reshape(shape[:3])[:, :, :n_splits + 1].double().cpu().numpy()
+            counters['evaluations'] = res['evaluations']
+    cv_f, test_f, test_var, status = hipops.gpc_predict(theta, xs, ys, ts, folds_dev, n_splits)
+    cv_f, test_f, test_var, status, theta_host = cv_f.cpu().numpy(), test_f.cpu().numpy(), test_var.cpu().numpy(), status.cpu().numpy(), theta.double().cpu().numpy()
+    if counters is not None:
+        counters['status'] = status
+        counters['theta'] = theta_host
+    y01 = y_host.astype(np.float64)
+    chosen = [_gp_select(cv_f[w], status[w], folds[w], y01[:, w], n_splits, test_f[w], test_var[w]) for w in range(W)]
+    proba = np.stack([c[2] for c in chosen], 1)      # [T, W]
+    metric, undefined = roc_auc_columns(torch.from_numpy(proba).float().to(x.device), test_y)
+    _report_undefined(undefined, f'of {W} windows')
+    if not return_params:
+        return metric, proba
+    params = [dict(kernel=tuple(float(v) for v in np.exp(theta_host[w, c[1], n_splits])), start=cands[c[1]], index=c[1]) for w, c in enumerate(chosen)]
+    return metric, proba, params
+
+
+def gp_metric(x, y, test_x, test_y, cat_features):
+    """Reference tabular.py:480-503 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (ROC-AUC, proba [T]) of
+    the GaussianProcessClassifier that GridSearchCV picks from the 24 kernels c * RBF(l) of param_grid['gp'] by min(5, n // 2)-fold stratified cross-validation
+    (INTEGRATION.md).  `gp_metric.batched` is the same for many problems at once; `batch_pred` uses it."""
+    metric, proba = _gp_batched(x[:, None], y[:, None], test_x[:, None], test_y[:, None])
+    return metric[0], proba[:, 0]
+
+
+gp_metric.batched = _gp_batched

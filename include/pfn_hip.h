@@ -682,6 +682,45 @@ int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32
                           int B, int T, int HP, int Lmax, int activation, int gen_causes,
                           uint64_t seed, uint64_t offset, void* stream);
 
+/* ---- Stroke prior of the few-shot study (ABI 10, additive): replaces the Pillow drawing loop of priors.stroke.get_batch (priors/stroke.py:9-63, :95-110).
+ * An image is up to PFN_STROKE_MAX_STROKES straight strokes of one width on a size x size 8-bit canvas, exactly the pixels Pillow's ImageDraw.line lights
+ * (csrc/stroke_prior.hip states the rule), each lit pixel holding a noise byte in 200 .. 254, blurred as Pillow's GaussianBlur(0.2) blurs it; the output is
+ * byte / 255 in f32, correctly rounded, and with normalize != 0 (x - mean) / (std + 1e-6) per image, std the unbiased one.  A stroke with a coordinate beyond
+ * +-PFN_STROKE_COORD_LIMIT is not drawn.  Stream-ordered, no allocation, no host synchronisation, no atomics.
+ * pfn_stroke_render: N images from explicit parameters.  segs [N,8,4] int32 = (x0, y0, x1, y1), 16-byte aligned; n_strokes [N], width [N] int32 -- DEVICE
+ *   arrays, so the call cannot refuse their values: the kernel clamps them to 0 .. 8 and 0 .. PFN_STROKE_MAX_WIDTH (hipops.stroke_render checks them first).
+ *   noise [N,size^2] uint8 or NULL: then pixel x of row y of image n takes word x % 4 of the Philox4x32-10 block at counter (n * 64 + y) * 16 + x / 4,
+ *   stream word offset * 8 + 4, key seed, as 200 + mulhi(u32, 55).  x: image n at x + n * image_stride floats (image_stride >= size^2, so a caller can write
+ *   into a larger layout); raw / img [N,size^2] uint8 or NULL: the image before / after the blur.
+ *   8 <= size <= 64 else PFN_ERR_UNSUPPORTED; N >= 0, image_stride >= size^2, non-NULL segs, n_strokes, width, x, segs 16-byte and the others 4-byte aligned else
+ *   PFN_ERR_ARGUMENT; all of it before any launch.  N == 0: PFN_OK, nothing launched.
+ * pfn_stroke_prior_sample: the prior.  Dataset b (global index d = first_dataset + b, so dataset b of a batch equals a call with B = 1, first_dataset = b) has
+ *   num_classes classes; image (b, t) is one of class labels[b,t] and lands in x [T,B,size^2].  Counter-based randomness: Philox4x32-10, counter = a global
+ *   index, stream word = offset * 8 + purpose, key = seed; an integer in [lo, hi] is lo + mulhi(u32, hi - lo + 1), whose bias is below (hi - lo + 1) 2^-32.
+ *   Class (d, c): stroke count in [strokes_lo, strokes_hi] from counter d * num_classes + c (purpose 0).  Stroke s of it, pass p < PFN_STROKE_MAX_PASSES = 256:
+ *   the block at counter ((d * 16 + c) * 8 + s) * 256 + p (purpose 1) gives (length, start x, start y, angle); length in [len_lo, len_hi] and the start in
+ *   [start_lo, start_hi]^2 are taken anew when p % 3 == 0, the angle theta = u32 * 2 pi / 2^32 on every pass; the pass is accepted iff both coordinates of
+ *   start + length (cos theta, sin theta) lie in [0, size - 1] (f64).  On the cap the last draw stays and status[b] counts it.
+ *   Image g = d * T + t: the block at counter g (purpose 2) gives (width in [width_lo, width_hi], offset x, offset y in [-max_offset, max_offset]); word pair
+ *   s % 2 of the block at counter g * 4 + s / 2 (purpose 3) the jitter of stroke s in [-max_target_offset, max_target_offset]^2; p0 = start + offset,
+ *   p1 = rint(p0 + (length (cos theta, sin theta) + jitter)) in f64, every step rounded; the noise as pfn_stroke_render with n = g.
+ *   Returned beside x: cls_n [B,C], cls_len [B,C,8], cls_start [B,C,8,2] int32, cls_dir [B,C,8] f64 (theta), segs [B,T,8,4], width [B,T] int32 (all required),
+ *   raw / img [B,T,size^2] uint8 or NULL, status [B] int32.
+ *   8 <= size <= 64, 1 <= num_classes <= PFN_STROKE_MAX_CLASSES, strokes_hi <= 8, width_hi <= PFN_STROKE_MAX_WIDTH, len_hi, start_hi, max_offset,
+ *   max_target_offset <= 1024 else PFN_ERR_UNSUPPORTED; B, T >= 1, B * T < 2^31, 0 <= lo <= hi for every range, max_offset, max_target_offset >= 0, non-NULL
+ *   and aligned buffers (segs 16 bytes, cls_dir 8, the others 4) else PFN_ERR_ARGUMENT; all of it before any launch. */
+#define PFN_STROKE_MAX_STROKES 8
+#define PFN_STROKE_MAX_CLASSES 16
+#define PFN_STROKE_MAX_WIDTH 64
+#define PFN_STROKE_MAX_PASSES 256
+#define PFN_STROKE_COORD_LIMIT 4096
+int pfn_stroke_render(const int32_t* segs, const int32_t* n_strokes, const int32_t* width, const uint8_t* noise, int64_t N, int size, int normalize,
+                      int64_t image_stride, uint64_t seed, uint64_t offset, float* x, uint8_t* raw, uint8_t* img, void* stream);
+int pfn_stroke_prior_sample(const int32_t* labels, int B, int T, int num_classes, int size, int normalize, int strokes_lo, int strokes_hi, int len_lo, int len_hi,
+                            int start_lo, int start_hi, int width_lo, int width_hi, int max_offset, int max_target_offset, uint64_t seed, uint64_t offset,
+                            uint64_t first_dataset, float* x, int32_t* cls_n, int32_t* cls_len, int32_t* cls_start, double* cls_dir, int32_t* segs, int32_t* width,
+                            uint8_t* raw, uint8_t* img, int32_t* status, void* stream);
+
 /* ---- single-op entry points (unit tests / profiling of individual kernels) --------------------
  * prec selects operand element type T: PFN_PREC_BF16 / PFN_PREC_FP16 (2 bytes) or PFN_PREC_F32; the LDS-DMA kernels (grouped weight gradients,
  * LayerNorm-fused GEMMs) take the two 16-bit formats only. */

@@ -142,6 +142,11 @@ SIGNATURES = {
     'pfn_gpc_lml_grad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     # (theta, train, labels, test, fold, P, n, T, F, NC, n_splits, cv_f, test_f, test_var, status, stream)
     'pfn_gpc_predict': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    # stroke prior of the few-shot study (ABI 10, additive).  (segs, n_strokes, width, noise, N, size, normalize, image_stride, seed, offset, x, raw, img, stream)
+    'pfn_stroke_render': (_I, [_P, _P, _P, _P, _L, _I, _I, _L, _U64, _U64, _P, _P, _P, _P]),
+    # (labels, B, T, num_classes, size, normalize, strokes_lo, strokes_hi, len_lo, len_hi, start_lo, start_hi, width_lo, width_hi, max_offset, max_target_offset, seed, offset,
+    #  first_dataset, x, cls_n, cls_len, cls_start, cls_dir, segs, width, raw, img, status, stream)
+    'pfn_stroke_prior_sample': (_I, [_P] + [_I] * 15 + [_U64] * 3 + [_P] * 11),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

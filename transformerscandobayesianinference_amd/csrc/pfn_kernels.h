@@ -655,4 +655,37 @@ struct MlpPriorArgs {
 };
 int launch_mlp_prior(const MlpPriorArgs& a, hipStream_t s);
 
+// ---- Stroke prior (stroke_prior.hip): glyphs of the few-shot study, one wave per image ------------------------------------------------------
+struct StrokeRenderArgs {
+  const int32_t* segs;       // [N,8,4] = (x0, y0, x1, y1)
+  const int32_t* n_strokes;  // [N]
+  const int32_t* width;      // [N]
+  const uint8_t* noise;      // [N,size^2] or null (Philox)
+  long N;
+  int size, normalize, vec16;      // vec16: size % 4 == 0 and every image of x 16-byte aligned
+  long image_stride;         // floats between two images of x
+  unsigned long long seed, offset;
+  float* x;
+  uint8_t* raw;              // [N,size^2] or null: before the blur
+  uint8_t* img;              // [N,size^2] or null: after the blur
+};
+struct StrokePriorArgs {
+  const int32_t* labels;     // [B,T]
+  int B, T, C, size, normalize, vec16;
+  int strokes_lo, strokes_hi, len_lo, len_hi, start_lo, start_hi, width_lo, width_hi, max_off, max_toff;
+  unsigned long long seed, offset, first_dataset;
+  float* x;                  // [T,B,size^2]
+  int32_t* cls_n;            // [B,C]
+  int32_t* cls_len;          // [B,C,8]
+  int32_t* cls_start;        // [B,C,8,2]
+  double* cls_dir;           // [B,C,8]
+  int32_t* segs;             // [B,T,8,4]
+  int32_t* width;            // [B,T]
+  uint8_t* raw;              // [B,T,size^2] or null
+  uint8_t* img;              // [B,T,size^2] or null
+  int32_t* status;           // [B]
+};
+int launch_stroke_render(const StrokeRenderArgs& a, hipStream_t s);
+int launch_stroke_prior(const StrokePriorArgs& a, hipStream_t s);
+
 }  // namespace pfn

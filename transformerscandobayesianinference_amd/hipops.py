@@ -652,3 +652,82 @@ def gpc_predict(theta, train, labels, test, fold, n_splits):
     _hip.check(_hip.lib().pfn_gpc_predict(theta.data_ptr(), train.data_ptr(), labels.data_ptr(), test.data_ptr(), fold.data_ptr(), P, n, T, F, NC, int(n_splits),
                                           cv_f.data_ptr(), test_f.data_ptr(), test_var.data_ptr(), status.data_ptr(), _hip.stream_ptr(dev)), 'pfn_gpc_predict')
     return cv_f, test_f, test_var, status
+
+
+# ---- stroke prior of the few-shot study (csrc/stroke_prior.hip; include/pfn_hip.h PFN_STROKE_*) ----
+STROKE_MAX_STROKES, STROKE_MAX_CLASSES, STROKE_MAX_WIDTH, STROKE_MAX_PASSES, STROKE_COORD_LIMIT = 8, 16, 64, 256, 4096
+STROKE_MIN_SIZE, STROKE_MAX_SIZE = 8, 64
+
+
+def stroke_check(size, n_strokes_hi=0, width_hi=0, num_classes=1):
+    """The limits of the stroke kernels, raised as ValueError before the device is asked for anything."""
+    if not STROKE_MIN_SIZE <= size <= STROKE_MAX_SIZE:
+        raise ValueError(f'stroke: size = {size} outside {STROKE_MIN_SIZE} .. {STROKE_MAX_SIZE} (one lane per row, a row\'s mask in 64 bits)')
+    if not 0 <= n_strokes_hi <= STROKE_MAX_STROKES:
+        raise ValueError(f'stroke: strokes = {n_strokes_hi} outside 0 .. {STROKE_MAX_STROKES}')
+    if not 0 <= width_hi <= STROKE_MAX_WIDTH:
+        raise ValueError(f'stroke: width = {width_hi} outside 0 .. {STROKE_MAX_WIDTH}')
+    if not 1 <= num_classes <= STROKE_MAX_CLASSES:
+        raise ValueError(f'stroke: num_classes = {num_classes} outside 1 .. {STROKE_MAX_CLASSES}')
+
+
+def stroke_render(segs, n_strokes, width, size, noise=None, normalize=False, out=None, seed=0, offset=0, want_bytes=False, check=True):
+    """N glyphs from explicit parameters (pfn_stroke_render): segs [N,8,4] int32 = (x0, y0, x1, y1), n_strokes [N], width [N] int32, noise [N,size^2] uint8 or
+    None (drawn on the device) on the GPU.  Returns x [N,size^2] f32 -- or writes image n to out[n] when `out` ([N, >= size^2] f32, rows contiguous) is given --
+    and with `want_bytes` (x, raw, img): the uint8 image before and after the blur.  `check` reads back the largest stroke count and width first (one
+    synchronisation) and raises ValueError beyond 8 / 64; without it the kernel clamps them."""
+    stroke_check(size)
+    if segs.dim() != 3 or tuple(segs.shape[1:]) != (STROKE_MAX_STROKES, 4) or n_strokes.shape != segs.shape[:1] or width.shape != segs.shape[:1]:
+        raise ValueError('segs [N, 8, 4], n_strokes [N], width [N]')
+    N, px = segs.shape[0], size * size
+    if noise is not None and (tuple(noise.shape) != (N, px) or noise.dtype != torch.uint8):
+        raise ValueError('noise [N, size^2] uint8')
+    _hip.require_gpu_tensor(segs, 'segs')
+    dev = segs.device
+    for t, name in ((segs, 'segs'), (n_strokes, 'n_strokes'), (width, 'width')):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == dev, f'{name}: contiguous int32 on {dev}'
+    assert noise is None or (noise.is_contiguous() and noise.device == dev), 'noise: contiguous on the same device'
+    if check and N:
+        n_lo, n_hi, w_lo, w_hi = (int(v) for v in torch.stack([n_strokes.min(), n_strokes.max(), width.min(), width.max()]).tolist())
+        stroke_check(size, n_hi if n_lo >= 0 else n_lo, w_hi if w_lo >= 0 else w_lo)
+    if out is None:
+        out = torch.empty(N, px, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.device == dev and out.dim() == 2 and out.shape[0] == N and out.shape[1] >= px and (N == 0 or out.stride(1) == 1), \
+        'out: [N, >= size^2] f32 with contiguous rows'
+    raw = torch.empty(N, px, dtype=torch.uint8, device=dev) if want_bytes else None
+    img = torch.empty(N, px, dtype=torch.uint8, device=dev) if want_bytes else None
+    _hip.check(_hip.lib().pfn_stroke_render(segs.data_ptr(), n_strokes.data_ptr(), width.data_ptr(), _hip.ptr(noise), N, size, int(bool(normalize)),
+                                            out.stride(0) if N > 1 else out.shape[1], int(seed) & (2 ** 64 - 1), int(offset), out.data_ptr(), _hip.ptr(raw),
+                                            _hip.ptr(img), _hip.stream_ptr(dev)), 'pfn_stroke_render')
+    return (out, raw, img) if want_bytes else out
+
+
+def stroke_prior_sample(labels, size, bounds, num_classes, seed, offset=0, first_dataset=0, normalize=False, want_bytes=False):
+    """One batch of the stroke prior (pfn_stroke_prior_sample): labels [B,T] int32 on the GPU; bounds: a dict of inclusive integer ranges strokes, len, start,
+    width = (lo, hi) and offset, jitter = (-m, m), as priors.stroke.integer_bounds gives.  Returns a dict: x [T,B,size^2] f32, cls_n [B,C], cls_len [B,C,8],
+    cls_start [B,C,8,2] int32, cls_dir [B,C,8] f64, segs [B,T,8,4], width [B,T] int32, status [B] int32 (class strokes that hit the retry cap) and, with
+    `want_bytes`, raw / img [B,T,size^2] uint8."""
+    if labels.dim() != 2:
+        raise ValueError('labels [B, T]')
+    B, T = labels.shape
+    C, px = int(num_classes), size * size
+    (s_lo, s_hi), (l_lo, l_hi), (p_lo, p_hi), (w_lo, w_hi) = bounds['strokes'], bounds['len'], bounds['start'], bounds['width']
+    stroke_check(size, s_hi, w_hi, C)
+    if bounds['offset'][0] != -bounds['offset'][1] or bounds['jitter'][0] != -bounds['jitter'][1]:
+        raise ValueError('offset and jitter ranges are symmetric: (-m, m)')
+    _hip.require_gpu_tensor(labels, 'labels')
+    dev = labels.device
+    assert labels.dtype == torch.int32 and labels.is_contiguous(), 'labels [B, T]: contiguous int32'
+    i32 = dict(dtype=torch.int32, device=dev)
+    r = dict(x=torch.empty(T, B, px, dtype=torch.float32, device=dev), cls_n=torch.empty(B, C, **i32), cls_len=torch.empty(B, C, STROKE_MAX_STROKES, **i32),
+             cls_start=torch.empty(B, C, STROKE_MAX_STROKES, 2, **i32), cls_dir=torch.empty(B, C, STROKE_MAX_STROKES, dtype=torch.float64, device=dev),
+             segs=torch.empty(B, T, STROKE_MAX_STROKES, 4, **i32), width=torch.empty(B, T, **i32), status=torch.empty(B, **i32))
+    if want_bytes:
+        r['raw'] = torch.empty(B, T, px, dtype=torch.uint8, device=dev)
+        r['img'] = torch.empty(B, T, px, dtype=torch.uint8, device=dev)
+    _hip.check(_hip.lib().pfn_stroke_prior_sample(labels.data_ptr(), B, T, C, size, int(bool(normalize)), s_lo, s_hi, l_lo, l_hi, p_lo, p_hi, w_lo, w_hi,
+                                                  bounds['offset'][1], bounds['jitter'][1], int(seed) & (2 ** 64 - 1), int(offset), int(first_dataset),
+                                                  r['x'].data_ptr(), r['cls_n'].data_ptr(), r['cls_len'].data_ptr(), r['cls_start'].data_ptr(), r['cls_dir'].data_ptr(),
+                                                  r['segs'].data_ptr(), r['width'].data_ptr(), _hip.ptr(r.get('raw')), _hip.ptr(r.get('img')), r['status'].data_ptr(),
+                                                  _hip.stream_ptr(dev)), 'pfn_stroke_prior_sample')
+    return r

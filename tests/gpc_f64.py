@@ -11,6 +11,8 @@ import math
 
 import numpy as np
 
+from tabular_cases import problem  # noqa: F401  (the seeded problems of the fixtures, shared with the other arm)
+
 UNUSED, CONVERGED, CAPPED, ONE_CLASS, NONPOSITIVE, NONFINITE = 0, 1, 2, 3, 4, 5      # hipops.GPC_*
 MAX_NEWTON = 100
 STOP32, EXTRA32 = 2.0 ** -20, 2      # the kernel's stopping level (of max(1, |Z|)) and the iterations it runs beyond it
@@ -34,23 +36,6 @@ def grid():
 
 def grid_theta():
     return np.log(np.asarray(grid(), dtype=np.float64))
-
-
-def problem(n, F, T, seed):
-    """Rows as the study normalises them (zero mean, unit std per column over the train rows) with, from F = 3 on, column 1 all zero (the study's padding);
-    labels from a noisy linear rule, both classes at least twice in the train rows.  Returns float32 x [n,F], y [n], test_x [T,F], test_y [T] as numpy."""
-    rng = np.random.RandomState(seed)
-    while True:
-        raw = rng.randn(n + T, F) * (0.5 + rng.rand(F)) + rng.randn(F)
-        beta = rng.randn(F) * (rng.rand(F) < 0.6)
-        y = ((raw - raw.mean(0)) @ beta + 0.7 * rng.randn(n + T) * max(np.sqrt((beta ** 2).sum()), 0.5) > 0).astype(np.float32)
-        if min(y[:n].sum(), n - y[:n].sum()) >= 2:
-            break
-    x = (raw - raw[:n].mean(0)) / (raw[:n].std(0, ddof=1) + 1e-6)
-    if F >= 3:
-        x[:, 1] = 0
-    x = x.astype(np.float32)
-    return x[:n], y[:n], x[n:], y[n:]
 
 
 def attach_rows(rec, wrap):

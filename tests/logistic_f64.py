@@ -6,6 +6,8 @@ Objective (scikit-learn's):  C sum_i m_i softplus(-y_i z_i) + r(w),  z = x w + b
 the intercept is never penalised.  A coefficient vector has F + 1 entries: the weights, then the intercept (0 without one)."""
 import numpy as np
 
+from tabular_cases import problem  # noqa: F401  (the seeded problems of the fixtures, shared with the other arm)
+
 NONE, L1, L2, FIT_INTERCEPT = 0, 1, 2, 4      # hipops.LOGIT_*
 UNUSED, CONVERGED, STALLED, CAPPED, ONE_CLASS, NONFINITE = 0, 1, 2, 3, 4, 5
 PENALTIES = {'none': NONE, None: NONE, 'l1': L1, 'l2': L2}
@@ -231,21 +233,3 @@ def solve_problem(x, y, test_x, folds, n_splits, cands, dtype=np.float64):
                 cv_z[c, held] = z
                 cv_correct[c, s] = int(((z > 0) == cls[held]).sum())
     return coef, status, cv_z, cv_correct, test_z
-
-
-# ---- the seeded problems -------------------------------------------------------------------------------------------------------------------------------------
-def problem(n, F, T, seed):
-    """Rows as the study normalises them (zero mean, unit std per column over the train rows) with, from F = 3 on, column 1 all zero (the study's padding);
-    labels from a noisy linear rule, both classes at least twice in the train rows.  Returns float32 x [n,F], y [n], test_x [T,F], test_y [T] as numpy."""
-    rng = np.random.RandomState(seed)
-    while True:
-        raw = rng.randn(n + T, F) * (0.5 + rng.rand(F)) + rng.randn(F)
-        beta = rng.randn(F) * (rng.rand(F) < 0.6)
-        y = ((raw - raw.mean(0)) @ beta + 0.7 * rng.randn(n + T) * max(np.sqrt((beta ** 2).sum()), 0.5) > 0).astype(np.float32)
-        if min(y[:n].sum(), n - y[:n].sum()) >= 2:
-            break
-    x = (raw - raw[:n].mean(0)) / (raw[:n].std(0, ddof=1) + 1e-6)
-    if F >= 3:
-        x[:, 1] = 0
-    x = x.astype(np.float32)
-    return x[:n], y[:n], x[n:], y[n:]

@@ -30,6 +30,25 @@ def knn_problem(n, T, F, seed):
     return x, y, tx, ty
 
 
+def problem(n, F, T, seed):
+    """The seeded problems of the logistic and the GP-classifier fixtures (logistic_f64.problem and gpc_f64.problem are this function; the fixtures store seeds,
+    not rows, so it must keep drawing the same bits).  Rows as the study normalises them (zero mean, unit std per column over the train rows) with, from F = 3
+    on, column 1 all zero (the study's padding); labels from a noisy linear rule, both classes at least twice in the train rows.  Returns float32 x [n,F], y [n],
+    test_x [T,F], test_y [T] as numpy."""
+    rng = np.random.RandomState(seed)
+    while True:
+        raw = rng.randn(n + T, F) * (0.5 + rng.rand(F)) + rng.randn(F)
+        beta = rng.randn(F) * (rng.rand(F) < 0.6)
+        y = ((raw - raw.mean(0)) @ beta + 0.7 * rng.randn(n + T) * max(np.sqrt((beta ** 2).sum()), 0.5) > 0).astype(np.float32)
+        if min(y[:n].sum(), n - y[:n].sum()) >= 2:
+            break
+    x = (raw - raw[:n].mean(0)) / (raw[:n].std(0, ddof=1) + 1e-6)
+    if F >= 3:
+        x[:, 1] = 0
+    x = x.astype(np.float32)
+    return x[:n], y[:n], x[n:], y[n:]
+
+
 def auc_case(T, C, kind, seed=0):
     """scores [T, C], labels [T, C] f32; every column has both classes.  'ties': scores rounded to one decimal."""
     g = torch.Generator().manual_seed(77 + 131 * T + 7 * C + seed)

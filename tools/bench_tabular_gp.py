@@ -72,10 +72,9 @@ def main():
     for sep in POSITIONS:
         keep, counters = {}, {}
         x_w, y_w = hipops.tabular_windows(X, y, starts, BPTT, sep, mode=hipops.TAB_NORM_TRAIN_ONLY)
-        n_splits = min(tabular.CV, sep // 2)
-        folds = np.stack([tabular._stratified_folds(y_w[:sep, wi].cpu().numpy() > 0.5, n_splits) for wi in range(WINDOWS)])
+        n_splits, _, _, (train, labels, _, folds) = tabular._fold_problems(x_w[:sep], y_w[:sep], x_w[sep:])
         theta = torch.tensor(cands, dtype=torch.float64).log().float().to(dev)[None, :, None, :].expand(WINDOWS, len(cands), hipops.GPC_SLOTS, 2).contiguous()
-        k_args = (theta, x_w[:sep].transpose(0, 1).contiguous(), y_w[:sep].t().contiguous(), torch.from_numpy(folds).to(dev), n_splits)
+        k_args = (theta, train, labels, folds, n_splits)
 
         def gp_batched():
             keep['batched'] = tabular.evaluate_position(X, y, [], tabular.gp_metric, BPTT, sep, max_samples=WINDOWS)

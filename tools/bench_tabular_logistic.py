@@ -69,10 +69,8 @@ def main():
         T = BPTT - sep
         keep = {}
         x_w, y_w = hipops.tabular_windows(X, y, starts, BPTT, sep, mode=hipops.TAB_NORM_TRAIN_ONLY)
-        n_splits = min(tabular.CV, sep // 2)
-        folds = np.stack([tabular._stratified_folds(y_w[:sep, wi].cpu().numpy() > 0.5, n_splits) for wi in range(WINDOWS)])
-        k_args = (x_w[:sep].transpose(0, 1).contiguous(), y_w[:sep].t().contiguous(), x_w[sep:].transpose(0, 1).contiguous(), torch.from_numpy(folds).to(dev), n_splits,
-                  [c for c, _ in cands], [k for _, k in cands])
+        n_splits, _, _, operands = tabular._fold_problems(x_w[:sep], y_w[:sep], x_w[sep:])
+        k_args = (*operands, n_splits, [c for c, _ in cands], [k for _, k in cands])
 
         def logistic_batched():
             keep['batched'] = tabular.evaluate_position(X, y, [], tabular.logistic_metric, BPTT, sep, max_samples=WINDOWS)

@@ -152,9 +152,8 @@ def record(name, draw, first_seed, pool):
     for seed in range(first_seed, first_seed + 5000, 100):
         x, y, test_x, test_y = draw(seed)
         n, F, T = len(x), x.shape[1], len(test_x)
-        n_splits = min(tabular.CV, n // 2)
-        try:
-            folds = tabular._stratified_folds(y > 0.5, n_splits)
+        try:      # the folds as the product makes them: one problem through its preparation of many
+            n_splits, (folds,), _, _ = tabular._fold_problems(*(torch.from_numpy(v)[:, None] for v in (x, y, test_x)))
         except ValueError:
             continue
         thetas = np.concatenate([gf.grid_theta(), gf.extra_thetas(seed)])

@@ -118,9 +118,8 @@ cross_check.short = 0
 def record(n, F, T, first_seed, entries, cands, entry_fit):
     for seed in range(first_seed, first_seed + 5000, 100):
         x, y, test_x, test_y = lf.problem(n, F, T, seed)
-        n_splits = min(tabular.CV, n // 2)
-        try:
-            folds = tabular._stratified_folds(y > 0.5, n_splits)
+        try:      # the folds as the product makes them: one problem through its preparation of many
+            n_splits, (folds,), _, _ = tabular._fold_problems(*(torch.from_numpy(v)[:, None] for v in (x, y, test_x)))
         except ValueError:
             continue
         coef, status, cv_z, cv_correct, test_z = lf.solve_problem(x, y, test_x, folds, n_splits, cands)

@@ -8,8 +8,8 @@
 // SVI and SVGD, and the offsets of the NUTS and predict kernels), slots -> lane registers (bnn_lane: SVI, SVGD), the data-row loop over resident or chunked
 // rows (bnn_data_rows: all three gradient kernels, the NUTS kernel never resident) with its staging prologue (bnn_stage_all: SVI, SVGD) and the n_of clamp
 // (bnn_n_rows: all three), Adam's bias corrections and its update of one coordinate (bnn_ipow, bnn_adam_at, bnn_adam: SVI's loc and u, SVGD's particle
-// coordinate) and, on the host, bnn_dispatch (the H / F / activation dispatch of all three files) and bnn_launch_lds (the launch with more than 64 KB of LDS
-// of SVI and SVGD).
+// coordinate) and, on the host, bnn_dispatch (the H / F / activation dispatch of all three files).  SVI and SVGD launch through launch_lds
+// (pfn_kernels.h: the launch with more than 64 KB of LDS).
 #pragma once
 #include <type_traits>
 #include "pfn_device.h"
@@ -192,7 +192,7 @@ PFN_DEV BnnAdamOut bnn_adam(float p, float m, float v, float g, const BnnAdam h)
   return {p - h.lr * (m1 / h.bc1) / (sqrtf(v1 / h.bc2) + h.eps), m1, v1};
 }
 
-// ---- host: one dispatch and one large-LDS launch for the three files ----
+// ---- host: one dispatch for the three files ----
 
 template <int V> using BnnInt = std::integral_constant<int, V>;
 
@@ -201,13 +201,6 @@ template <class Fn> int bnn_dispatch(int H, int F, int activation, Fn&& fn) {
   auto act = [&](auto hp, auto fp) { return activation ? fn(hp, fp, BnnInt<1>{}) : fn(hp, fp, BnnInt<0>{}); };
   auto feat = [&](auto hp) { return F <= 4 ? act(hp, BnnInt<4>{}) : F <= 8 ? act(hp, BnnInt<8>{}) : act(hp, BnnInt<16>{}); };
   return H <= 8 ? feat(BnnInt<8>{}) : H <= 16 ? feat(BnnInt<16>{}) : H <= 32 ? feat(BnnInt<32>{}) : feat(BnnInt<64>{});
-}
-
-// a launch with `bytes` of dynamic LDS, raising the kernel's allowance first when it is more than the 64 KB a kernel has by default
-template <class A, class C> int bnn_launch_lds(void (*kernel)(A, C), LdsAllowance& allow, dim3 grid, dim3 block, size_t bytes, hipStream_t s, const A& a, const C& c) {
-  if (bytes > 64 * 1024) allow.ensure(kernel, bytes);
-  kernel<<<grid, block, bytes, s>>>(a, c);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 
 }  // namespace

@@ -274,7 +274,7 @@ int launch_bnn_svgd_steps(const BnnSvgdArgs& a, hipStream_t s) {
     const size_t bytes = ((size_t)c.cap * FP + ((c.cap + 3) & ~3) + (size_t)4 * a.N * c.LW + SVGD_WAVES * SVGD_CI * 64 + 64) * sizeof(float);
     static_assert(BNN_SVGD_STATE_BUDGET + SVGD_ROWS_BUDGET + 16 + BNN_CHUNK * (FP + 1) * 4 + (SVGD_WAVES * SVGD_CI * 64 + 64) * 4 <= 160 * 1024, "bnn_svgd: LDS");
     static LdsAllowance allow;      // one per instantiation
-    return bnn_launch_lds(bnn_svgd_kernel<HP, FP, ACT>, allow, dim3((unsigned)a.P), dim3(64 * SVGD_WAVES), bytes, s, a, c);
+    return launch_lds(bnn_svgd_kernel<HP, FP, ACT>, allow, dim3((unsigned)a.P), dim3(64 * SVGD_WAVES), bytes, s, a, c);
   });
 }
 

@@ -169,7 +169,7 @@ int launch_bnn_svi_steps(const BnnSviArgs& a, hipStream_t s) {
     const size_t bytes = ((size_t)(8 + c.waves * CPW + 2 * c.waves) * c.Dp + 4 + (size_t)c.cap * (FP + 1)) * sizeof(float);
     static_assert((size_t)(8 + BNN_MAX_WAVES * CPW + 2 * BNN_MAX_WAVES) * (HP * (FP + 3) + 4) * 4 + 16 + SVI_ROWS_BUDGET + BNN_CHUNK * (FP + 1) * 4 <= 160 * 1024, "bnn_svi: LDS");
     static LdsAllowance allow;      // one per instantiation
-    return bnn_launch_lds(bnn_svi_kernel<HP, FP, ACT>, allow, dim3((unsigned)a.P), dim3(64 * c.waves), bytes, s, a, c);
+    return launch_lds(bnn_svi_kernel<HP, FP, ACT>, allow, dim3((unsigned)a.P), dim3(64 * c.waves), bytes, s, a, c);
   });
 }
 

@@ -8,7 +8,7 @@ mkdir -p ../_build
 pids=()
 for f in $SRCS; do
   o=../_build/${f%.hip}.o
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ pfn_device.h -nt "$o" ] || [ pfn_kernels.h -nt "$o" ] || [ bnn_device.h -nt "$o" ] || [ ../../include/pfn_hip.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ pfn_device.h -nt "$o" ] || [ pfn_kernels.h -nt "$o" ] || [ bnn_device.h -nt "$o" ] || [ fold_device.h -nt "$o" ] || [ ../../include/pfn_hip.h -nt "$o" ]; then
     extra=""
     # attention.hip: no SLP packing -- v_pk_add/mul_f32 beside MFMAs issue slower than the scalar ops they replace
     [ "$f" = attention.hip ] && extra="-fno-slp-vectorize"

@@ -10,7 +10,7 @@
 //   prediction  decision values as pairs (m, e), f* = m exp(-e), so that the sign survives where exp underflows in f32; var = c - |L^-1 W^1/2 k*|^2
 // K, the factor (inverted in place for the gradient) and one more n x n matrix (the exponent arguments d^2 / 2 l^2) live in LDS at the odd stride n | 1.  No global
 // atomics, no workspace, no communication between blocks, no warm start: a result is a bitwise function of its own (problem, theta, slot).
-#include "pfn_kernels.h"
+#include "fold_device.h"
 
 namespace pfn {
 
@@ -39,15 +39,6 @@ GPC_DEV GpcLds gpc_carve(float* base, int n, int ns) {
   s.idx = reinterpret_cast<int*>(v + 14 * n); s.qidx = reinterpret_cast<int*>(v + 15 * n);
   s.red = v + 16 * n;
   return s;
-}
-
-// every thread calls; the result is the same bits in every thread
-GPC_DEV float gpc_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // the exponent argument d^2 / 2 l^2 of two rows
@@ -161,8 +152,8 @@ GPC_DEV int gpc_mode(const GpcLds& s, int m, int ns, float* Z_out, int* iters_ou
       const float z = s.y[tid] > 0.5f ? -acc : acc;      // -(2y - 1) f
       t = -0.5f * s.a[tid] * acc - (fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)))) - 0.5f * log1pf(s.px[tid]);      // log L_ii = 1/2 log(pivot)
     }
-    const float dZ = gpc_sum(t - tprev, s.red);      // the rows' differences, not the difference of two totals
-    Z = gpc_sum(t, s.red);
+    const float dZ = block_sum(t - tprev, s.red);      // the rows' differences, not the difference of two totals
+    Z = block_sum(t, s.red);
     tprev = t;
     if (left > 0) { if (--left == 0) { reason = PFN_GPC_CONVERGED; break; } }
     else if (it > 1 && !(dZ >= GPC_STOP * fmaxf(1.f, fabsf(Z)))) left = GPC_EXTRA;      // (a NaN counts as met: the fit ends, and is found non-finite below)
@@ -236,8 +227,8 @@ __global__ void __launch_bounds__(GPC_THREADS) gpc_lml_grad_kernel(GpcArgs a) {
       s.s2[tid] = -0.5f * omb * (1.f - 2.f * s.pi[tid]);
       p0 = 0.5f * (s.a[tid] * s.f[tid] - omb);
     }
-    g0 = gpc_sum(p0, s.red);
-    g1 = gpc_sum(p1, s.red);      // (the barriers publish u0, u1 and s2)
+    g0 = block_sum(p0, s.red);
+    g1 = block_sum(p1, s.red);      // (the barriers publish u0, u1 and s2)
     if (tid < m) {      // L^-1 W^1/2 b_j
       float t0 = 0.f, t1 = 0.f;
       for (int i = 0; i <= tid; ++i) {
@@ -269,8 +260,8 @@ __global__ void __launch_bounds__(GPC_THREADS) gpc_lml_grad_kernel(GpcArgs a) {
       q0 = s.s2[tid] * (s.u0[tid] - k0);
       q1 = s.s2[tid] * (s.u1[tid] - k1);
     }
-    g0 += gpc_sum(q0, s.red);
-    g1 += gpc_sum(q1, s.red);
+    g0 += block_sum(q0, s.red);
+    g1 += block_sum(q1, s.red);
     if (!(fabsf(g0) < __builtin_inff()) || !(fabsf(g1) < __builtin_inff())) reason = PFN_GPC_NONFINITE;
   }
   if (tid == 0) {
@@ -349,21 +340,14 @@ __global__ void __launch_bounds__(GPC_THREADS) gpc_predict_kernel(GpcArgs a) {
 
 }  // namespace
 
-static int gpc_launch(void (*kernel)(GpcArgs), LdsAllowance& allowance, const GpcArgs& a, hipStream_t s) {
-  const size_t lds = gpc_lds_bytes(a.n);
-  if (lds > 64 * 1024) allowance.ensure(kernel, lds);
-  kernel<<<dim3(PFN_GPC_SLOTS, (unsigned)a.NC, (unsigned)a.P), dim3(GPC_THREADS), lds, s>>>(a);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-}
-
 int launch_gpc_lml_grad(const GpcArgs& a, hipStream_t s) {
   static LdsAllowance allowance;
-  return gpc_launch(gpc_lml_grad_kernel, allowance, a, s);
+  return launch_lds(gpc_lml_grad_kernel, allowance, dim3(PFN_GPC_SLOTS, (unsigned)a.NC, (unsigned)a.P), dim3(GPC_THREADS), gpc_lds_bytes(a.n), s, a);
 }
 
 int launch_gpc_predict(const GpcArgs& a, hipStream_t s) {
   static LdsAllowance allowance;
-  return gpc_launch(gpc_predict_kernel, allowance, a, s);
+  return launch_lds(gpc_predict_kernel, allowance, dim3(PFN_GPC_SLOTS, (unsigned)a.NC, (unsigned)a.P), dim3(GPC_THREADS), gpc_lds_bytes(a.n), s, a);
 }
 
 }  // namespace pfn

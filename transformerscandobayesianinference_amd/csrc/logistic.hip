@@ -6,7 +6,7 @@
 //   stop        KKT_inf <= 64 2^-23 C max_j sum_i m_i |x_ij|, or no decrease, or the iteration cap; every loop has a constant cap and a NaN leaves every
 //               comparison towards "stop"
 // No global atomics, no workspace, no communication between blocks: a fit is a bitwise function of its own problem and candidate.
-#include "pfn_kernels.h"
+#include "fold_device.h"
 
 namespace pfn {
 
@@ -22,14 +22,7 @@ constexpr float LOGIT_EPS = 1.1920929e-07f;      // 2^-23
 constexpr float LOGIT_DAMP = 1.52587890625e-05f; // 2^-16 of the mean diagonal: changes steps, never the optimum
 constexpr float LOGIT_ARMIJO = 1e-4f;
 
-// ---- block reductions (every thread calls; the result is the same bits in every thread) ----
-LOGIT_DEV float block_sum(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();      // the previous use of red is over
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
+// the block maximum, a reduction like block_sum (fold_device.h): every thread calls; the result is the same bits in every thread
 LOGIT_DEV float block_max(float v, float* red) {      // a NaN in any lane comes out as NaN (so that the caller's comparison stops)
   bool bad = v != v;
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -342,10 +335,7 @@ __global__ void __launch_bounds__(LOGIT_THREADS) logit_cv_kernel(LogitCvArgs a) 
 
 int launch_logit_cv(const LogitCvArgs& a, hipStream_t s) {
   static LdsAllowance allowance;
-  const size_t lds = logit_cv_lds_bytes(a.n, a.F);
-  if (lds > 64 * 1024) allowance.ensure(logit_cv_kernel, lds);
-  logit_cv_kernel<<<dim3(PFN_LOGIT_SLOTS, (unsigned)a.NC, (unsigned)a.P), dim3(LOGIT_THREADS), lds, s>>>(a);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+  return launch_lds(logit_cv_kernel, allowance, dim3(PFN_LOGIT_SLOTS, (unsigned)a.NC, (unsigned)a.P), dim3(LOGIT_THREADS), logit_cv_lds_bytes(a.n, a.F), s, a);
 }
 
 }  // namespace pfn

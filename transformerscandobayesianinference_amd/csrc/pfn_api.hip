@@ -1691,12 +1691,24 @@ int pfn_auc_counts(const float* scores, const float* labels, int T, int C, int64
   PFN_TRY(launch_auc_counts(scores, labels, T, C, counts, (hipStream_t)stream));
   return PFN_OK;
 }
+// The shape check of the four fold-based entry points (pfn_knn_cv, pfn_logistic_cv, pfn_gpc_lml_grad, pfn_gpc_predict): the ranges (PFN_ERR_UNSUPPORTED; `why` says
+// what sets them) before P, n_splits and the pointers (PFN_ERR_ARGUMENT).  max_nc = 0: a call without candidates, max_splits = 0: one without n_splits (kNN).
+static int fold_shapes(const char* what, const char* why, int P, int n, int max_n, int T, int F, int NC, int max_nc, int n_splits, int max_splits, bool pointers) {
+  char own[48] = "";      // the clause of what only some of the calls have
+  if (n < 4 || n > max_n || T < 1 || T > 128 || F < 1 || F > 128 || (max_nc && (NC < 1 || NC > max_nc))) {
+    if (max_nc) snprintf(own, sizeof own, ", NC %d outside 1 .. %d", NC, max_nc);
+    return fail(PFN_ERR_UNSUPPORTED, "%s: n %d outside 4 .. %d, T %d outside 1 .. 128, F %d outside 1 .. 128%s (%s)", what, n, max_n, T, F, own, why);
+  }
+  if (P < 1 || (max_splits && (n_splits < 2 || n_splits > max_splits)) || !pointers) {
+    if (max_splits) snprintf(own, sizeof own, ", 2 <= n_splits %d <= %d", n_splits, max_splits);
+    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (P %d >= 1%s, no NULL buffer)", what, P, own);
+  }
+  return PFN_OK;
+}
 int pfn_knn_cv(const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F, int32_t* cv_correct, int32_t* test_pos,
                int32_t* test_nbr, void* stream) {
-  if (n < 4 || n > 128 || T < 1 || T > 128 || F < 1 || F > 128)
-    return fail(PFN_ERR_UNSUPPORTED, "knn_cv: n %d outside 4 .. 128, T %d outside 1 .. 128 or F %d outside 1 .. 128 (one thread per query, every row in LDS)", n, T, F);
-  if (P < 1 || !train || !labels || !test || !fold || !cv_correct || !test_pos || !test_nbr)
-    return fail(PFN_ERR_ARGUMENT, "bad knn_cv arguments (P %d >= 1, train, labels, test, fold, cv_correct, test_pos, test_nbr not NULL)", P);
+  if (const int rc = fold_shapes("knn_cv", "one thread per query, every row in LDS", P, n, 128, T, F, 0, 0, 0, 0,
+                                 train && labels && test && fold && cv_correct && test_pos && test_nbr)) return rc;
   KnnCvArgs a{};
   a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.P = P; a.n = n; a.T = T; a.F = F; a.cv_correct = cv_correct; a.test_pos = test_pos; a.test_nbr = test_nbr;
   PFN_TRY(launch_knn_cv(a, (hipStream_t)stream));
@@ -1706,12 +1718,8 @@ int pfn_knn_cv(const float* train, const float* labels, const float* test, const
 // ---- Logistic regression with its grid search (logistic.hip; ABI 10, additive) ----
 int pfn_logistic_cv(const float* train, const float* labels, const float* test, const int32_t* fold, const float* cand_C, const int32_t* cand_kind, int P, int n, int T,
                     int F, int NC, int n_splits, int32_t* cv_correct, float* test_z, int32_t* status, float* coef, void* stream) {
-  if (n < 4 || n > 128 || T < 1 || T > 128 || F < 1 || F > 128 || NC < 1 || NC > PFN_LOGIT_MAX_CANDIDATES)
-    return fail(PFN_ERR_UNSUPPORTED, "logistic_cv: n %d outside 4 .. 128, T %d outside 1 .. 128, F %d outside 1 .. 128 or NC %d outside 1 .. %d (one block per fit, its rows "
-                "and its Hessian in LDS)", n, T, F, NC, PFN_LOGIT_MAX_CANDIDATES);
-  if (P < 1 || n_splits < 2 || n_splits > PFN_LOGIT_FOLDS || !train || !labels || !test || !fold || !cand_C || !cand_kind || !cv_correct || !test_z || !status)
-    return fail(PFN_ERR_ARGUMENT, "bad logistic_cv arguments (P %d >= 1, 2 <= n_splits %d <= %d, train, labels, test, fold, cand_C, cand_kind, cv_correct, test_z, status "
-                "not NULL)", P, n_splits, PFN_LOGIT_FOLDS);
+  if (const int rc = fold_shapes("logistic_cv", "one block per fit, its rows and its Hessian in LDS", P, n, 128, T, F, NC, PFN_LOGIT_MAX_CANDIDATES, n_splits, PFN_LOGIT_FOLDS,
+                                 train && labels && test && fold && cand_C && cand_kind && cv_correct && test_z && status)) return rc;      // (coef may be NULL)
   LogitCvArgs a{};
   a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.cand_C = cand_C; a.cand_kind = cand_kind; a.P = P; a.n = n; a.T = T; a.F = F; a.NC = NC;
   a.n_splits = n_splits; a.cv_correct = cv_correct; a.test_z = test_z; a.status = status; a.coef = coef;
@@ -1721,12 +1729,7 @@ int pfn_logistic_cv(const float* train, const float* labels, const float* test, 
 
 // ---- GP classifier with its grid search (gpc.hip; ABI 10, additive) ----
 static int gpc_shapes(const char* what, int P, int n, int T, int F, int NC, int n_splits, bool pointers) {
-  if (n < 4 || n > PFN_GPC_MAX_N || T < 1 || T > 128 || F < 1 || F > 128 || NC < 1 || NC > PFN_GPC_MAX_CANDIDATES)
-    return fail(PFN_ERR_UNSUPPORTED, "%s: n %d outside 4 .. %d, T %d outside 1 .. 128, F %d outside 1 .. 128 or NC %d outside 1 .. %d (one block per fit, three n x n "
-                "matrices in LDS)", what, n, PFN_GPC_MAX_N, T, F, NC, PFN_GPC_MAX_CANDIDATES);
-  if (P < 1 || n_splits < 2 || n_splits > PFN_GPC_FOLDS || !pointers)
-    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (P %d >= 1, 2 <= n_splits %d <= %d, no NULL buffer)", what, P, n_splits, PFN_GPC_FOLDS);
-  return PFN_OK;
+  return fold_shapes(what, "one block per fit, three n x n matrices in LDS", P, n, PFN_GPC_MAX_N, T, F, NC, PFN_GPC_MAX_CANDIDATES, n_splits, PFN_GPC_FOLDS, pointers);
 }
 int pfn_gpc_lml_grad(const float* theta, const float* train, const float* labels, const int32_t* fold, int P, int n, int F, int NC, int n_splits, float* value,
                      float* grad, int32_t* status, void* stream) {

@@ -24,6 +24,15 @@ struct LdsAllowance {
   }
 };
 
+// A launch with `bytes` of dynamic LDS that raises the kernel's allowance only above the 64 KB a kernel has by default (the BNN step loops, the fold-based
+// kernels of the tabular study; other launchers call ensure() unconditionally).  `allow`: the call site's own static, one per kernel instantiation.
+template <class... P, class... A>
+int launch_lds(void (*kernel)(P...), LdsAllowance& allow, dim3 grid, dim3 block, size_t bytes, hipStream_t s, const A&... args) {
+  if (bytes > 64 * 1024) allow.ensure(kernel, bytes);
+  kernel<<<grid, block, bytes, s>>>(args...);
+  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+}
+
 // Operand element types (include/pfn_hip.h PFN_PREC_*): two 16-bit formats on the matrix cores at the same rate and bytes, and the exact-f32 parity mode.
 inline bool prec_is16(int p) { return p == PFN_PREC_BF16 || p == PFN_PREC_FP16; }
 inline int prec_esize(int p) { return prec_is16(p) ? 2 : 4; }

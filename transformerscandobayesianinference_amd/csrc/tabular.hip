@@ -272,10 +272,7 @@ int launch_auc_counts(const float* scores, const float* labels, int T, int C, in
 
 int launch_knn_cv(const KnnCvArgs& a, hipStream_t s) {
   static LdsAllowance allowance;
-  const size_t lds = knn_cv_lds_bytes(a.n, a.T, a.F);
-  if (lds > 64 * 1024) allowance.ensure(knn_cv_kernel, lds);
-  knn_cv_kernel<<<dim3((unsigned)a.P), dim3(256), lds, s>>>(a);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+  return launch_lds(knn_cv_kernel, allowance, dim3((unsigned)a.P), dim3(256), knn_cv_lds_bytes(a.n, a.T, a.F), s, a);
 }
 
 }  // namespace pfn

@@ -520,26 +520,40 @@ def auc_from_counts(counts):
         return np.where(pairs > 0, (2 * c[:, 2] + c[:, 3]).astype(np.float64) / (2. * pairs), np.nan)
 
 
-def knn_cv_check(n, T, F):
-    for name, v in (('n', n), ('T', T), ('F', F)):
-        lo, hi = KNN_LIMITS[name]
+def _limits_check(prefix, limits, **sizes):
+    """The limits of a fold-based launch (KNN_LIMITS, LOGIT_LIMITS, GPC_LIMITS), raised as ValueError in the order given.  Host only."""
+    for name, v in sizes.items():
+        lo, hi = limits[name]
         if not lo <= v <= hi:
-            raise ValueError(f'knn_cv: {name} = {v} outside {lo} .. {hi}')
+            raise ValueError(f'{prefix}: {name} = {v} outside {lo} .. {hi}')
+
+
+def _fold_args(check, train, labels, fold, test=None, NC=None, splits=None, also_f32=(), layout='train [P, n, F], labels [P, n], test [P, T, F], fold [P, n]'):
+    """What knn_cv, logistic_cv and the gpc_* wrappers check alike, ValueErrors first and the device after: the shapes (`layout` is their message), the launch's
+    limits (`check`, with NC where the call has candidates), P >= 1 and splits = (n_splits, most folds) where the call has n_splits, then train on the GPU, train /
+    labels / test / `also_f32` f32 and contiguous there, fold int32.  A call without test rows counts as T = 1.  Returns (P, n, T, F)."""
+    if train.dim() != 3 or labels.shape != train.shape[:2] or fold.shape != train.shape[:2] or \
+            (test is not None and (test.dim() != 3 or test.shape[0] != train.shape[0] or test.shape[2] != train.shape[2])):
+        raise ValueError(layout)
+    P, n, F = train.shape
+    T = 1 if test is None else test.shape[1]
+    check(n, T, F, *(() if NC is None else (NC,)))
+    if P < 1 or (splits is not None and not 2 <= int(splits[0]) <= splits[1]):
+        raise ValueError('P >= 1' if splits is None else f'P >= 1, 2 <= n_splits = {splits[0]} <= {splits[1]}')
+    _hip.require_gpu_tensor(train, 'train')
+    _bnn_f32(train, labels, *(() if test is None else (test,)), *also_f32)
+    assert fold.dtype == torch.int32 and fold.is_contiguous() and fold.device == train.device, 'fold [P, n] int32'
+    return P, n, T, F
+
+
+def knn_cv_check(n, T, F):
+    _limits_check('knn_cv', KNN_LIMITS, n=n, T=T, F=F)
 
 
 def knn_cv(train, labels, test, fold):
     """Neighbour lists for the kNN grid search of every problem in one launch (pfn_knn_cv): train [P,n,F], labels [P,n], test [P,T,F] f32 and fold [P,n] int32
     (the CV test fold of each train row, 0 .. 4) on the GPU.  Returns int32 (cv_correct [P,5,5], test_pos [P,T,5], test_nbr [P,T,5])."""
-    if train.dim() != 3 or test.dim() != 3 or test.shape[0] != train.shape[0] or test.shape[2] != train.shape[2] or labels.shape != train.shape[:2] or fold.shape != train.shape[:2]:
-        raise ValueError('train [P, n, F], labels [P, n], test [P, T, F], fold [P, n]')
-    P, n, F = train.shape
-    T = test.shape[1]
-    knn_cv_check(n, T, F)
-    if P < 1:
-        raise ValueError('P >= 1')
-    _hip.require_gpu_tensor(train, 'train')
-    _bnn_f32(train, labels, test)
-    assert fold.dtype == torch.int32 and fold.is_contiguous() and fold.device == train.device, 'fold [P, n] int32'
+    P, n, T, F = _fold_args(knn_cv_check, train, labels, fold, test)
     dev = train.device
     cv_correct = torch.empty(P, KNN_MAX_K, KNN_MAX_FOLDS, dtype=torch.int32, device=dev)
     test_pos = torch.empty(P, T, KNN_MAX_K, dtype=torch.int32, device=dev)
@@ -558,10 +572,7 @@ LOGIT_LIMITS = dict(n=(4, 128), T=(1, 128), F=(1, 128), NC=(1, LOGIT_MAX_CANDIDA
 
 
 def logistic_cv_check(n, T, F, NC=1):
-    for name, v in (('n', n), ('T', T), ('F', F), ('NC', NC)):
-        lo, hi = LOGIT_LIMITS[name]
-        if not lo <= v <= hi:
-            raise ValueError(f'logistic_cv: {name} = {v} outside {lo} .. {hi}')
+    _limits_check('logistic_cv', LOGIT_LIMITS, n=n, T=T, F=F, NC=NC)
 
 
 def logistic_cv(train, labels, test, fold, n_splits, cand_C, cand_kind, return_coef=False):
@@ -569,20 +580,11 @@ def logistic_cv(train, labels, test, fold, n_splits, cand_C, cand_kind, return_c
     CV test fold of each train row) on the GPU; cand_C / cand_kind: the NC candidates' C and penalty code | LOGIT_FIT_INTERCEPT (host sequences).  Slot
     s < n_splits of a candidate is the fit without fold s, slot n_splits the refit on all rows.  Returns (cv_correct [P,NC,5] int32, test_z [P,NC,T] f32,
     status [P,NC,6,2] int32 = (LOGIT_* exit reason, iterations), coef [P,NC,6,F+1] f32 or None)."""
-    if train.dim() != 3 or test.dim() != 3 or test.shape[0] != train.shape[0] or test.shape[2] != train.shape[2] or labels.shape != train.shape[:2] or fold.shape != train.shape[:2]:
-        raise ValueError('train [P, n, F], labels [P, n], test [P, T, F], fold [P, n]')
-    P, n, F = train.shape
-    T = test.shape[1]
     cand_C, cand_kind = [float(v) for v in cand_C], [int(v) for v in cand_kind]
     NC = len(cand_C)
-    logistic_cv_check(n, T, F, NC)
     if len(cand_kind) != NC or any((k & 3) == 3 or not 0 <= k < 8 for k in cand_kind) or not all(v > 0 for v in cand_C):
         raise ValueError('cand_C [NC] > 0, cand_kind [NC] = LOGIT_NONE / LOGIT_L1 / LOGIT_L2, optionally | LOGIT_FIT_INTERCEPT')
-    if P < 1 or not 2 <= int(n_splits) <= LOGIT_FOLDS:
-        raise ValueError(f'P >= 1, 2 <= n_splits = {n_splits} <= {LOGIT_FOLDS}')
-    _hip.require_gpu_tensor(train, 'train')
-    _bnn_f32(train, labels, test)
-    assert fold.dtype == torch.int32 and fold.is_contiguous() and fold.device == train.device, 'fold [P, n] int32'
+    P, n, T, F = _fold_args(logistic_cv_check, train, labels, fold, test, NC=NC, splits=(n_splits, LOGIT_FOLDS))
     dev = train.device
     c_dev = torch.tensor(cand_C, dtype=torch.float32).to(dev)
     k_dev = torch.tensor(cand_kind, dtype=torch.int32).to(dev)
@@ -603,24 +605,15 @@ GPC_LIMITS = dict(n=(4, GPC_MAX_N), T=(1, 128), F=(1, 128), NC=(1, GPC_MAX_CANDI
 
 
 def gpc_check(n, T, F, NC=1):
-    for name, v in (('n', n), ('T', T), ('F', F), ('NC', NC)):
-        lo, hi = GPC_LIMITS[name]
-        if not lo <= v <= hi:
-            raise ValueError(f'gpc: {name} = {v} outside {lo} .. {hi}')
+    _limits_check('gpc', GPC_LIMITS, n=n, T=T, F=F, NC=NC)
 
 
 def _gpc_args(theta, train, labels, fold, n_splits, test=None):
-    if train.dim() != 3 or labels.shape != train.shape[:2] or fold.shape != train.shape[:2] or theta.dim() != 4 or theta.shape[0] != train.shape[0] or \
-            tuple(theta.shape[2:]) != (GPC_SLOTS, 2) or (test is not None and (test.dim() != 3 or test.shape[0] != train.shape[0] or test.shape[2] != train.shape[2])):
-        raise ValueError('theta [P, NC, 6, 2], train [P, n, F], labels [P, n], fold [P, n], test [P, T, F]')
-    P, n, F = train.shape
+    layout = 'theta [P, NC, 6, 2], train [P, n, F], labels [P, n], fold [P, n], test [P, T, F]'
+    if theta.dim() != 4 or theta.shape[:1] != train.shape[:1] or tuple(theta.shape[2:]) != (GPC_SLOTS, 2):
+        raise ValueError(layout)
     NC = theta.shape[1]
-    gpc_check(n, 1 if test is None else test.shape[1], F, NC)
-    if P < 1 or not 2 <= int(n_splits) <= GPC_FOLDS:
-        raise ValueError(f'P >= 1, 2 <= n_splits = {n_splits} <= {GPC_FOLDS}')
-    _hip.require_gpu_tensor(train, 'train')
-    _bnn_f32(train, labels, theta, *(() if test is None else (test,)))
-    assert fold.dtype == torch.int32 and fold.is_contiguous() and fold.device == train.device, 'fold [P, n] int32'
+    P, n, _, F = _fold_args(gpc_check, train, labels, fold, test, NC=NC, splits=(n_splits, GPC_FOLDS), also_f32=(theta,), layout=layout)
     return P, n, F, NC
 
 

@@ -30,6 +30,7 @@ signature still runs through `batch_pred`, one window at a time, as the referenc
 so a PFN trained here loads into the reference's `TransformerModel` and vice versa: the state-dict keys are the
 reference's (INTEGRATION.md).
 """
+import functools
 import os
 import time
 import warnings
@@ -344,6 +345,60 @@ def batch_pred(metric_function, eval_xs, eval_ys, categorical_feats, start=2, ta
     return np.array(metrics), np.array(outputs).T
 
 
+## What the baseline arms share (kNN, logistic regression, GP classifier), each arm handing in what is its own: the problems before the launch, GridSearchCV's
+## ranking, the tail after the selection, the single-problem form
+
+def _fold_problems(x, y, test_x, one_class_error=None):
+    """Before the launch, for W problems: x [n, W, F] normalised train rows, y [n, W], test_x [T, W, F] -> (n_splits = min(CV, n // 2), folds [W, n] int32: every
+    row's test fold, cls [n, W] bool: label > 0.5, both on the host, and the kernels' operands on x's device: (train [W, n, F], labels [W, n], test [W, T, F] f32,
+    fold [W, n] int32)).  one_class_error: the arm's name where a window whose train rows hold one class raises ValueError, as scikit-learn's fit does."""
+    n, W, _ = x.shape
+    n_splits = min(CV, n // 2)
+    cls = y.detach().cpu().numpy() > 0.5
+    if one_class_error is not None:
+        for w in range(W):
+            if cls[:, w].all() or not cls[:, w].any():
+                raise ValueError(f'{one_class_error}_metric: the train rows of window {w} hold one class only')
+    folds = np.stack([_stratified_folds(cls[:, w], n_splits) for w in range(W)])
+    return n_splits, folds, cls, (x.float().transpose(0, 1).contiguous(), y.float().t().contiguous(), test_x.float().transpose(0, 1).contiguous(),
+                                  torch.from_numpy(folds).to(x.device))
+
+
+def _fold_sizes(folds, n_splits):
+    """The rows in every test fold of one problem, f64 [n_splits]: what a fold's count of correct rows is divided by."""
+    return np.bincount(np.asarray(folds), minlength=n_splits)[:n_splits].astype(np.float64)
+
+
+def _first_maximum(scores, all_failed_error=None):
+    """GridSearchCV's ranking of one problem: scores [candidates, n_splits] f64, NaN where a fit did not run -> (mean_test_score [candidates], index of the best:
+    the FIRST maximum, NaN ranks last).  all_failed_error: the arm's name where scores that are all NaN raise ValueError; without it candidate 0 wins then."""
+    if all_failed_error is not None and np.isnan(scores).all():
+        raise ValueError(f'{all_failed_error}_metric: every fit of every candidate failed (each fold\'s training part holds one class)')
+    mean = scores.mean(axis=1)
+    return mean, int(np.argmax(np.where(np.isnan(mean), -np.inf, mean)))
+
+
+def _fold_metric(chosen, test_y):
+    """After the selection: chosen = per problem (mean_test_score, best, proba [T] f64), test_y [T, W] on the GPU -> (ROC-AUC [W], proba [T, W]) numpy."""
+    proba = np.stack([c[2] for c in chosen], 1)
+    metric, undefined = roc_auc_columns(torch.from_numpy(proba).float().to(test_y.device), test_y)
+    _report_undefined(undefined, f'of {len(chosen)} windows')
+    return metric, proba
+
+
+def _single_problem(batched):
+    """Decorator that gives a documented metric function (x [n, F], y [n], test_x [T, F], test_y [T], cat_features) -> (metric, proba [T]) its body: the batched
+    form on one problem.  The batched form itself is attached as `.batched`; `batch_pred` uses it."""
+    def build(documented):
+        @functools.wraps(documented)
+        def metric_function(x, y, test_x, test_y, cat_features):
+            metric, proba = batched(x[:, None], y[:, None], test_x[:, None], test_y[:, None])
+            return metric[0], proba[:, 0]
+        metric_function.batched = batched
+        return metric_function
+    return build
+
+
 ## KNN (reference tabular.py:349-369)
 
 def _stratified_folds(y, n_splits):
@@ -383,15 +438,14 @@ def _knn_select(cv_correct, folds, n_splits, ks, test_pos):
     f64 -- NaN where k exceeds the fold's training rows (the fit fails, error_score = nan) --, a candidate's score the mean over folds, the best candidate the
     FIRST maximum (NaN ranks last), the refit on all rows gives predict_proba[:, 1] = positives among the k* nearest / k*.
     Returns (mean_test_score [len(ks)] f64, best k, proba [T] f64)."""
-    sizes = np.bincount(np.asarray(folds), minlength=n_splits)[:n_splits].astype(np.float64)
+    sizes = _fold_sizes(folds, n_splits)
     correct = np.asarray(cv_correct, dtype=np.float64)
     scores = np.empty((len(ks), n_splits), dtype=np.float64)
     for i, k in enumerate(ks):
         scores[i] = correct[k - 1, :n_splits] / sizes
         scores[i, sizes.sum() - sizes < k] = np.nan
-    mean = scores.mean(axis=1)
-    ranked = np.where(np.isnan(mean), -np.inf, mean)
-    best = int(ks[int(np.argmax(ranked))])
+    mean, first = _first_maximum(scores)
+    best = int(ks[first])
     proba = np.asarray(test_pos, dtype=np.float64)[:, best - 1] / float(best)
     return mean, best, proba
 
@@ -401,30 +455,21 @@ def _knn_batched(x, y, test_x, test_y, return_k=False):
     pfn_knn_cv launch finds every neighbour list; the folds (before) and the scores (after) are host arithmetic.  Returns (ROC-AUC [W], proba [T, W]) numpy,
     and with return_k the chosen k of every problem as a third entry."""
     n, W, F = x.shape
-    T = test_x.shape[0]
-    hipops.knn_cv_check(n, T, F)
-    ks, n_splits = _knn_grid(n)
-    y_host = y.detach().cpu().numpy()
-    folds = np.stack([_stratified_folds(y_host[:, w] > 0.5, n_splits) for w in range(W)])      # [W, n]
-    cv_correct, test_pos, _ = hipops.knn_cv(x.float().transpose(0, 1).contiguous(), y.float().t().contiguous(), test_x.float().transpose(0, 1).contiguous(),
-                                            torch.from_numpy(folds).to(x.device))
+    hipops.knn_cv_check(n, test_x.shape[0], F)
+    ks, _ = _knn_grid(n)
+    n_splits, folds, _, operands = _fold_problems(x, y, test_x)
+    cv_correct, test_pos, _ = hipops.knn_cv(*operands)
     cv_correct, test_pos = cv_correct.cpu().numpy(), test_pos.cpu().numpy()
     chosen = [_knn_select(cv_correct[w], folds[w], n_splits, ks, test_pos[w]) for w in range(W)]
-    proba = np.stack([c[2] for c in chosen], 1)      # [T, W]
-    metric, undefined = roc_auc_columns(torch.from_numpy(proba).float().to(x.device), test_y)
-    _report_undefined(undefined, f'of {W} windows')
+    metric, proba = _fold_metric(chosen, test_y)
     return (metric, proba, [c[1] for c in chosen]) if return_k else (metric, proba)
 
 
+@_single_problem(_knn_batched)
 def knn_metric(x, y, test_x, test_y, cat_features):
     """Reference tabular.py:351-369 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (ROC-AUC, proba [T]) of
     a KNeighborsClassifier whose k is grid-searched over 1 .. min(5, n - 2) by min(5, n // 2)-fold stratified cross-validation.  `knn_metric.batched` is the
     same for many problems in one launch; `batch_pred` uses it."""
-    metric, proba = _knn_batched(x[:, None], y[:, None], test_x[:, None], test_y[:, None])
-    return metric[0], proba[:, 0]
-
-
-knn_metric.batched = _knn_batched
 
 
 ## Logistic regression (reference tabular.py:325-346)
@@ -460,14 +505,9 @@ def _logistic_select(cv_correct, status, folds, n_splits, entry_fit, test_z):
     the best entry the FIRST maximum over the full entry order (NaN ranks last; where a failed fold leaves every mean NaN that is entry 0, as in sklearn),
     predict_proba[:, 1] = sigmoid(decision value of its refit) in f64.
     Returns (mean_test_score [entries] f64, best entry index, proba [T] f64); raises ValueError when every fit of every candidate failed."""
-    sizes = np.bincount(np.asarray(folds), minlength=n_splits)[:n_splits].astype(np.float64)
-    scores = np.asarray(cv_correct, dtype=np.float64)[:, :n_splits] / sizes
-    failed = np.asarray(status)[:, :n_splits, 0] == hipops.LOGIT_ONE_CLASS
-    if failed.all():
-        raise ValueError('logistic_metric: every fit of every candidate failed (each fold\'s training part holds one class)')
-    scores[failed] = np.nan
-    mean = scores.mean(axis=1)[np.asarray(entry_fit)]
-    best = int(np.argmax(np.where(np.isnan(mean), -np.inf, mean)))
+    scores = np.asarray(cv_correct, dtype=np.float64)[:, :n_splits] / _fold_sizes(folds, n_splits)
+    scores[np.asarray(status)[:, :n_splits, 0] == hipops.LOGIT_ONE_CLASS] = np.nan
+    mean, best = _first_maximum(scores[np.asarray(entry_fit)], all_failed_error='logistic')      # every entry has the scores of its fit
     z = np.asarray(test_z, dtype=np.float64)[entry_fit[best]]
     e = np.exp(-np.abs(z))
     proba = np.where(z >= 0, 1 / (1 + e), e / (1 + e))
@@ -480,34 +520,21 @@ def _logistic_batched(x, y, test_x, test_y, return_params=False):
     (ROC-AUC [W], proba [T, W]) numpy, and with return_params the chosen parameter dict of every problem as a third entry.  Raises ValueError, as sklearn's fit
     does, for a window whose train rows hold one class."""
     n, W, F = x.shape
-    T = test_x.shape[0]
     entries, cands, entry_fit = _logistic_grid()
-    hipops.logistic_cv_check(n, T, F, len(cands))
-    n_splits = min(CV, n // 2)
-    y_host = y.detach().cpu().numpy() > 0.5
-    for w in range(W):
-        if y_host[:, w].all() or not y_host[:, w].any():
-            raise ValueError(f'logistic_metric: the train rows of window {w} hold one class only')
-    folds = np.stack([_stratified_folds(y_host[:, w], n_splits) for w in range(W)])      # [W, n]
-    cv_correct, test_z, status, _ = hipops.logistic_cv(x.float().transpose(0, 1).contiguous(), y.float().t().contiguous(), test_x.float().transpose(0, 1).contiguous(),
-                                                       torch.from_numpy(folds).to(x.device), n_splits, [c for c, _ in cands], [k for _, k in cands])
+    hipops.logistic_cv_check(n, test_x.shape[0], F, len(cands))
+    n_splits, folds, _, operands = _fold_problems(x, y, test_x, one_class_error='logistic')
+    cv_correct, test_z, status, _ = hipops.logistic_cv(*operands, n_splits, [c for c, _ in cands], [k for _, k in cands])
     cv_correct, test_z, status = cv_correct.cpu().numpy(), test_z.cpu().numpy(), status.cpu().numpy()
     chosen = [_logistic_select(cv_correct[w], status[w], folds[w], n_splits, entry_fit, test_z[w]) for w in range(W)]
-    proba = np.stack([c[2] for c in chosen], 1)      # [T, W]
-    metric, undefined = roc_auc_columns(torch.from_numpy(proba).float().to(x.device), test_y)
-    _report_undefined(undefined, f'of {W} windows')
+    metric, proba = _fold_metric(chosen, test_y)
     return (metric, proba, [entries[c[1]] for c in chosen]) if return_params else (metric, proba)
 
 
+@_single_problem(_logistic_batched)
 def logistic_metric(x, y, test_x, test_y, cat_features):
     """Reference tabular.py:326-346 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (ROC-AUC, proba [T]) of
     the LogisticRegression that GridSearchCV picks from param_grid['logistic'] by min(5, n // 2)-fold stratified cross-validation, every candidate solved to its
     optimum.  `logistic_metric.batched` is the same for many problems in one launch; `batch_pred` uses it."""
-    metric, proba = _logistic_batched(x[:, None], y[:, None], test_x[:, None], test_y[:, None])
-    return metric[0], proba[:, 0]
-
-
-logistic_metric.batched = _logistic_batched
 
 
 ## GP classifier (reference tabular.py:480-503)
@@ -551,15 +578,12 @@ def _gp_select(cv_f, status, folds, y, n_splits, test_f, test_var):
     folds, cls = np.asarray(folds), np.asarray(y) > 0.5
     reasons = np.asarray(status)[:, :n_splits, 0]
     ran = (reasons == hipops.GPC_CONVERGED) | (reasons == hipops.GPC_CAPPED)
-    if not ran.any():
-        raise ValueError('gp_metric: every fit of every candidate failed (each fold\'s training part holds one class)')
     right = (_gp_f_star(cv_f) > 0) == cls[None, :]      # [NC, n]
+    sizes = _fold_sizes(folds, n_splits)
     scores = np.full(ran.shape, np.nan)
     for s in range(n_splits):
-        held = folds == s
-        scores[:, s] = np.where(ran[:, s], right[:, held].sum(1) / float(held.sum()), np.nan)
-    mean = scores.mean(axis=1)
-    best = int(np.argmax(np.where(np.isnan(mean), -np.inf, mean)))
+        scores[:, s] = np.where(ran[:, s], right[:, folds == s].sum(1) / sizes[s], np.nan)
+    mean, best = _first_maximum(scores, all_failed_error='gp')
     return mean, best, _gp_proba(_gp_f_star(np.asarray(test_f)[best]), np.asarray(test_var)[best])
 
 
@@ -588,18 +612,10 @@ def _gp_batched(x, y, test_x, test_y, optimize=True, return_params=False, counte
     problem dict(kernel=(c, l) of the chosen refit after optimisation, start=(c, l) of its candidate, index).  `counters`, a dict, receives the L-BFGS pass
     count and the fits' exit reasons.  Raises ValueError, as scikit-learn's fit does, for a window whose train rows hold one class."""
     n, W, F = x.shape
-    T = test_x.shape[0]
     cands = _gp_grid()
     NC = len(cands)
-    hipops.gpc_check(n, T, F, NC)
-    n_splits = min(CV, n // 2)
-    y_host = y.detach().cpu().numpy() > 0.5
-    for w in range(W):
-        if y_host[:, w].all() or not y_host[:, w].any():
-            raise ValueError(f'gp_metric: the train rows of window {w} hold one class only')
-    folds = np.stack([_stratified_folds(y_host[:, w], n_splits) for w in range(W)])      # [W, n]
-    xs, ys, ts = x.float().transpose(0, 1).contiguous(), y.float().t().contiguous(), test_x.float().transpose(0, 1).contiguous()
-    folds_dev = torch.from_numpy(folds).to(x.device)
+    hipops.gpc_check(n, test_x.shape[0], F, NC)
+    n_splits, folds, cls, (xs, ys, ts, folds_dev) = _fold_problems(x, y, test_x, one_class_error='gp')
     shape = (W, NC, hipops.GPC_SLOTS, 2)
     theta = torch.tensor(cands, dtype=torch.float64).log().float().to(x.device)[None, :, None, :].expand(shape).contiguous()
     if optimize:
@@ -614,23 +630,17 @@ def _gp_batched(x, y, test_x, test_y, optimize=True, return_params=False, counte
     if counters is not None:
         counters['status'] = status
         counters['theta'] = theta_host
-    y01 = y_host.astype(np.float64)
+    y01 = cls.astype(np.float64)
     chosen = [_gp_select(cv_f[w], status[w], folds[w], y01[:, w], n_splits, test_f[w], test_var[w]) for w in range(W)]
-    proba = np.stack([c[2] for c in chosen], 1)      # [T, W]
-    metric, undefined = roc_auc_columns(torch.from_numpy(proba).float().to(x.device), test_y)
-    _report_undefined(undefined, f'of {W} windows')
+    metric, proba = _fold_metric(chosen, test_y)
     if not return_params:
         return metric, proba
     params = [dict(kernel=tuple(float(v) for v in np.exp(theta_host[w, c[1], n_splits])), start=cands[c[1]], index=c[1]) for w, c in enumerate(chosen)]
     return metric, proba, params
 
 
+@_single_problem(_gp_batched)
 def gp_metric(x, y, test_x, test_y, cat_features):
     """Reference tabular.py:480-503 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (ROC-AUC, proba [T]) of
     the GaussianProcessClassifier that GridSearchCV picks from the 24 kernels c * RBF(l) of param_grid['gp'] by min(5, n // 2)-fold stratified cross-validation
     (INTEGRATION.md).  `gp_metric.batched` is the same for many problems at once; `batch_pred` uses it."""
-    metric, proba = _gp_batched(x[:, None], y[:, None], test_x[:, None], test_y[:, None])
-    return metric[0], proba[:, 0]
-
-
-gp_metric.batched = _gp_batched

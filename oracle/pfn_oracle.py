@@ -47,7 +47,7 @@ def d_q_mask(T, sep, dtype, device):
     return torch.zeros(T, T, dtype=dtype, device=device).masked_fill(~allowed, float('-inf'))
 
 
-# ---- dropout masks: the integers of csrc/pfn_kernels.h (mix32 / dropout_site_seed / dropout_pair_seed / dropout_keep), in numpy ----
+# ---- dropout masks: the integers of csrc/pfn_host.h (mix32) and csrc/pfn_kernels.h (dropout_site_seed / dropout_pair_seed / dropout_keep), in numpy ----
 _M32 = 0xFFFFFFFF
 
 
@@ -85,27 +85,27 @@ UNIT_ROUNDOFF = {'bf16': 2.0 ** -9, 'fp16': 2.0 ** -12}
 # switches the site, None = every 16-bit pass.  Lines: transformerscandobayesianinference_amd/csrc/pfn_api.hip unless a file is named.
 ROUNDING_SITES = {
     # name        kind  when           what is stored, and where
-    'W':         ('Rv', None,          'the operand copies of every weight matrix: pfn_prepare_params launch_cast_params :696 (biases, LayerNorm weights: f32 `params + ...`)'),
-    'X':         ('Rv', None,          'GEMM A operands cut from f32 rows: x0_t embed_fwd :769, x1_t / x2_t layer_tail_forward :399 :411 :427 :440, xt_t :859-861'),
-    'xaug':      ('Rv', 'emb_t',       'the embedding weight gradient reads x | y from xaug_t :770-771 -> launch_gemm_tn :1328 (the forward embeds the f32 inputs)'),
-    'emb_grad':  ('Rg', 'emb_t',       'd(src) leaves layer 0 in gA_t: layer_backward_dx out_f32 = (l == 0 && !emb_t) :1313'),
-    'qkv':       ('R',  None,          'q|k|v projection out_t = a.qkv :799 (keys after the f32 shift, EPI_ROWSHIFT :807); gradient at.dqkv = a.dqkv_t :1303'),
+    'W':         ('Rv', None,          'the operand copies of every weight matrix: pfn_prepare_params launch_cast_params :689 (biases, LayerNorm weights: f32 `params + ...`)'),
+    'X':         ('Rv', None,          'GEMM A operands cut from f32 rows: x0_t embed_fwd :762, x1_t / x2_t layer_tail_forward :393 :405 :421 :434, xt_t :852-854'),
+    'xaug':      ('Rv', 'emb_t',       'the embedding weight gradient reads x | y from xaug_t :763-764 -> launch_gemm_tn :1321 (the forward embeds the f32 inputs)'),
+    'emb_grad':  ('Rg', 'emb_t',       'd(src) leaves layer 0 in gA_t: layer_backward_dx out_f32 = (l == 0 && !emb_t) :1306'),
+    'qkv':       ('R',  None,          'q|k|v projection out_t = a.qkv :792 (keys after the f32 shift, EPI_ROWSHIFT :800); gradient at.dqkv = a.dqkv_t :1296'),
     'P':         ('Rv', None,          'softmax numerators enter P.V and dO^T.P as MFMA operands: attention.hip :13-14 ("P and dS go from the accumulator straight into the operand slots" :791)'),
     'dS':        ('Rg', None,          'dS = P (dP - delta) in operand precision, the values dK, dQ consume: attention.hip :790-792'),
-    'ctx':       ('R',  None,          'attention output at.ctx = a.ctx :821; its gradient d(ctx) out_t = dctx_t / top_dctx_t :1270-1271'),
-    'y_grad':    ('Rg', None,          'LayerNorm-input gradients dy2_t :551 :534, dy1_t :530 :570 (launch_layernorm_bwd dx_t / GemmLNB::dx_t)'),
-    'Y':         ('Rv', 'y16',         'pre-LayerNorm sums in fp16 inside the fused GEMMs, g.y16 :399 :427: the next residual add and the LayerNorm backward read the rounded sum'),
-    'Yu':        ('Rv', 'y16u',        'fp16 sums ahead of a separate LayerNorm: EPI_RESID_T | EPI_OUT_T :407 :435 -- residual from the operand copy, the rounded sum is what is normalised'),
-    'x1_grad':   ('Rg', 'not fuse_lnb', 'dx1 = dh . W1 + dy2 out_t = dx1_t :566-567 (fused: the sum stays in the epilogue of gemm_nt_lnbwd_kernel :563)'),
-    'out_grad':  ('Rg', 'per layer',   'gradient of a layer output in gA_t: the top layer by launch_scatter_test_rows :1208-1209 unless it runs on the test rows (dxt f32 :1225), '
-                                       'lower layers by layer_backward_dx EPI_OUT_T :584-585 unless fuse_lnb (:582)'),
-    'act':       ('Rv', None,          'GELU output u.h :416, decoder dt :450'),
-    'dgelu':     ('Rv', None,          'the stored GELU derivative out2_t = u.hpre :416, dpre :450, multiplied in EPI_GELU_BWD :557 :462'),
-    'pre_grad':  ('Rg', None,          'd(pre-activation) dh_t :558, dd_t :463'),
-    'dlog':      ('Rg', None,          'dlogits cast to dlog_t: launch_cast_rows :1190 (times the loss scale in fp16)'),
-    'drop_grad': ('Rg', 'dropout',     'masked copies of the LayerNorm-input gradients dy2m_t :554, dy1m_t :1267 (launch_dropout_scale writes operand precision)'),
-    'center':    (None, 'center',      'not a rounding, but it decides what K rounds: the keys leave the projection centred per dataset, launch_key_shift :805-807 (key_centering :161)'),
-    'drop_act':  ('Rv', 'dropout',    'the FFN dropout rescales h and hpre in place in operand precision: launch_dropout_scale :419'),
+    'ctx':       ('R',  None,          'attention output at.ctx = a.ctx :814; its gradient d(ctx) out_t = dctx_t / top_dctx_t :1263-1264'),
+    'y_grad':    ('Rg', None,          'LayerNorm-input gradients dy2_t :545 :528, dy1_t :524 :564 (launch_layernorm_bwd dx_t / GemmLNB::dx_t)'),
+    'Y':         ('Rv', 'y16',         'pre-LayerNorm sums in fp16 inside the fused GEMMs, g.y16 :393 :421: the next residual add and the LayerNorm backward read the rounded sum'),
+    'Yu':        ('Rv', 'y16u',        'fp16 sums ahead of a separate LayerNorm: EPI_RESID_T | EPI_OUT_T :401 :429 -- residual from the operand copy, the rounded sum is what is normalised'),
+    'x1_grad':   ('Rg', 'not fuse_lnb', 'dx1 = dh . W1 + dy2 out_t = dx1_t :560-561 (fused: the sum stays in the epilogue of gemm_nt_lnbwd_kernel :557)'),
+    'out_grad':  ('Rg', 'per layer',   'gradient of a layer output in gA_t: the top layer by launch_scatter_test_rows :1201-1202 unless it runs on the test rows (dxt f32 :1218), '
+                                       'lower layers by layer_backward_dx EPI_OUT_T :578-579 unless fuse_lnb (:576)'),
+    'act':       ('Rv', None,          'GELU output u.h :410, decoder dt :444'),
+    'dgelu':     ('Rv', None,          'the stored GELU derivative out2_t = u.hpre :410, dpre :444, multiplied in EPI_GELU_BWD :551 :456'),
+    'pre_grad':  ('Rg', None,          'd(pre-activation) dh_t :552, dd_t :457'),
+    'dlog':      ('Rg', None,          'dlogits cast to dlog_t: launch_cast_rows :1183 (times the loss scale in fp16)'),
+    'drop_grad': ('Rg', 'dropout',     'masked copies of the LayerNorm-input gradients dy2m_t :548, dy1m_t :1260 (launch_dropout_scale writes operand precision)'),
+    'center':    (None, 'center',      'not a rounding, but it decides what K rounds: the keys leave the projection centred per dataset, launch_key_shift :798-800 (key_centering :155)'),
+    'drop_act':  ('Rv', 'dropout',    'the FFN dropout rescales h and hpre in place in operand precision: launch_dropout_scale :413'),
 }
 
 

@@ -32,12 +32,13 @@ def recorded():
 
 def test_the_symbols_are_declared_exported_and_bound_at_abi_10():
     header = open(os.path.join(ROOT, 'include', 'pfn_hip.h')).read()
-    kernels = open(os.path.join(CSRC, 'pfn_kernels.h')).read()
+    source = open(os.path.join(CSRC, 'gpc.hip')).read()      # the entry points stand beside their kernels
     lib = _hip.lib()
     for symbol, nargs in (('pfn_gpc_lml_grad', 13), ('pfn_gpc_predict', 16)):
         assert re.search(r'\b%s\s*\(' % symbol, header)
         assert symbol in _hip.SIGNATURES and hasattr(lib, symbol) and len(_hip.SIGNATURES[symbol][1]) == nargs
-    assert re.search(r'\blaunch_gpc_lml_grad\s*\(', kernels) and re.search(r'\blaunch_gpc_predict\s*\(', kernels)
+        assert re.search(r'^int %s\s*\(' % symbol, source, re.M), symbol      # defined there ...
+    assert re.search(r'\blaunch_gpc_lml_grad\s*\(', source) and re.search(r'\blaunch_gpc_predict\s*\(', source)      # ... and wired to its launcher
     assert _hip.ABI_VERSION == 10 and lib.pfn_abi_version() == 10 and '#define PFN_ABI_VERSION 10' in header
     for name, value in (('FOLDS', 5), ('SLOTS', 6), ('MAX_CANDIDATES', 64), ('MAX_N', 112), ('MAX_NEWTON', 100), ('UNUSED', 0), ('CONVERGED', 1), ('CAPPED', 2),
                         ('ONE_CLASS', 3), ('NONPOSITIVE', 4), ('NONFINITE', 5)):
@@ -50,7 +51,7 @@ def test_the_symbols_are_declared_exported_and_bound_at_abi_10():
 
 
 def lds_bytes(n):
-    """The launcher's dynamic LDS (pfn_kernels.h gpc_lds_bytes): K, the exponent arguments and the factor (inverted in place for the gradient) at the odd stride n | 1, sixteen vectors over
+    """The launcher's dynamic LDS (gpc.hip gpc_lds_bytes): K, the exponent arguments and the factor (inverted in place for the gradient) at the odd stride n | 1, sixteen vectors over
     the rows, eight words of reduction space."""
     return 4 * (3 * n * (n | 1) + 16 * n + 8)
 
@@ -76,7 +77,7 @@ def test_the_kernels_keep_their_register_scratch_and_lds_budgets(tmp_path):
         assert lds_bytes(114) > 160 * 1024      # (and not much room is given away)
         # the study's largest shape: one block per CU there, two from n = 56 down
         assert lds_bytes(80) == 4 * (3 * 80 * 81 + 1280 + 8) == 82912
-    text = open(os.path.join(CSRC, 'pfn_kernels.h')).read()
+    text = open(os.path.join(CSRC, 'gpc.hip')).read()
     assert '((size_t)3 * n * (n | 1) + 16 * (size_t)n + 8) * 4' in text
 
 

@@ -26,11 +26,12 @@ def recorded():
 
 def test_the_symbol_is_declared_exported_and_bound_at_abi_10():
     header = open(os.path.join(ROOT, 'include', 'pfn_hip.h')).read()
-    kernels = open(os.path.join(CSRC, 'pfn_kernels.h')).read()
+    source = open(os.path.join(CSRC, 'logistic.hip')).read()      # the entry point stands beside its kernel
     lib = _hip.lib()
     assert re.search(r'\bpfn_logistic_cv\s*\(', header)
     assert 'pfn_logistic_cv' in _hip.SIGNATURES and hasattr(lib, 'pfn_logistic_cv') and len(_hip.SIGNATURES['pfn_logistic_cv'][1]) == 17
-    assert re.search(r'\blaunch_logit_cv\s*\(', kernels)
+    assert re.search(r'^extern "C" int pfn_logistic_cv\s*\(', source, re.M)      # defined there ...
+    assert re.search(r'\blaunch_logit_cv\s*\(', source)      # ... and wired to its launcher
     assert _hip.ABI_VERSION == 10 and lib.pfn_abi_version() == 10 and '#define PFN_ABI_VERSION 10' in header
     for name, value in (('NONE', 0), ('L1', 1), ('L2', 2), ('FIT_INTERCEPT', 4), ('FOLDS', 5), ('SLOTS', 6), ('MAX_CANDIDATES', 64), ('UNUSED', 0), ('CONVERGED', 1),
                         ('STALLED', 2), ('CAPPED', 3), ('ONE_CLASS', 4), ('NONFINITE', 5)):
@@ -43,7 +44,7 @@ def test_the_symbol_is_declared_exported_and_bound_at_abi_10():
 
 
 def lds_bytes(n, F):
-    """The launcher's dynamic LDS (pfn_kernels.h logit_cv_lds_bytes), in floats: the n rows and the F + 1 rows of H at the odd stride (F + 1) | 1, six vectors over
+    """The launcher's dynamic LDS (logistic.hip logit_cv_lds_bytes), in floats: the n rows and the F + 1 rows of H at the odd stride (F + 1) | 1, six vectors over
     the rows (sign, mask, sigma, gradient weight, curvature weight, x . delta), five over the F + 1 coordinates (w, gradient, direction, alive, trial point),
     eight words of reduction space."""
     stride = (F + 1) | 1
@@ -70,7 +71,7 @@ def test_the_kernel_keeps_its_register_scratch_and_lds_budgets(tmp_path):
     assert lds_bytes(128, 128) == 4 * (257 * 129 + 768 + 645 + 8) == 138296 and lds_bytes(128, 128) + static_lds <= 160 * 1024
     # the study's shape: 141 rows of 61 floats, 480 + 305 + 8 words: four blocks share a CU's 160 KB
     assert lds_bytes(80, 60) == 4 * (141 * 61 + 480 + 305 + 8) == 37576 and 4 * (lds_bytes(80, 60) + static_lds) <= 160 * 1024
-    text = open(os.path.join(CSRC, 'pfn_kernels.h')).read()
+    text = open(os.path.join(CSRC, 'logistic.hip')).read()
     assert '((size_t)(n + F + 1) * ((F + 1) | 1) + 6 * (size_t)n + 5 * (size_t)(F + 1) + 8) * 4' in text
 
 

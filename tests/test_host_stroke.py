@@ -165,12 +165,13 @@ def test_integer_bounds_are_the_references_expressions(size):
 
 def test_the_symbols_are_declared_exported_and_bound_at_abi_10():
     header = open(os.path.join(ROOT, 'include', 'pfn_hip.h')).read()
-    kernels = open(os.path.join(CSRC, 'pfn_kernels.h')).read()
+    source = open(os.path.join(CSRC, 'stroke_prior.hip')).read()      # the entry points stand beside their kernels
     lib = _hip.lib()
     for symbol, nargs in (('pfn_stroke_render', 14), ('pfn_stroke_prior_sample', 30)):
         assert re.search(r'\b%s\s*\(' % symbol, header)
         assert symbol in _hip.SIGNATURES and hasattr(lib, symbol) and len(_hip.SIGNATURES[symbol][1]) == nargs
-    assert re.search(r'\blaunch_stroke_render\s*\(', kernels) and re.search(r'\blaunch_stroke_prior\s*\(', kernels)
+        assert re.search(r'^int %s\s*\(' % symbol, source, re.M), symbol      # defined there ...
+    assert re.search(r'\blaunch_stroke_render\s*\(', source) and re.search(r'\blaunch_stroke_prior\s*\(', source)      # ... and wired to its launcher
     assert _hip.ABI_VERSION == 10 and lib.pfn_abi_version() == 10 and '#define PFN_ABI_VERSION 10' in header
     for name, value in (('MAX_STROKES', 8), ('MAX_CLASSES', 16), ('MAX_WIDTH', 64), ('MAX_PASSES', 256), ('COORD_LIMIT', 4096)):
         assert f'#define PFN_STROKE_{name} {value}\n' in header and getattr(hipops, 'STROKE_' + name) == value, name

@@ -27,13 +27,14 @@ def recorded():
 
 def test_the_three_symbols_are_declared_exported_and_bound_at_abi_10():
     header = open(os.path.join(ROOT, 'include', 'pfn_hip.h')).read()
-    kernels = open(os.path.join(ROOT, 'transformerscandobayesianinference_amd', 'csrc', 'pfn_kernels.h')).read()
+    source = open(os.path.join(ROOT, 'transformerscandobayesianinference_amd', 'csrc', 'tabular.hip')).read()      # the entry points stand beside their kernels
     lib = _hip.lib()
     for name in NEW:
         assert re.search(r'\b' + name + r'\s*\(', header), name
         assert name in _hip.SIGNATURES and hasattr(lib, name)
+        assert re.search(r'^int ' + name + r'\s*\(', source, re.M), name      # defined there ...
     for launcher in ('launch_tab_windows', 'launch_auc_counts', 'launch_knn_cv'):
-        assert re.search(r'\b' + launcher + r'\s*\(', kernels), launcher
+        assert re.search(r'\b' + launcher + r'\s*\(', source), launcher      # ... and wired to its launcher
     assert _hip.ABI_VERSION == 10 and lib.pfn_abi_version() == 10 and '#define PFN_ABI_VERSION 10' in header
     assert '#define PFN_TAB_NORM_WITH_TEST 0' in header and '#define PFN_TAB_NORM_TRAIN_ONLY 1' in header
     assert (hipops.TAB_NORM_WITH_TEST, hipops.TAB_NORM_TRAIN_ONLY) == (0, 1)

@@ -5,10 +5,37 @@
 // gather, half-normal tail correction -- one pass over each logits row, one wave per row.
 // HBM-bound: algorithmic traffic is one read of the logits row (+ one write in the backward).
 #include <algorithm>
+#include <cstring>
 #include "pfn_device.h"
-#include "pfn_kernels.h"
+#include "pfn_host.h"
 
 namespace pfn {
+
+struct BarArgs {
+  const float* logits; long ld;  // [R, nbars]
+  const float* y;                // [R]
+  const float* borders;          // [nbars+1]
+  float* nll;                    // [R]
+  float* lse;                    // [R] saved for backward
+  int* bucket;                   // [R] saved for backward
+  long R; int nbars; int full_support;
+  // backward
+  const float* gout; float* dlogits;
+  // mean
+  float* mean_out;
+};
+// posterior summaries and draws (definitions: the header of that section below)
+struct BarStatsArgs {
+  const float* logits; long ld;  // [R, nbars]
+  const float* borders;          // [nbars+1]
+  long R; int nbars; int full_support;
+  int K; int kinds[PFN_BAR_STATS_MAX];      // PFN_BAR_STAT_*
+  int has_var, has_icdf;                    // any statistic of that kind among the K
+  const float* args; long arg_ld;           // [K] (arg_ld == 0) or [R, arg_ld]
+  float* out;                               // [R, K] (read by the backward)
+  const float* gout; float* dlogits;        // backward: [R, K], [R, nbars] with row stride ld
+  int n_samples; unsigned long long seed; float* samples;      // draws: [n_samples, R]
+};
 
 constexpr float HALFNORMAL_ICDF_HALF = 0.6744897501960817f;  // HalfNormal(1).icdf(0.5), bar_distribution.py:85-87
 constexpr float LOG_2 = 0.6931471805599453f;
@@ -144,27 +171,10 @@ __global__ __launch_bounds__(256) void bar_mean_bwd_kernel(BarArgs a) {
   }
 }
 
-static int rows_grid(long R) { return (int)std::max<long>(1, std::min<long>((R + 3) / 4, 8192)); }
-
-int launch_bar_nll_fwd(const BarArgs& a, hipStream_t s) {
+// every kernel of this file: four rows per workgroup of 256 threads, grid-stride over the a.R rows
+template <class A> static int launch_rows(void (*kernel)(A), const A& a, size_t lds, hipStream_t s) {
   if (a.R == 0) return PFN_OK;
-  if (a.nbars < 1) return PFN_ERR_ARGUMENT;
-  hipLaunchKernelGGL(bar_nll_fwd_kernel, dim3(rows_grid(a.R)), dim3(256), 0, s, a);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-}
-int launch_bar_nll_bwd(const BarArgs& a, hipStream_t s) {
-  if (a.R == 0) return PFN_OK;
-  hipLaunchKernelGGL(bar_nll_bwd_kernel, dim3(rows_grid(a.R)), dim3(256), 0, s, a);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-}
-int launch_bar_mean(const BarArgs& a, hipStream_t s) {
-  if (a.R == 0) return PFN_OK;
-  hipLaunchKernelGGL(bar_mean_kernel, dim3(rows_grid(a.R)), dim3(256), 0, s, a);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-}
-int launch_bar_mean_bwd(const BarArgs& a, hipStream_t s) {
-  if (a.R == 0) return PFN_OK;
-  hipLaunchKernelGGL(bar_mean_bwd_kernel, dim3(rows_grid(a.R)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(kernel, dim3((int)std::max<long>(1, std::min<long>((a.R + 3) / 4, 8192))), dim3(256), lds, s, a);
   return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 
@@ -584,23 +594,100 @@ template <bool LDS> __global__ __launch_bounds__(256) void bar_sample_kernel(Bar
   }
 }
 
-int launch_bar_stats(const BarStatsArgs& a, hipStream_t s) {
-  if (a.R == 0) return PFN_OK;
-  if (a.nbars <= BAR_LDS_MAX) hipLaunchKernelGGL(bar_stats_kernel<true>, dim3(rows_grid(a.R)), dim3(256), bar_lds_bytes(a.nbars), s, a);
-  else hipLaunchKernelGGL(bar_stats_kernel<false>, dim3(rows_grid(a.R)), dim3(256), 0, s, a);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+// the checks shared by pfn_bar_stats / pfn_bar_stats_backward / pfn_bar_sample; fills the common fields
+static int bar_stats_common(BarStatsArgs& a, const char* what, const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support) {
+  if (R < 0) return fail(PFN_ERR_ARGUMENT, "%s: R = %lld", what, (long long)R);
+  if (nbars < 1 || (full_support && nbars < 2)) return fail(PFN_ERR_ARGUMENT, "%s: nbars = %d%s", what, nbars, full_support ? " (full support needs two buckets)" : "");
+  if (ld < nbars) return fail(PFN_ERR_ARGUMENT, "%s: ld %lld < nbars %d", what, (long long)ld, nbars);
+  if (!logits || !borders) return fail(PFN_ERR_ARGUMENT, "%s: null pointer", what);
+  memset(&a, 0, sizeof(a));
+  a.logits = logits; a.ld = ld; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support ? 1 : 0;
+  return PFN_OK;
 }
-int launch_bar_stats_bwd(const BarStatsArgs& a, hipStream_t s) {
-  if (a.R == 0) return PFN_OK;
-  if (a.nbars <= BAR_LDS_MAX) hipLaunchKernelGGL(bar_stats_bwd_kernel<true>, dim3(rows_grid(a.R)), dim3(256), bar_lds_bytes(a.nbars), s, a);
-  else hipLaunchKernelGGL(bar_stats_bwd_kernel<false>, dim3(rows_grid(a.R)), dim3(256), 0, s, a);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-}
-int launch_bar_sample(const BarStatsArgs& a, hipStream_t s) {
-  if (a.R == 0 || a.n_samples == 0) return PFN_OK;
-  if (a.nbars <= BAR_LDS_MAX) hipLaunchKernelGGL(bar_sample_kernel<true>, dim3(rows_grid(a.R)), dim3(256), bar_lds_bytes(a.nbars), s, a);
-  else hipLaunchKernelGGL(bar_sample_kernel<false>, dim3(rows_grid(a.R)), dim3(256), 0, s, a);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+static int bar_stats_spec(BarStatsArgs& a, const char* what, const int32_t* kinds, int K, const float* args, int64_t arg_ld) {
+  if (K < 1 || K > PFN_BAR_STATS_MAX) return fail(PFN_ERR_ARGUMENT, "%s: K = %d outside 1 .. %d", what, K, PFN_BAR_STATS_MAX);
+  if (!kinds || !args) return fail(PFN_ERR_ARGUMENT, "%s: null pointer", what);
+  if (arg_ld != 0 && arg_ld < K) return fail(PFN_ERR_ARGUMENT, "%s: arg_ld %lld < K %d", what, (long long)arg_ld, K);
+  for (int k = 0; k < K; ++k) {
+    if (kinds[k] < PFN_BAR_STAT_MEAN || kinds[k] > PFN_BAR_STAT_EI_MIN) return fail(PFN_ERR_ARGUMENT, "%s: unknown statistic %d at position %d", what, (int)kinds[k], k);
+    a.kinds[k] = kinds[k];
+    a.has_var |= kinds[k] == PFN_BAR_STAT_VARIANCE; a.has_icdf |= kinds[k] == PFN_BAR_STAT_ICDF;
+  }
+  a.K = K; a.args = args; a.arg_ld = arg_ld;
+  return PFN_OK;
 }
 
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+int pfn_bar_nll_forward(const float* logits, int64_t ld, const float* y, const float* borders, int64_t R, int nbars,
+                        int full_support, float* nll, float* lse, int32_t* bucket, void* stream) {
+  if (R < 0 || nbars < 1 || (R > 0 && (!logits || !y || !borders || !nll || !lse || !bucket))) return fail(PFN_ERR_ARGUMENT, "bad bar_nll_forward arguments");
+  BarArgs a; memset(&a, 0, sizeof(a));
+  a.logits = logits; a.ld = ld; a.y = y; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support;
+  a.nll = nll; a.lse = lse; a.bucket = bucket;
+  PFN_TRY(launch_rows(bar_nll_fwd_kernel, a, 0, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_bar_nll_backward(const float* logits, int64_t ld, const float* lse, const int32_t* bucket, const float* gout,
+                         int64_t R, int nbars, float* dlogits, void* stream) {
+  if (R < 0 || nbars < 1 || (R > 0 && (!logits || !lse || !bucket || !gout || !dlogits))) return fail(PFN_ERR_ARGUMENT, "bad bar_nll_backward arguments");
+  BarArgs a; memset(&a, 0, sizeof(a));
+  a.logits = logits; a.ld = ld; a.R = R; a.nbars = nbars; a.lse = const_cast<float*>(lse); a.bucket = const_cast<int*>(bucket);
+  a.gout = gout; a.dlogits = dlogits;
+  PFN_TRY(launch_rows(bar_nll_bwd_kernel, a, 0, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_bar_mean(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support, float* mean, void* stream) {
+  if (R < 0 || nbars < 1 || (R > 0 && (!logits || !borders || !mean))) return fail(PFN_ERR_ARGUMENT, "bad bar_mean arguments");
+  BarArgs a; memset(&a, 0, sizeof(a));
+  a.logits = logits; a.ld = ld; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support; a.mean_out = mean;
+  PFN_TRY(launch_rows(bar_mean_kernel, a, 0, (hipStream_t)stream));
+  return PFN_OK;
+}
+// dlogits = gout p (c - mean): mean_out holds the forward's means (read only)
+int pfn_bar_mean_backward(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support, const float* mean, const float* gout,
+                          float* dlogits, void* stream) {
+  if (R < 0 || nbars < 1 || (R > 0 && (!logits || !borders || !mean || !gout || !dlogits))) return fail(PFN_ERR_ARGUMENT, "bad bar_mean_backward arguments");
+  BarArgs a; memset(&a, 0, sizeof(a));
+  a.logits = logits; a.ld = ld; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support;
+  a.mean_out = const_cast<float*>(mean); a.gout = gout; a.dlogits = dlogits;
+  PFN_TRY(launch_rows(bar_mean_bwd_kernel, a, 0, (hipStream_t)stream));
+  return PFN_OK;
+}
+
+int pfn_bar_stats(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                  const int32_t* kinds, int K, const float* args, int64_t arg_ld, float* out, void* stream) {
+  BarStatsArgs a;
+  PFN_TRY(bar_stats_common(a, "pfn_bar_stats", logits, ld, borders, R, nbars, full_support));
+  PFN_TRY(bar_stats_spec(a, "pfn_bar_stats", kinds, K, args, arg_ld));
+  if (!out) return fail(PFN_ERR_ARGUMENT, "pfn_bar_stats: null pointer");
+  a.out = out;
+  PFN_TRY(launch_rows(nbars <= BAR_LDS_MAX ? bar_stats_kernel<true> : bar_stats_kernel<false>, a, bar_lds_bytes(nbars), (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_bar_stats_backward(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                           const int32_t* kinds, int K, const float* args, int64_t arg_ld, const float* out, const float* gout,
+                           float* dlogits, void* stream) {
+  BarStatsArgs a;
+  PFN_TRY(bar_stats_common(a, "pfn_bar_stats_backward", logits, ld, borders, R, nbars, full_support));
+  PFN_TRY(bar_stats_spec(a, "pfn_bar_stats_backward", kinds, K, args, arg_ld));
+  if (!out || !gout || !dlogits) return fail(PFN_ERR_ARGUMENT, "pfn_bar_stats_backward: null pointer");
+  a.out = const_cast<float*>(out); a.gout = gout; a.dlogits = dlogits;
+  PFN_TRY(launch_rows(nbars <= BAR_LDS_MAX ? bar_stats_bwd_kernel<true> : bar_stats_bwd_kernel<false>, a, bar_lds_bytes(nbars), (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_bar_sample(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
+                   int n_samples, uint64_t seed, float* out, void* stream) {
+  BarStatsArgs a;
+  PFN_TRY(bar_stats_common(a, "pfn_bar_sample", logits, ld, borders, R, nbars, full_support));
+  if (n_samples < 0) return fail(PFN_ERR_ARGUMENT, "pfn_bar_sample: n_samples = %d", n_samples);
+  if (!out) return fail(PFN_ERR_ARGUMENT, "pfn_bar_sample: null pointer");
+  a.n_samples = n_samples; a.seed = seed; a.samples = out;
+  if (n_samples == 0) return PFN_OK;
+  PFN_TRY(launch_rows(nbars <= BAR_LDS_MAX ? bar_sample_kernel<true> : bar_sample_kernel<false>, a, bar_lds_bytes(nbars), (hipStream_t)stream));
+  return PFN_OK;
+}
+}  // extern "C"

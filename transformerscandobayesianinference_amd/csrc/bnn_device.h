@@ -8,12 +8,12 @@
 // SVI and SVGD, and the offsets of the NUTS and predict kernels), slots -> lane registers (bnn_lane: SVI, SVGD), the data-row loop over resident or chunked
 // rows (bnn_data_rows: all three gradient kernels, the NUTS kernel never resident) with its staging prologue (bnn_stage_all: SVI, SVGD) and the n_of clamp
 // (bnn_n_rows: all three), Adam's bias corrections and its update of one coordinate (bnn_ipow, bnn_adam_at, bnn_adam: SVI's loc and u, SVGD's particle
-// coordinate) and, on the host, bnn_dispatch (the H / F / activation dispatch of all three files).  SVI and SVGD launch through launch_lds
-// (pfn_kernels.h: the launch with more than 64 KB of LDS).
+// coordinate) and, on the host, bnn_dispatch (the H / F / activation dispatch of all three files) and the argument checks that more than one of their entry
+// points make (bnn_limits, bnn_batch, bnn_check, bnn_steps_check).  SVI and SVGD launch through launch_lds (pfn_host.h: the launch with more than 64 KB of LDS).
 #pragma once
 #include <type_traits>
 #include "pfn_device.h"
-#include "pfn_kernels.h"
+#include "pfn_host.h"
 
 namespace pfn {
 
@@ -204,5 +204,33 @@ template <class Fn> int bnn_dispatch(int H, int F, int activation, Fn&& fn) {
 }
 
 }  // namespace
+
+// ---- host: the argument checks the entry points of the three files share ----
+
+inline int bnn_limits(int F, int H, int activation) {      // what the kernels are built for; the checks come shapes first: nothing here touches a pointer or HIP
+  if (F < 1 || F > 16) return fail(PFN_ERR_UNSUPPORTED, "F %d outside 1 .. 16 (a lane keeps its row of W1 in registers)", F);
+  if (H < 1 || H > 64) return fail(PFN_ERR_UNSUPPORTED, "H %d outside 1 .. 64 (lane = hidden unit, one wave per chain at most)", H);
+  if (activation < 0 || activation > 1) return fail(PFN_ERR_UNSUPPORTED, "activation %d (0 identity, 1 tanh)", activation);
+  return PFN_OK;
+}
+inline int bnn_batch(int P, int K, int F, int H, int64_t ld) {      // K parameter vectors of D numbers, ld apart, for each of P problems
+  if (P < 1 || K < 1 || (int64_t)P * K > 0x7fffffff) return fail(PFN_ERR_ARGUMENT, "P %d x K %d chains: need P >= 1, K >= 1, P K < 2^31", P, K);
+  if (ld < (int64_t)H * (F + 3) + 2) return fail(PFN_ERR_ARGUMENT, "ld %lld < D = H (F + 3) + 2 = %d", (long long)ld, H * (F + 3) + 2);
+  return PFN_OK;
+}
+inline int bnn_check(int P, int K, int F, int H, int activation, int64_t ld) {
+  if (int rc = bnn_limits(F, H, activation)) return rc;
+  return bnn_batch(P, K, F, H, ld);
+}
+// what the two step loops (SVI, SVGD) ask of their common arguments, after the limits: the problem and step counts and the pointers, ld, Adam's numbers
+inline int bnn_steps_check(const char* fn, int P, int S, int F, int H, int64_t ld, int64_t step0, int num_steps, const void* x, const void* y, const void* state, float lr,
+                           float beta1, float beta2, float eps) {
+  if (P < 1 || S < 1 || step0 < 0 || num_steps < 0 || !x || !y || !state)
+    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (P %d >= 1, S %d >= 1, step0 %lld >= 0, num_steps %d >= 0, x, y, state not NULL)", fn, P, S, (long long)step0, num_steps);
+  if (int rc = bnn_batch(P, 1, F, H, ld)) return rc;      // ld >= D
+  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
+    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (lr %g >= 0, beta1 %g and beta2 %g in [0, 1), eps %g >= 0)", fn, lr, beta1, beta2, eps);
+  return PFN_OK;
+}
 
 }  // namespace pfn

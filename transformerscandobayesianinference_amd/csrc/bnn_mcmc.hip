@@ -13,6 +13,20 @@
 
 namespace pfn {
 
+struct BnnArgs {
+  const float* x;        // [P,S,F]
+  const float* y;        // [P,S]: class = y > 0.5
+  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [0,S]); null = S
+  const float* theta;    // [P*K, ld]: W1 [H,F], b1 [H], W2 [2,H], b2 [2]
+  long ld;
+  int P, K, S, F, H, activation;      // activation: 0 identity, 1 tanh
+  float* value;          // [P*K]
+  float* grad;           // [P*K, ld] or null; columns >= D are never written
+  const float* x_test;   // [P,m,F]   (predict)
+  int m;
+  float* prob1;          // [P*K, m]
+};
+
 namespace {
 
 struct BnnChain {
@@ -131,8 +145,27 @@ int bnn_launch(const BnnArgs& a, bool predict, hipStream_t s) {
 }
 
 }  // namespace
-
-int launch_bnn_logp_grad(const BnnArgs& a, hipStream_t s) { return bnn_launch(a, false, s); }
-int launch_bnn_predict(const BnnArgs& a, hipStream_t s) { return bnn_launch(a, true, s); }
-
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+int pfn_bnn_logp_grad(const float* x, const float* y, const int32_t* n_of, const float* theta, int64_t ld, int P, int K, int S, int F, int H, int activation,
+                      float* value, float* grad, void* stream) {
+  if (int rc = bnn_check(P, K, F, H, activation, ld)) return rc;
+  if (S < 1 || !x || !y || !theta || !value) return fail(PFN_ERR_ARGUMENT, "bad bnn_logp_grad arguments (S %d >= 1, x, y, theta, value not NULL)", S);
+  BnnArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.theta = theta; a.ld = ld; a.P = P; a.K = K; a.S = S; a.F = F; a.H = H; a.activation = activation; a.value = value; a.grad = grad;
+  PFN_TRY(bnn_launch(a, false, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_bnn_predict(const float* x_test, const float* theta, int64_t ld, int P, int K, int m, int F, int H, int activation, float* prob1, void* stream) {
+  if (int rc = bnn_check(P, K, F, H, activation, ld)) return rc;
+  if (m < 0 || !theta || (m > 0 && (!x_test || !prob1))) return fail(PFN_ERR_ARGUMENT, "bad bnn_predict arguments (m %d >= 0, x_test, theta, prob1 not NULL)", m);
+  if (m == 0) return PFN_OK;
+  BnnArgs a{};
+  a.theta = theta; a.ld = ld; a.P = P; a.K = K; a.F = F; a.H = H; a.activation = activation; a.x_test = x_test; a.m = m; a.prob1 = prob1;
+  PFN_TRY(bnn_launch(a, true, (hipStream_t)stream));
+  return PFN_OK;
+}
+}  // extern "C"

@@ -17,9 +17,28 @@
 #include <algorithm>
 #include <cmath>
 #include "bnn_device.h"
-#include "pfn_kernels.h"
 
 namespace pfn {
+
+struct BnnSvgdArgs {
+  const float* x;        // [P,S,F]
+  const float* y;        // [P,S]: class = y > 0.5
+  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [0,S]); null = S
+  float* state;          // [P,3,N,ld]: particles, m, v; columns >= D are never touched
+  long ld;
+  int P, S, F, H, activation, N;      // N particles per problem
+  long step0;
+  int num_steps;
+  float lr, beta1, beta2, eps, bandwidth_factor;
+  float* grads;          // [P,N,D] (the workspace) when the state is not resident in LDS, else unused
+  float* potential;      // [P,num_steps] or null
+  float* bandwidth;      // [P,ld] or null
+};
+// particles, gradients and both Adam moments ([4][N][D | 1] f32) stay in LDS for the whole launch when they fit this many bytes; otherwise the state stays in
+// the caller's buffer, the gradients go through the workspace and LDS holds a tile of 64 coordinate columns
+constexpr long BNN_SVGD_STATE_BUDGET = 66560;
+inline bool bnn_svgd_resident(int N, int D) { return 16L * N * (D | 1) <= BNN_SVGD_STATE_BUDGET; }
+inline int64_t bnn_svgd_workspace_bytes(int P, int N, int D) { return bnn_svgd_resident(N, D) ? 0 : (int64_t)P * N * D * 4; }
 
 namespace {
 
@@ -259,8 +278,6 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * SVGD_W
   }
 }
 
-}  // namespace
-
 int launch_bnn_svgd_steps(const BnnSvgdArgs& a, hipStream_t s) {
   return bnn_dispatch(a.H, a.F, a.activation, [&](auto hp, auto fp, auto act) {
     constexpr int HP = decltype(hp)::value, FP = decltype(fp)::value, ACT = decltype(act)::value;
@@ -278,4 +295,39 @@ int launch_bnn_svgd_steps(const BnnSvgdArgs& a, hipStream_t s) {
   });
 }
 
+int bnn_svgd_limits(int F, int H, int activation, int N) {      // what the kernel is built for: nothing here touches a pointer or HIP
+  if (int rc = bnn_limits(F, H, activation)) return rc;
+  if (N < 2 || N > PFN_BNN_SVGD_MAX_PARTICLES)
+    return fail(PFN_ERR_UNSUPPORTED, "num_particles %d outside 2 .. %d (lane = particle in the Stein step; the median needs a pair)", N, PFN_BNN_SVGD_MAX_PARTICLES);
+  return PFN_OK;
+}
+
+}  // namespace
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+int64_t pfn_bnn_svgd_workspace_bytes(int P, int num_particles, int F, int H) {
+  if (P < 1 || bnn_svgd_limits(F, H, 0, num_particles)) return -1;
+  return bnn_svgd_workspace_bytes(P, num_particles, H * (F + 3) + 2);
+}
+int pfn_bnn_svgd_steps(const float* x, const float* y, const int32_t* n_of, float* state, int64_t ld, int P, int S, int F, int H, int activation, int num_particles,
+                       int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, float bandwidth_factor, void* workspace,
+                       int64_t workspace_bytes, float* potential, float* bandwidth, void* stream) {
+  if (int rc = bnn_svgd_limits(F, H, activation, num_particles)) return rc;
+  if (int rc = bnn_steps_check("bnn_svgd_steps", P, S, F, H, ld, step0, num_steps, x, y, state, lr, beta1, beta2, eps)) return rc;
+  if (!(lr <= 3.4e38f) || !(bandwidth_factor > 0.f)) return fail(PFN_ERR_ARGUMENT, "bad bnn_svgd_steps arguments (lr %g finite, bandwidth_factor %g > 0)", lr, bandwidth_factor);
+  const int D = H * (F + 3) + 2;
+  const int64_t need = bnn_svgd_workspace_bytes(P, num_particles, D);
+  if (workspace_bytes < need || (need > 0 && !workspace))
+    return fail(PFN_ERR_ARGUMENT, "workspace_bytes %lld < pfn_bnn_svgd_workspace_bytes = %lld (or a NULL workspace)", (long long)workspace_bytes, (long long)need);
+  if (num_steps == 0) return PFN_OK;
+  BnnSvgdArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.state = state; a.ld = ld; a.P = P; a.S = S; a.F = F; a.H = H; a.activation = activation; a.N = num_particles; a.step0 = step0;
+  a.num_steps = num_steps; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.bandwidth_factor = bandwidth_factor;
+  a.grads = need > 0 ? (float*)workspace : nullptr; a.potential = potential; a.bandwidth = bandwidth;
+  PFN_TRY(launch_bnn_svgd_steps(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+}  // extern "C"

@@ -12,9 +12,23 @@
 // updated by thread i mod blockDim, which adds the waves' rows in wave order and takes the Adam step.  The order of every sum depends on (H, F, K) only.
 #include <algorithm>
 #include "bnn_device.h"
-#include "pfn_kernels.h"
 
 namespace pfn {
+
+struct BnnSviArgs {
+  const float* x;        // [P,S,F]
+  const float* y;        // [P,S]: class = y > 0.5
+  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [0,S]); null = S
+  float* state;          // [P,6,ld]: loc, u (scale = softplus(u)), m_loc, v_loc, m_u, v_u; columns >= D are never touched
+  long ld;
+  int P, S, F, H, activation, K;      // K particles per step
+  long step0;
+  int num_steps;
+  float lr, beta1, beta2, eps;
+  unsigned long long seed;
+  const int64_t* problem_ids;   // [P] or null (the problem's index): the Philox stream
+  float* loss;           // [P,num_steps] or null
+};
 
 namespace {
 
@@ -156,8 +170,6 @@ template <int HP, int FP, int ACT> __global__ void __launch_bounds__(64 * BNN_MA
   }
 }
 
-}  // namespace
-
 int launch_bnn_svi_steps(const BnnSviArgs& a, hipStream_t s) {
   return bnn_dispatch(a.H, a.F, a.activation, [&](auto hp, auto fp, auto act) {
     constexpr int HP = decltype(hp)::value, FP = decltype(fp)::value, ACT = decltype(act)::value, CPW = 64 / HP;
@@ -173,4 +185,23 @@ int launch_bnn_svi_steps(const BnnSviArgs& a, hipStream_t s) {
   });
 }
 
+}  // namespace
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" int pfn_bnn_svi_steps(const float* x, const float* y, const int32_t* n_of, float* state, int64_t ld, int P, int S, int F, int H, int activation,
+                                 int num_particles, int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, uint64_t seed,
+                                 const int64_t* problem_ids, float* loss, void* stream) {
+  if (int rc = bnn_limits(F, H, activation)) return rc;
+  if (int rc = bnn_steps_check("bnn_svi_steps", P, S, F, H, ld, step0, num_steps, x, y, state, lr, beta1, beta2, eps)) return rc;
+  if (num_particles < 1) return fail(PFN_ERR_ARGUMENT, "bad bnn_svi_steps arguments (num_particles %d >= 1)", num_particles);
+  if (step0 > (int64_t)1 << 40 || (step0 + num_steps + 1) * (int64_t)num_particles >= (int64_t)1 << 53)
+    return fail(PFN_ERR_ARGUMENT, "step0 %lld must not exceed 2^40 and (step0 + num_steps + 1) num_particles must stay below 2^53 (the Philox counter of a particle's noise)", (long long)step0);
+  if (num_steps == 0) return PFN_OK;
+  BnnSviArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.state = state; a.ld = ld; a.P = P; a.S = S; a.F = F; a.H = H; a.activation = activation; a.K = num_particles; a.step0 = step0;
+  a.num_steps = num_steps; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.seed = seed; a.problem_ids = problem_ids; a.loss = loss;
+  PFN_TRY(launch_bnn_svi_steps(a, (hipStream_t)stream));
+  return PFN_OK;
+}

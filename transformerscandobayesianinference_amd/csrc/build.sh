@@ -5,10 +5,25 @@ cd "$(dirname "$0")"
 OUT=../libpfn_hip.so
 SRCS="pfn_api.hip gemm.hip gemm_tn.hip attention.hip rowwise.hip bar.hip optim.hip gp_prior.hip gp_fit.hip gp_mcmc.hip bnn_mcmc.hip bnn_svi.hip bnn_svgd.hip tabular.hip logistic.hip gpc.hip mlp_prior.hip stroke_prior.hip"
 mkdir -p ../_build
+# the headers a source is rebuilt for: the ones every file may include, and those of its own family
+headers_of() {
+  echo pfn_host.h pfn_device.h ../../include/pfn_hip.h
+  case "$1" in
+    pfn_api.hip) echo pfn_kernels.h gp_prior.h ;;
+    gemm.hip|gemm_tn.hip|attention.hip|rowwise.hip) echo pfn_kernels.h ;;
+    gp_prior.hip|gp_fit.hip) echo gp_prior.h ;;
+    bnn_*.hip) echo bnn_device.h ;;
+    tabular.hip|logistic.hip|gpc.hip) echo fold_device.h ;;
+  esac
+}
 pids=()
 for f in $SRCS; do
   o=../_build/${f%.hip}.o
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ pfn_device.h -nt "$o" ] || [ pfn_kernels.h -nt "$o" ] || [ bnn_device.h -nt "$o" ] || [ fold_device.h -nt "$o" ] || [ ../../include/pfn_hip.h -nt "$o" ]; then
+  stale=""
+  for d in "$f" $(headers_of "$f"); do
+    if [ ! -f "$o" ] || [ "$d" -nt "$o" ]; then stale=1; fi
+  done
+  if [ -n "$stale" ]; then
     extra=""
     # attention.hip: no SLP packing -- v_pk_add/mul_f32 beside MFMAs issue slower than the scalar ops they replace
     [ "$f" = attention.hip ] && extra="-fno-slp-vectorize"

@@ -21,9 +21,27 @@
 // No atomics anywhere: problem p's outputs are a function of (x_p, y_p, n_p, theta_p) alone.
 #include <algorithm>
 #include "pfn_device.h"
-#include "pfn_kernels.h"
+#include "gp_prior.h"
 
 namespace pfn {
+
+struct GpFitArgs {
+  const float* x;        // [P,S,nf]
+  const float* y;        // [P,S]
+  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [1,S]); null = S
+  const float* theta;    // [P,nf+3]: log lengthscale_d, log outputscale, log(noise - floor), constant mean
+  const float* prior;    // [8]: a_l, b_l, a_o, b_o, a_n, b_n, noise_floor, 0
+  int P, S, nf, kernel, flags;
+  void* ws;              // gp_fit_workspace_bytes(P, S)
+  float* value;          // [P]
+  float* grad;           // [P,nf+3] or null
+  const float* x_test;   // [P,m,nf]   (predict)
+  int m;
+  float* mean;           // [P,m]
+  float* var;            // [P,m]
+  int32_t* info;         // [P]
+};
+
 namespace {
 
 constexpr int FT = 64;        // tile / panel width
@@ -482,8 +500,6 @@ int fit_factor(const GpFitArgs& a, const FitWs& w, hipStream_t s) {
   return launch_gp_factor(g, s);
 }
 
-}  // namespace
-
 int64_t gp_fit_workspace_bytes(int P, int S) {
   FitWs w;
   return carve(w, nullptr, P, S);
@@ -520,4 +536,44 @@ int launch_gp_fit_predict(const GpFitArgs& a, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 
+int gp_fit_check(const float* x, const float* y, const float* theta, const float* prior, int P, int S, int nf, int kernel, void* ws, int64_t ws_bytes, int32_t* info) {
+  if (!x || !y || !theta || !prior || !ws || !info || P < 1 || S < 1 || nf < 1) return fail(PFN_ERR_ARGUMENT, "bad gp_fit arguments");
+  if (P > 65535) return fail(PFN_ERR_UNSUPPORTED, "P %d > 65535 problems per call", P);
+  if (S % 4) return fail(PFN_ERR_UNSUPPORTED, "S %d is not a multiple of 4", S);
+  if (nf > 126) return fail(PFN_ERR_UNSUPPORTED, "nf %d > 126 (the tiles stage 128 rows of x in 64 KB of LDS)", nf);
+  if (kernel < 0 || kernel > 3) return fail(PFN_ERR_UNSUPPORTED, "kernel %d (0 = RBF, 1 / 2 / 3 = Matern nu 5/2, 3/2, 1/2)", kernel);
+  if (ws_bytes < gp_fit_workspace_bytes(P, S)) return fail(PFN_ERR_ARGUMENT, "ws_bytes %lld < pfn_gp_fit_workspace_bytes = %lld", (long long)ws_bytes, (long long)gp_fit_workspace_bytes(P, S));
+  return PFN_OK;
+}
+
+}  // namespace
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+int64_t pfn_gp_fit_workspace_bytes(int P, int S) {
+  if (P < 1 || S < 1) return -1;
+  return gp_fit_workspace_bytes(P, S);
+}
+int pfn_gp_mll_grad(const float* x, const float* y, const int32_t* n_of, const float* theta, const float* prior, int P, int S, int nf, int kernel, int flags,
+                    void* ws, int64_t ws_bytes, float* value, float* grad, int32_t* info, void* stream) {
+  if (int rc = gp_fit_check(x, y, theta, prior, P, S, nf, kernel, ws, ws_bytes, info)) return rc;
+  if (!value) return fail(PFN_ERR_ARGUMENT, "bad gp_mll_grad arguments");
+  GpFitArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.theta = theta; a.prior = prior; a.P = P; a.S = S; a.nf = nf; a.kernel = kernel; a.flags = flags;
+  a.ws = ws; a.value = value; a.grad = grad; a.info = info;
+  PFN_TRY(launch_gp_mll_grad(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_gp_fit_predict(const float* x, const float* y, const int32_t* n_of, const float* theta, const float* prior, int P, int S, int nf, int kernel,
+                       const float* x_test, int m, void* ws, int64_t ws_bytes, float* mean, float* var, int32_t* info, void* stream) {
+  if (int rc = gp_fit_check(x, y, theta, prior, P, S, nf, kernel, ws, ws_bytes, info)) return rc;
+  if (m < 0 || (m > 0 && (!x_test || !mean || !var))) return fail(PFN_ERR_ARGUMENT, "bad gp_fit_predict arguments");
+  GpFitArgs a{};
+  a.x = x; a.y = y; a.n_of = n_of; a.theta = theta; a.prior = prior; a.P = P; a.S = S; a.nf = nf; a.kernel = kernel; a.flags = 0;
+  a.ws = ws; a.x_test = x_test; a.m = m; a.mean = mean; a.var = var; a.info = info;
+  PFN_TRY(launch_gp_fit_predict(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+}  // extern "C"

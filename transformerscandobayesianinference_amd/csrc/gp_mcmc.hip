@@ -7,7 +7,7 @@
 // the same launch; reductions are wave shuffles, every decision goes through readfirstlane, the only atomic is the counter of finished chains.  The tree's
 // checkpoint momenta (one row per set bit of the leaf index: max_tree_depth rows) are workspace rows selected by a wave-uniform index -- no per-thread arrays.
 #include "pfn_device.h"
-#include "pfn_kernels.h"
+#include "pfn_host.h"
 
 namespace pfn {
 namespace {
@@ -326,28 +326,65 @@ __global__ __launch_bounds__(256) void nuts_advance_kernel(NutsAdvanceArgs a) {
   }
 }
 
-}  // namespace
-
 int64_t nuts_workspace_bytes(int C, int D, int depth) {
   return (int64_t)sizeof(NutsHeader) + nuts_inv_mass_bytes(C, D) + sizeof(NutsScalars) * (int64_t)C + sizeof(float) * nuts_vec_count(depth) * C * D;
 }
 
-int launch_nuts_init(const NutsInit& i, hipStream_t s) {
-  NutsInitArgs a{};
-  a.ws = i.ws; a.C = i.C; a.D = i.D; a.depth = i.depth; a.ld = i.ld; a.W = i.W; a.N = i.N; a.flags = i.flags; a.n_windows = i.n_windows; a.window_start = i.window_start;
-  for (int k = 0; k < PFN_NUTS_MAX_WINDOWS; ++k) a.window_ends[k] = k < i.n_windows ? i.window_ends[k] : 0;
-  a.step_size = i.step_size; a.target = i.target; a.seed = i.seed; a.chain_ids = (const long long*)i.chain_ids; a.theta0 = i.theta0; a.inv_mass0 = i.inv_mass0;
-  a.trial = i.trial; a.done_count = i.done_count;
-  nuts_init_kernel<<<dim3((i.C + NUTS_WAVES - 1) / NUTS_WAVES), dim3(64 * NUTS_WAVES), 0, s>>>(a);
+int launch_nuts_init(const NutsInitArgs& a, hipStream_t s) {
+  nuts_init_kernel<<<dim3((a.C + NUTS_WAVES - 1) / NUTS_WAVES), dim3(64 * NUTS_WAVES), 0, s>>>(a);
   return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 
-int launch_nuts_advance(const NutsAdvance& v, hipStream_t s) {
-  NutsAdvanceArgs a{};
-  a.ws = v.ws; a.C = v.C; a.D = v.D; a.depth = v.depth; a.W = v.W; a.N = v.N; a.ld = v.ld; a.value = v.value; a.grad = v.grad; a.info = v.info; a.scale = v.scale; a.shift = v.shift;
-  a.trial = v.trial; a.samples = v.samples; a.stats = v.stats; a.warm = v.warm; a.done_count = v.done_count;
-  nuts_advance_kernel<<<dim3((v.C + NUTS_WAVES - 1) / NUTS_WAVES), dim3(64 * NUTS_WAVES), 0, s>>>(a);
+int launch_nuts_advance(const NutsAdvanceArgs& a, hipStream_t s) {
+  nuts_advance_kernel<<<dim3((a.C + NUTS_WAVES - 1) / NUTS_WAVES), dim3(64 * NUTS_WAVES), 0, s>>>(a);
   return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 
+int nuts_check(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int depth) {
+  if (C < 1 || D < 1 || D > 128 || depth < 1 || depth > 10 || ld < D || !ws) return fail(PFN_ERR_ARGUMENT, "bad nuts arguments (C %d, D %d in 1..128, ld %lld >= D, max_tree_depth %d in 1..10)", C, D, (long long)ld, depth);
+  if (ws_bytes < nuts_workspace_bytes(C, D, depth)) return fail(PFN_ERR_ARGUMENT, "ws_bytes %lld < pfn_nuts_workspace_bytes = %lld", (long long)ws_bytes, (long long)nuts_workspace_bytes(C, D, depth));
+  return PFN_OK;
+}
+
+}  // namespace
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+int64_t pfn_nuts_workspace_bytes(int C, int D, int max_tree_depth) {
+  if (C < 1 || D < 1 || D > 128 || max_tree_depth < 1 || max_tree_depth > 10) return -1;
+  return nuts_workspace_bytes(C, D, max_tree_depth);
+}
+// window_ends: a HOST array [n_windows]; chain_ids [C] or null (the chain's index); inv_mass0 [C, D] or null (ones)
+int pfn_nuts_init(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int max_tree_depth, int num_warmup, int num_samples, int flags, const int32_t* window_ends,
+                  int n_windows, int window_start, float step_size, float target_accept, uint64_t seed, const int64_t* chain_ids, const float* theta0,
+                  const float* inv_mass0, float* trial, int32_t* done_count, void* stream) {
+  if (int rc = nuts_check(ws, ws_bytes, C, D, ld, max_tree_depth)) return rc;
+  if (!theta0 || !trial || !done_count || num_warmup < 0 || num_samples < 1 || !(step_size > 0.f) || !(target_accept > 0.f && target_accept < 1.f))
+    return fail(PFN_ERR_ARGUMENT, "bad nuts_init arguments");
+  if (flags & ~(PFN_NUTS_ADAPT_MASS | PFN_NUTS_KEEP_WARMUP)) return fail(PFN_ERR_ARGUMENT, "unknown nuts flags 0x%x", flags);
+  if (n_windows < 0 || n_windows > PFN_NUTS_MAX_WINDOWS || (n_windows > 0 && !window_ends) || window_start < 0) return fail(PFN_ERR_ARGUMENT, "bad adaptation windows");
+  for (int i = 0; i < n_windows; ++i)
+    if (window_ends[i] <= (i ? window_ends[i - 1] : window_start) || window_ends[i] >= num_warmup)
+      return fail(PFN_ERR_ARGUMENT, "adaptation window ends must increase and lie below num_warmup (dual averaging restarts at a window end and needs transitions after it)");
+  NutsInitArgs a{};
+  a.ws = ws; a.C = C; a.D = D; a.depth = max_tree_depth; a.ld = ld; a.W = num_warmup; a.N = num_samples; a.flags = flags; a.n_windows = n_windows;
+  a.window_start = window_start;
+  for (int k = 0; k < n_windows; ++k) a.window_ends[k] = window_ends[k];
+  a.step_size = step_size; a.target = target_accept; a.seed = seed; a.chain_ids = (const long long*)chain_ids; a.theta0 = theta0; a.inv_mass0 = inv_mass0;
+  a.trial = trial; a.done_count = done_count;
+  PFN_TRY(launch_nuts_init(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_nuts_advance(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int max_tree_depth, int num_warmup, int num_samples, const float* value, const float* grad,
+                     const int32_t* info, const float* scale, const float* shift, float* trial, float* samples, float* stats, float* warm, int32_t* done_count, void* stream) {
+  if (int rc = nuts_check(ws, ws_bytes, C, D, ld, max_tree_depth)) return rc;
+  if (!value || !grad || !trial || !samples || !stats || !done_count || num_warmup < 0 || num_samples < 1) return fail(PFN_ERR_ARGUMENT, "bad nuts_advance arguments");
+  NutsAdvanceArgs a{};
+  a.ws = ws; a.C = C; a.D = D; a.depth = max_tree_depth; a.W = num_warmup; a.N = num_samples; a.ld = ld; a.value = value; a.grad = grad; a.info = info; a.scale = scale; a.shift = shift;
+  a.trial = trial; a.samples = samples; a.stats = stats; a.warm = warm; a.done_count = done_count;
+  PFN_TRY(launch_nuts_advance(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+}  // extern "C"

@@ -21,7 +21,7 @@
 // S^3/3 flop (Cholesky) + S^2 (nf+2) (Gram); the matrix (4 S^2 bytes) lives in K_ws.
 #include <algorithm>
 #include "pfn_device.h"
-#include "pfn_kernels.h"
+#include "gp_prior.h"
 
 namespace pfn {
 
@@ -835,7 +835,7 @@ void gp_attach_planes(GpArgs& a) {      // a.K = the caller's K_ws of gp_workspa
   a.planes = a.plane_rows > 0 ? reinterpret_cast<char*>(a.K) + gp_k_bytes(a.B, a.S) : nullptr;
 }
 
-int launch_gp_sample(const GpArgs& a, hipStream_t s) {
+static int launch_gp_sample(const GpArgs& a, hipStream_t s) {
   const int S = a.S, B = a.B;
   if (S % 4) return PFN_ERR_UNSUPPORTED;  // 16-byte aligned matrix rows
   if (!a.w) {
@@ -917,7 +917,9 @@ __global__ __launch_bounds__(256) void gp_posterior_kernel(GpArgs a, const float
   }
 }
 
-int launch_gp_posterior(const GpArgs& a, const float* y_data, float* nll, float* mean, float* var, hipStream_t s) {
+// Sequential exact-GP predictions from ONE factorisation: for every t, the posterior at x_t given points 0..t-1.
+//   mean[b,t], var[b,t] (with observation noise), nll[b,t] = -log N(y_t; mean, var)
+static int launch_gp_posterior(const GpArgs& a, const float* y_data, float* nll, float* mean, float* var, hipStream_t s) {
   if (!a.w || !a.y || !y_data) return PFN_ERR_ARGUMENT;
   if (hipMemcpyAsync(a.y, y_data, sizeof(float) * a.B * a.S, hipMemcpyDeviceToDevice, s) != hipSuccess) return PFN_ERR_LAUNCH;
   const int rc = launch_gp_sample(a, s);
@@ -927,4 +929,53 @@ int launch_gp_posterior(const GpArgs& a, const float* y_data, float* nll, float*
   return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 
+// PFN_TUNE_GP_PLANES (test / profiling knob): 1 (default) = the rank-256 trailing update of the blocked Cholesky multiplies the pre-split fp16 planes the wide
+// triangular solve leaves behind K (gp_syrk_planes_kernel: two terms on a power-of-two scale, three products); 0 = it re-reads the f32 panel per tile and splits it
+// into three bf16 terms, six products (gp_syrk_kernel, rounds 2-3).  Both are f32-accurate (tools/sim_gp_split.py, tools/exp_gp_accuracy.py).
+static bool g_gp_planes = true;
+void set_gp_planes(int on) { g_gp_planes = on != 0; }
+static int gp_check_workspace(GpArgs& a, int64_t K_ws_bytes) {      // ABI 7: the planes only when the caller's allocation holds them
+  a.planes = nullptr; a.plane_rows = 0;
+  if (K_ws_bytes < (int64_t)a.B * a.S * a.S * 4) return fail(PFN_ERR_ARGUMENT, "K_ws_bytes %lld < B*S*S*4 = %lld", (long long)K_ws_bytes, (long long)a.B * a.S * a.S * 4);
+  if (g_gp_planes && K_ws_bytes >= gp_workspace_bytes(a.B, a.S)) gp_attach_planes(a);
+  return PFN_OK;
+}
+
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+int64_t pfn_gp_workspace_bytes(int B, int S) {
+  if (B < 1 || S < 1) return -1;
+  return gp_workspace_bytes(B, S);
+}
+int pfn_gp_prior_sample(float* x, float* z, float* y, float* K_ws, int64_t K_ws_bytes, const float* lengthscale, const float* outputscale,
+                        const float* noise, int B, int S, int nf, int kernel, int gen_x, int gen_z, uint64_t seed, uint64_t offset,
+                        int32_t* info, void* stream) {
+  if (!x || !z || !y || !K_ws || !lengthscale || !outputscale || !noise || !info || B < 1 || S < 1 || nf < 1) return fail(PFN_ERR_ARGUMENT, "bad gp_prior_sample arguments");
+  if (kernel < 0 || kernel > 3) return fail(PFN_ERR_UNSUPPORTED, "kernel %d (0 = RBF, 1 / 2 / 3 = Matern nu 5/2, 3/2, 1/2)", kernel);
+  GpArgs a;
+  a.x = x; a.z = z; a.y = y; a.K = K_ws; a.lengthscale = lengthscale; a.outputscale = outputscale; a.noise = noise;
+  a.B = B; a.S = S; a.nf = nf; a.kernel = kernel; a.seed = seed; a.offset = offset; a.gen_x = gen_x; a.gen_z = gen_z; a.info = info;
+  a.w = nullptr;
+  if (int rc = gp_check_workspace(a, K_ws_bytes)) return rc;
+  PFN_TRY(launch_gp_sample(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+
+int pfn_gp_posterior(const float* x, const float* y, float* K_ws, int64_t K_ws_bytes, float* resid_ws, float* w_ws, const float* lengthscale,
+                     const float* outputscale, const float* noise, int B, int S, int nf, int kernel, float* nll, float* mean,
+                     float* var, int32_t* info, void* stream) {
+  if (!x || !y || !K_ws || !resid_ws || !w_ws || !lengthscale || !outputscale || !noise || !info || B < 1 || S < 1 || nf < 1)
+    return fail(PFN_ERR_ARGUMENT, "bad gp_posterior arguments");
+  if (kernel < 0 || kernel > 3) return fail(PFN_ERR_UNSUPPORTED, "kernel %d (0 = RBF, 1 / 2 / 3 = Matern nu 5/2, 3/2, 1/2)", kernel);
+  GpArgs a;
+  a.x = const_cast<float*>(x); a.z = nullptr; a.y = resid_ws; a.K = K_ws; a.lengthscale = lengthscale; a.outputscale = outputscale;
+  a.noise = noise; a.B = B; a.S = S; a.nf = nf; a.kernel = kernel; a.seed = 0; a.offset = 0; a.gen_x = 0; a.gen_z = 0; a.info = info;
+  a.w = w_ws;
+  if (int rc = gp_check_workspace(a, K_ws_bytes)) return rc;
+  PFN_TRY(launch_gp_posterior(a, y, nll, mean, var, (hipStream_t)stream));
+  return PFN_OK;
+}
+}  // extern "C"

@@ -14,6 +14,24 @@
 
 namespace pfn {
 
+struct GpcArgs {
+  const float* theta;        // [P,NC,6,2] = (log c, log l) of every fit
+  const float* train;        // [P,n,F]
+  const float* labels;       // [P,n]: class = label > 0.5
+  const float* test;         // [P,T,F] (predict)
+  const int32_t* fold;       // [P,n]: the CV test fold of each train row
+  int P, n, T, F, NC, n_splits;
+  float* value;              // [P,NC,6] = -Z (lml_grad)
+  float* grad;               // [P,NC,6,2] = -dZ/dtheta (lml_grad)
+  int32_t* status;           // [P,NC,6,2] = (exit reason, Newton iterations)
+  float* cv_f;               // [P,NC,n,2] (predict): (m, e) of every held-out row
+  float* test_f;             // [P,NC,T,2] (predict)
+  float* test_var;           // [P,NC,T] (predict)
+};
+// K, the exponent arguments and the factor (inverted in place for the gradient) at the odd stride n | 1, sixteen vectors over the rows, eight words of reduction space:
+// 159,072 bytes at n = 112, 82,912 at the study's n = 80
+inline size_t gpc_lds_bytes(int n) { return ((size_t)3 * n * (n | 1) + 16 * (size_t)n + 8) * 4; }
+
 namespace {
 
 #define GPC_DEV __device__ __forceinline__
@@ -338,8 +356,6 @@ __global__ void __launch_bounds__(GPC_THREADS) gpc_predict_kernel(GpcArgs a) {
   }
 }
 
-}  // namespace
-
 int launch_gpc_lml_grad(const GpcArgs& a, hipStream_t s) {
   static LdsAllowance allowance;
   return launch_lds(gpc_lml_grad_kernel, allowance, dim3(PFN_GPC_SLOTS, (unsigned)a.NC, (unsigned)a.P), dim3(GPC_THREADS), gpc_lds_bytes(a.n), s, a);
@@ -350,4 +366,32 @@ int launch_gpc_predict(const GpcArgs& a, hipStream_t s) {
   return launch_lds(gpc_predict_kernel, allowance, dim3(PFN_GPC_SLOTS, (unsigned)a.NC, (unsigned)a.P), dim3(GPC_THREADS), gpc_lds_bytes(a.n), s, a);
 }
 
+int gpc_shapes(const char* what, int P, int n, int T, int F, int NC, int n_splits, bool pointers) {
+  return fold_shapes(what, "one block per fit, three n x n matrices in LDS", P, n, PFN_GPC_MAX_N, T, F, NC, PFN_GPC_MAX_CANDIDATES, n_splits, PFN_GPC_FOLDS, pointers);
+}
+
+}  // namespace
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+int pfn_gpc_lml_grad(const float* theta, const float* train, const float* labels, const int32_t* fold, int P, int n, int F, int NC, int n_splits, float* value,
+                     float* grad, int32_t* status, void* stream) {
+  if (const int rc = gpc_shapes("gpc_lml_grad", P, n, 1, F, NC, n_splits, theta && train && labels && fold && value && grad && status)) return rc;
+  GpcArgs a{};
+  a.theta = theta; a.train = train; a.labels = labels; a.fold = fold; a.P = P; a.n = n; a.T = 1; a.F = F; a.NC = NC; a.n_splits = n_splits; a.value = value; a.grad = grad;
+  a.status = status;
+  PFN_TRY(launch_gpc_lml_grad(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_gpc_predict(const float* theta, const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F, int NC, int n_splits,
+                    float* cv_f, float* test_f, float* test_var, int32_t* status, void* stream) {
+  if (const int rc = gpc_shapes("gpc_predict", P, n, T, F, NC, n_splits, theta && train && labels && test && fold && cv_f && test_f && test_var && status)) return rc;
+  GpcArgs a{};
+  a.theta = theta; a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.P = P; a.n = n; a.T = T; a.F = F; a.NC = NC; a.n_splits = n_splits; a.cv_f = cv_f;
+  a.test_f = test_f; a.test_var = test_var; a.status = status;
+  PFN_TRY(launch_gpc_predict(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+}  // extern "C"

@@ -10,6 +10,23 @@
 
 namespace pfn {
 
+struct LogitCvArgs {
+  const float* train;        // [P,n,F]
+  const float* labels;       // [P,n]: class = label > 0.5
+  const float* test;         // [P,T,F]
+  const int32_t* fold;       // [P,n]: the CV test fold of each train row
+  const float* cand_C;       // [NC]
+  const int32_t* cand_kind;  // [NC]: penalty code | PFN_LOGIT_FIT_INTERCEPT
+  int P, n, T, F, NC, n_splits;
+  int32_t* cv_correct;       // [P,NC,5]
+  float* test_z;             // [P,NC,T]
+  int32_t* status;           // [P,NC,6,2] = (exit reason, iterations)
+  float* coef;               // [P,NC,6,F+1] or null
+};
+// the n rows at an odd stride of (F + 1) | 1 floats (features, then a column of ones), H [F+1] rows at the same stride, six vectors over the rows, five over
+// the coordinates, eight words of reduction space: 138,296 bytes at n = F = 128, 37,576 at the study's n = 80, F = 60
+inline size_t logit_cv_lds_bytes(int n, int F) { return ((size_t)(n + F + 1) * ((F + 1) | 1) + 6 * (size_t)n + 5 * (size_t)(F + 1) + 8) * 4; }
+
 namespace {
 
 #define LOGIT_DEV __device__ __forceinline__
@@ -331,11 +348,23 @@ __global__ void __launch_bounds__(LOGIT_THREADS) logit_cv_kernel(LogitCvArgs a) 
   }
 }
 
-}  // namespace
-
 int launch_logit_cv(const LogitCvArgs& a, hipStream_t s) {
   static LdsAllowance allowance;
   return launch_lds(logit_cv_kernel, allowance, dim3(PFN_LOGIT_SLOTS, (unsigned)a.NC, (unsigned)a.P), dim3(LOGIT_THREADS), logit_cv_lds_bytes(a.n, a.F), s, a);
 }
 
+}  // namespace
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" int pfn_logistic_cv(const float* train, const float* labels, const float* test, const int32_t* fold, const float* cand_C, const int32_t* cand_kind, int P,
+                               int n, int T, int F, int NC, int n_splits, int32_t* cv_correct, float* test_z, int32_t* status, float* coef, void* stream) {
+  if (const int rc = fold_shapes("logistic_cv", "one block per fit, its rows and its Hessian in LDS", P, n, 128, T, F, NC, PFN_LOGIT_MAX_CANDIDATES, n_splits, PFN_LOGIT_FOLDS,
+                                 train && labels && test && fold && cand_C && cand_kind && cv_correct && test_z && status)) return rc;      // (coef may be NULL)
+  LogitCvArgs a{};
+  a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.cand_C = cand_C; a.cand_kind = cand_kind; a.P = P; a.n = n; a.T = T; a.F = F; a.NC = NC;
+  a.n_splits = n_splits; a.cv_correct = cv_correct; a.test_z = test_z; a.status = status; a.coef = coef;
+  PFN_TRY(launch_logit_cv(a, (hipStream_t)stream));
+  return PFN_OK;
+}

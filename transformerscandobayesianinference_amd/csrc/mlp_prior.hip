@@ -10,9 +10,23 @@
 // tile, so a k step is two 16-byte LDS reads for 16 FMAs.  Noise and (optionally) the causes come from the
 // counter-based generator; both can be injected for the parity tests.  f32 throughout, like the reference.
 #include "pfn_device.h"
-#include "pfn_kernels.h"
+#include "pfn_host.h"
 
 namespace pfn {
+
+struct MlpPriorArgs {
+  const float* weights;   // [num_models][Lmax][HP][HP]: layer l transposed ([in][out]), zero padded
+  const float* biases;    // [num_models][Lmax][HP], zero padded
+  const int* model_of;    // [B] model index of each dataset
+  const int* dims;        // [num_models][3] = (num_causes, hidden, num_layers)
+  const float* noise_std; // [num_models]
+  float* causes;          // [B][T][HP]: N(0,1) in the first num_causes columns, written when gen_causes != 0, else input
+  const float* noise;     // optional [B][Lmax-1][T][HP] injected standard normals (else generated)
+  float* y;               // [B][T] last layer, column 0
+  float* hidden;          // optional [B][Lmax-1][T][HP]: the outputs (noise included) of layers 1 .. L-1, the node pool of the causal variant
+  int B, T, HP, Lmax, activation, gen_causes;
+  unsigned long long seed, offset;
+};
 
 constexpr int MLP_TR = 32;   // rows per workgroup
 
@@ -119,7 +133,7 @@ __global__ __launch_bounds__(256) void mlp_prior_kernel(MlpPriorArgs a) {
   if (threadIdx.x < MLP_TR && t0 + threadIdx.x < a.T) a.y[(long)b * a.T + t0 + threadIdx.x] = ain[threadIdx.x];   // column 0 of the last layer
 }
 
-int launch_mlp_prior(const MlpPriorArgs& a, hipStream_t s) {
+static int launch_mlp_prior(const MlpPriorArgs& a, hipStream_t s) {
   if (a.B < 1 || a.T < 1 || a.HP < 4 || a.HP % 4 || a.Lmax < 1) return PFN_ERR_ARGUMENT;
   const size_t lds = ((size_t)a.HP * a.HP + 2 * (size_t)a.HP * MLP_TR) * sizeof(float);
   if (lds > 160 * 1024) return PFN_ERR_UNSUPPORTED;
@@ -130,3 +144,17 @@ int launch_mlp_prior(const MlpPriorArgs& a, hipStream_t s) {
 }
 
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
+                                     float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
+                                     uint64_t seed, uint64_t offset, void* stream) {
+  if (!weights || !biases || !model_of || !dims || !noise_std || !causes || !y) return fail(PFN_ERR_ARGUMENT, "bad mlp_prior_forward arguments");
+  if (activation < 0 || activation > 3) return fail(PFN_ERR_UNSUPPORTED, "activation %d (0 identity, 1 relu, 2 tanh, 3 sigmoid)", activation);
+  MlpPriorArgs a;
+  a.weights = weights; a.biases = biases; a.model_of = model_of; a.dims = dims; a.noise_std = noise_std; a.causes = causes; a.noise = noise; a.y = y; a.hidden = hidden;
+  a.B = B; a.T = T; a.HP = HP; a.Lmax = Lmax; a.activation = activation; a.gen_causes = gen_causes; a.seed = seed; a.offset = offset;
+  PFN_TRY(launch_mlp_prior(a, (hipStream_t)stream));
+  return PFN_OK;
+}

@@ -6,9 +6,17 @@
 // HBM-bound: 4 arrays read + 3 written per element (28 B / parameter).
 #include <algorithm>
 #include "pfn_device.h"
-#include "pfn_kernels.h"
+#include "pfn_host.h"
 
 namespace pfn {
+
+struct AdamArgs {
+  float* p; float* g; float* m; float* v; long n;
+  float lr, beta1, beta2, eps, max_norm, grad_scale;
+  int step;
+  int zero_grad;
+  float* scratch;  // >= 1025 floats; scratch[0] receives the pre-clip global grad norm
+};
 
 constexpr int NORM_BLOCKS = 1024;
 constexpr int SKIPPED_AT = 1 + NORM_BLOCKS;      // scratch[SKIPPED_AT]: number of skipped (non-finite gradient) steps since the caller zeroed the scratch
@@ -84,7 +92,7 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(AdamArgs a, long n4, int
   }
 }
 
-int launch_clip_adam(const AdamArgs& a, hipStream_t s) {
+static int launch_clip_adam(const AdamArgs& a, hipStream_t s) {
   if (a.n % 4) return PFN_ERR_ALIGNMENT;
   const long n4 = a.n / 4;
   if (n4 == 0) return PFN_OK;
@@ -96,3 +104,15 @@ int launch_clip_adam(const AdamArgs& a, hipStream_t s) {
 }
 
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" int pfn_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                                  float beta2, float eps, float max_norm, float grad_scale, int step, int zero_grad, float* scratch, void* stream) {
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !scratch || n < 0 || step < 1) return fail(PFN_ERR_ARGUMENT, "bad clip_adam arguments");
+  AdamArgs a;
+  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  a.max_norm = max_norm; a.grad_scale = grad_scale; a.step = step; a.zero_grad = zero_grad; a.scratch = scratch;
+  PFN_TRY(launch_clip_adam(a, (hipStream_t)stream));
+  return PFN_OK;
+}

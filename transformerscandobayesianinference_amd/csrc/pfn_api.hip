@@ -11,6 +11,7 @@
 #include <cstring>
 #include <mutex>
 #include <vector>
+#include "gp_prior.h"      // set_gp_planes
 #include "pfn_kernels.h"
 
 using namespace pfn;
@@ -44,24 +45,17 @@ void prof_end(void* token, int slot, hipStream_t s) {
 }
 }  // namespace pfn
 
-namespace {
-
-thread_local char g_err[512] = "";
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
+static thread_local char g_err[512] = "";      // what pfn_last_error_string returns
+int pfn::fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-#define PFN_TRY(expr)                                                                   \
-  do {                                                                                  \
-    int rc_ = (expr);                                                                   \
-    if (rc_ != PFN_OK) return fail(rc_, "%s failed with %d at %s:%d", #expr, rc_, __FILE__, __LINE__); \
-  } while (0)
 
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+namespace {
+
 inline int esize(int prec) { return prec_esize(prec); }
 
 int check_desc(const pfn_model_desc* d) {
@@ -590,7 +584,6 @@ int layer_backward_dx(const Model& m, const LayerP& t, const char* dqkv_t, const
 
 extern "C" {
 
-static bool g_gp_planes = true;      // PFN_TUNE_GP_PLANES (see pfn_gp_prior_sample)
 static bool g_fuse_delta = true;     // PFN_TUNE_FUSE_DELTA: the attention backward's delta from the d(ctx) GEMM's epilogue (stack_backward_impl)
 // Defaults handed to NEW descriptors by pfn_default_schedule() (test / profiling hook); the entry points read pfn_model_desc::schedule only.
 static int g_default_schedule = 0;
@@ -645,7 +638,7 @@ int pfn_set_tuning(int key, int value) {
       if (value > 0) g_default_schedule |= PFN_SCHED_KEY_CENTERING; else if (value == 0) g_default_schedule |= PFN_SCHED_NO_KEY_CENTERING;
       return PFN_OK;
     case PFN_TUNE_GEMM_LN_ROWS: set_gemm_ln_rows64(value); return PFN_OK;
-    case PFN_TUNE_GP_PLANES: g_gp_planes = value != 0; return PFN_OK;
+    case PFN_TUNE_GP_PLANES: set_gp_planes(value); return PFN_OK;
     case PFN_TUNE_FUSE_DELTA: g_fuse_delta = value != 0; return PFN_OK;
     case PFN_TUNE_ATTN_CACHE_SPLITS: set_attn_cache_split_cap(value); return PFN_OK;
     case PFN_TUNE_FUSE_LN_WIDE: g_default_schedule = value ? (g_default_schedule | PFN_SCHED_FUSE_LN_WIDE) : (g_default_schedule & ~PFN_SCHED_FUSE_LN_WIDE); return PFN_OK;
@@ -1360,453 +1353,6 @@ int pfn_stack_input_grads(const pfn_model_desc* d, const float* params, int B, i
   e.S = S; e.B = B; e.nf = d->num_features; e.E = E; e.sep = sep;
   e.scale_amax = (prec == PFN_PREC_FP16 && sep < S) ? w.lscale : nullptr;
   return launch_embed_input_grad(e, s);
-}
-
-int pfn_bar_mean_backward(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support, const float* mean, const float* gout,
-                          float* dlogits, void* stream) {
-  if (R < 0 || nbars < 1 || (R > 0 && (!logits || !borders || !mean || !gout || !dlogits))) return fail(PFN_ERR_ARGUMENT, "bad bar_mean_backward arguments");
-  BarArgs a; memset(&a, 0, sizeof(a));
-  a.logits = logits; a.ld = ld; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support;
-  a.mean_out = const_cast<float*>(mean); a.gout = gout; a.dlogits = dlogits;
-  PFN_TRY(launch_bar_mean_bwd(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-int pfn_bar_nll_forward(const float* logits, int64_t ld, const float* y, const float* borders, int64_t R, int nbars,
-                        int full_support, float* nll, float* lse, int32_t* bucket, void* stream) {
-  if (R < 0 || nbars < 1 || (R > 0 && (!logits || !y || !borders || !nll || !lse || !bucket))) return fail(PFN_ERR_ARGUMENT, "bad bar_nll_forward arguments");
-  BarArgs a; memset(&a, 0, sizeof(a));
-  a.logits = logits; a.ld = ld; a.y = y; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support;
-  a.nll = nll; a.lse = lse; a.bucket = bucket;
-  PFN_TRY(launch_bar_nll_fwd(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_bar_nll_backward(const float* logits, int64_t ld, const float* lse, const int32_t* bucket, const float* gout,
-                         int64_t R, int nbars, float* dlogits, void* stream) {
-  if (R < 0 || nbars < 1 || (R > 0 && (!logits || !lse || !bucket || !gout || !dlogits))) return fail(PFN_ERR_ARGUMENT, "bad bar_nll_backward arguments");
-  BarArgs a; memset(&a, 0, sizeof(a));
-  a.logits = logits; a.ld = ld; a.R = R; a.nbars = nbars; a.lse = const_cast<float*>(lse); a.bucket = const_cast<int*>(bucket);
-  a.gout = gout; a.dlogits = dlogits;
-  PFN_TRY(launch_bar_nll_bwd(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_bar_mean(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support, float* mean, void* stream) {
-  if (R < 0 || nbars < 1 || (R > 0 && (!logits || !borders || !mean))) return fail(PFN_ERR_ARGUMENT, "bad bar_mean arguments");
-  BarArgs a; memset(&a, 0, sizeof(a));
-  a.logits = logits; a.ld = ld; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support; a.mean_out = mean;
-  PFN_TRY(launch_bar_mean(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// the checks shared by pfn_bar_stats / pfn_bar_stats_backward / pfn_bar_sample; fills the common fields
-static int bar_stats_common(BarStatsArgs& a, const char* what, const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support) {
-  if (R < 0) return fail(PFN_ERR_ARGUMENT, "%s: R = %lld", what, (long long)R);
-  if (nbars < 1 || (full_support && nbars < 2)) return fail(PFN_ERR_ARGUMENT, "%s: nbars = %d%s", what, nbars, full_support ? " (full support needs two buckets)" : "");
-  if (ld < nbars) return fail(PFN_ERR_ARGUMENT, "%s: ld %lld < nbars %d", what, (long long)ld, nbars);
-  if (!logits || !borders) return fail(PFN_ERR_ARGUMENT, "%s: null pointer", what);
-  memset(&a, 0, sizeof(a));
-  a.logits = logits; a.ld = ld; a.borders = borders; a.R = R; a.nbars = nbars; a.full_support = full_support ? 1 : 0;
-  return PFN_OK;
-}
-static int bar_stats_spec(BarStatsArgs& a, const char* what, const int32_t* kinds, int K, const float* args, int64_t arg_ld) {
-  if (K < 1 || K > PFN_BAR_STATS_MAX) return fail(PFN_ERR_ARGUMENT, "%s: K = %d outside 1 .. %d", what, K, PFN_BAR_STATS_MAX);
-  if (!kinds || !args) return fail(PFN_ERR_ARGUMENT, "%s: null pointer", what);
-  if (arg_ld != 0 && arg_ld < K) return fail(PFN_ERR_ARGUMENT, "%s: arg_ld %lld < K %d", what, (long long)arg_ld, K);
-  for (int k = 0; k < K; ++k) {
-    if (kinds[k] < PFN_BAR_STAT_MEAN || kinds[k] > PFN_BAR_STAT_EI_MIN) return fail(PFN_ERR_ARGUMENT, "%s: unknown statistic %d at position %d", what, (int)kinds[k], k);
-    a.kinds[k] = kinds[k];
-    a.has_var |= kinds[k] == PFN_BAR_STAT_VARIANCE; a.has_icdf |= kinds[k] == PFN_BAR_STAT_ICDF;
-  }
-  a.K = K; a.args = args; a.arg_ld = arg_ld;
-  return PFN_OK;
-}
-int pfn_bar_stats(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
-                  const int32_t* kinds, int K, const float* args, int64_t arg_ld, float* out, void* stream) {
-  BarStatsArgs a;
-  PFN_TRY(bar_stats_common(a, "pfn_bar_stats", logits, ld, borders, R, nbars, full_support));
-  PFN_TRY(bar_stats_spec(a, "pfn_bar_stats", kinds, K, args, arg_ld));
-  if (!out) return fail(PFN_ERR_ARGUMENT, "pfn_bar_stats: null pointer");
-  a.out = out;
-  PFN_TRY(launch_bar_stats(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_bar_stats_backward(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
-                           const int32_t* kinds, int K, const float* args, int64_t arg_ld, const float* out, const float* gout,
-                           float* dlogits, void* stream) {
-  BarStatsArgs a;
-  PFN_TRY(bar_stats_common(a, "pfn_bar_stats_backward", logits, ld, borders, R, nbars, full_support));
-  PFN_TRY(bar_stats_spec(a, "pfn_bar_stats_backward", kinds, K, args, arg_ld));
-  if (!out || !gout || !dlogits) return fail(PFN_ERR_ARGUMENT, "pfn_bar_stats_backward: null pointer");
-  a.out = const_cast<float*>(out); a.gout = gout; a.dlogits = dlogits;
-  PFN_TRY(launch_bar_stats_bwd(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_bar_sample(const float* logits, int64_t ld, const float* borders, int64_t R, int nbars, int full_support,
-                   int n_samples, uint64_t seed, float* out, void* stream) {
-  BarStatsArgs a;
-  PFN_TRY(bar_stats_common(a, "pfn_bar_sample", logits, ld, borders, R, nbars, full_support));
-  if (n_samples < 0) return fail(PFN_ERR_ARGUMENT, "pfn_bar_sample: n_samples = %d", n_samples);
-  if (!out) return fail(PFN_ERR_ARGUMENT, "pfn_bar_sample: null pointer");
-  a.n_samples = n_samples; a.seed = seed; a.samples = out;
-  PFN_TRY(launch_bar_sample(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-int pfn_clip_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                       float beta2, float eps, float max_norm, float grad_scale, int step, int zero_grad, float* scratch, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !scratch || n < 0 || step < 1) return fail(PFN_ERR_ARGUMENT, "bad clip_adam arguments");
-  AdamArgs a;
-  a.p = params; a.g = grads; a.m = exp_avg; a.v = exp_avg_sq; a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.max_norm = max_norm; a.grad_scale = grad_scale; a.step = step; a.zero_grad = zero_grad; a.scratch = scratch;
-  PFN_TRY(launch_clip_adam(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// PFN_TUNE_GP_PLANES (test / profiling knob): 1 (default) = the rank-256 trailing update of the blocked Cholesky multiplies the pre-split fp16 planes the wide
-// triangular solve leaves behind K (gp_syrk_planes_kernel: two terms on a power-of-two scale, three products); 0 = it re-reads the f32 panel per tile and splits it
-// into three bf16 terms, six products (gp_syrk_kernel, rounds 2-3).  Both are f32-accurate (tools/sim_gp_split.py, tools/exp_gp_accuracy.py).
-int64_t pfn_gp_workspace_bytes(int B, int S) {
-  if (B < 1 || S < 1) return -1;
-  return gp_workspace_bytes(B, S);
-}
-static int gp_check_workspace(GpArgs& a, int64_t K_ws_bytes) {      // ABI 7: the planes only when the caller's allocation holds them
-  a.planes = nullptr; a.plane_rows = 0;
-  if (K_ws_bytes < (int64_t)a.B * a.S * a.S * 4) return fail(PFN_ERR_ARGUMENT, "K_ws_bytes %lld < B*S*S*4 = %lld", (long long)K_ws_bytes, (long long)a.B * a.S * a.S * 4);
-  if (g_gp_planes && K_ws_bytes >= gp_workspace_bytes(a.B, a.S)) gp_attach_planes(a);
-  return PFN_OK;
-}
-int pfn_gp_prior_sample(float* x, float* z, float* y, float* K_ws, int64_t K_ws_bytes, const float* lengthscale, const float* outputscale,
-                        const float* noise, int B, int S, int nf, int kernel, int gen_x, int gen_z, uint64_t seed, uint64_t offset,
-                        int32_t* info, void* stream) {
-  if (!x || !z || !y || !K_ws || !lengthscale || !outputscale || !noise || !info || B < 1 || S < 1 || nf < 1) return fail(PFN_ERR_ARGUMENT, "bad gp_prior_sample arguments");
-  if (kernel < 0 || kernel > 3) return fail(PFN_ERR_UNSUPPORTED, "kernel %d (0 = RBF, 1 / 2 / 3 = Matern nu 5/2, 3/2, 1/2)", kernel);
-  GpArgs a;
-  a.x = x; a.z = z; a.y = y; a.K = K_ws; a.lengthscale = lengthscale; a.outputscale = outputscale; a.noise = noise;
-  a.B = B; a.S = S; a.nf = nf; a.kernel = kernel; a.seed = seed; a.offset = offset; a.gen_x = gen_x; a.gen_z = gen_z; a.info = info;
-  a.w = nullptr;
-  if (int rc = gp_check_workspace(a, K_ws_bytes)) return rc;
-  PFN_TRY(launch_gp_sample(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-int pfn_gp_posterior(const float* x, const float* y, float* K_ws, int64_t K_ws_bytes, float* resid_ws, float* w_ws, const float* lengthscale,
-                     const float* outputscale, const float* noise, int B, int S, int nf, int kernel, float* nll, float* mean,
-                     float* var, int32_t* info, void* stream) {
-  if (!x || !y || !K_ws || !resid_ws || !w_ws || !lengthscale || !outputscale || !noise || !info || B < 1 || S < 1 || nf < 1)
-    return fail(PFN_ERR_ARGUMENT, "bad gp_posterior arguments");
-  if (kernel < 0 || kernel > 3) return fail(PFN_ERR_UNSUPPORTED, "kernel %d (0 = RBF, 1 / 2 / 3 = Matern nu 5/2, 3/2, 1/2)", kernel);
-  GpArgs a;
-  a.x = const_cast<float*>(x); a.z = nullptr; a.y = resid_ws; a.K = K_ws; a.lengthscale = lengthscale; a.outputscale = outputscale;
-  a.noise = noise; a.B = B; a.S = S; a.nf = nf; a.kernel = kernel; a.seed = 0; a.offset = 0; a.gen_x = 0; a.gen_z = 0; a.info = info;
-  a.w = w_ws;
-  if (int rc = gp_check_workspace(a, K_ws_bytes)) return rc;
-  PFN_TRY(launch_gp_posterior(a, y, nll, mean, var, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// ---- GP hyper-parameter fit (gp_fit.hip; ABI 10, additive) ----
-int64_t pfn_gp_fit_workspace_bytes(int P, int S) {
-  if (P < 1 || S < 1) return -1;
-  return gp_fit_workspace_bytes(P, S);
-}
-static int gp_fit_check(const float* x, const float* y, const float* theta, const float* prior, int P, int S, int nf, int kernel, void* ws, int64_t ws_bytes, int32_t* info) {
-  if (!x || !y || !theta || !prior || !ws || !info || P < 1 || S < 1 || nf < 1) return fail(PFN_ERR_ARGUMENT, "bad gp_fit arguments");
-  if (P > 65535) return fail(PFN_ERR_UNSUPPORTED, "P %d > 65535 problems per call", P);
-  if (S % 4) return fail(PFN_ERR_UNSUPPORTED, "S %d is not a multiple of 4", S);
-  if (nf > 126) return fail(PFN_ERR_UNSUPPORTED, "nf %d > 126 (the tiles stage 128 rows of x in 64 KB of LDS)", nf);
-  if (kernel < 0 || kernel > 3) return fail(PFN_ERR_UNSUPPORTED, "kernel %d (0 = RBF, 1 / 2 / 3 = Matern nu 5/2, 3/2, 1/2)", kernel);
-  if (ws_bytes < gp_fit_workspace_bytes(P, S)) return fail(PFN_ERR_ARGUMENT, "ws_bytes %lld < pfn_gp_fit_workspace_bytes = %lld", (long long)ws_bytes, (long long)gp_fit_workspace_bytes(P, S));
-  return PFN_OK;
-}
-int pfn_gp_mll_grad(const float* x, const float* y, const int32_t* n_of, const float* theta, const float* prior, int P, int S, int nf, int kernel, int flags,
-                    void* ws, int64_t ws_bytes, float* value, float* grad, int32_t* info, void* stream) {
-  if (int rc = gp_fit_check(x, y, theta, prior, P, S, nf, kernel, ws, ws_bytes, info)) return rc;
-  if (!value) return fail(PFN_ERR_ARGUMENT, "bad gp_mll_grad arguments");
-  GpFitArgs a{};
-  a.x = x; a.y = y; a.n_of = n_of; a.theta = theta; a.prior = prior; a.P = P; a.S = S; a.nf = nf; a.kernel = kernel; a.flags = flags;
-  a.ws = ws; a.value = value; a.grad = grad; a.info = info;
-  PFN_TRY(launch_gp_mll_grad(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_gp_fit_predict(const float* x, const float* y, const int32_t* n_of, const float* theta, const float* prior, int P, int S, int nf, int kernel,
-                       const float* x_test, int m, void* ws, int64_t ws_bytes, float* mean, float* var, int32_t* info, void* stream) {
-  if (int rc = gp_fit_check(x, y, theta, prior, P, S, nf, kernel, ws, ws_bytes, info)) return rc;
-  if (m < 0 || (m > 0 && (!x_test || !mean || !var))) return fail(PFN_ERR_ARGUMENT, "bad gp_fit_predict arguments");
-  GpFitArgs a{};
-  a.x = x; a.y = y; a.n_of = n_of; a.theta = theta; a.prior = prior; a.P = P; a.S = S; a.nf = nf; a.kernel = kernel; a.flags = 0;
-  a.ws = ws; a.x_test = x_test; a.m = m; a.mean = mean; a.var = var; a.info = info;
-  PFN_TRY(launch_gp_fit_predict(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-int64_t pfn_nuts_workspace_bytes(int C, int D, int max_tree_depth) {
-  if (C < 1 || D < 1 || D > 128 || max_tree_depth < 1 || max_tree_depth > 10) return -1;
-  return nuts_workspace_bytes(C, D, max_tree_depth);
-}
-static int nuts_check(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int depth) {
-  if (C < 1 || D < 1 || D > 128 || depth < 1 || depth > 10 || ld < D || !ws) return fail(PFN_ERR_ARGUMENT, "bad nuts arguments (C %d, D %d in 1..128, ld %lld >= D, max_tree_depth %d in 1..10)", C, D, (long long)ld, depth);
-  if (ws_bytes < nuts_workspace_bytes(C, D, depth)) return fail(PFN_ERR_ARGUMENT, "ws_bytes %lld < pfn_nuts_workspace_bytes = %lld", (long long)ws_bytes, (long long)nuts_workspace_bytes(C, D, depth));
-  return PFN_OK;
-}
-int pfn_nuts_init(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int max_tree_depth, int num_warmup, int num_samples, int flags, const int32_t* window_ends,
-                  int n_windows, int window_start, float step_size, float target_accept, uint64_t seed, const int64_t* chain_ids, const float* theta0,
-                  const float* inv_mass0, float* trial, int32_t* done_count, void* stream) {
-  if (int rc = nuts_check(ws, ws_bytes, C, D, ld, max_tree_depth)) return rc;
-  if (!theta0 || !trial || !done_count || num_warmup < 0 || num_samples < 1 || !(step_size > 0.f) || !(target_accept > 0.f && target_accept < 1.f))
-    return fail(PFN_ERR_ARGUMENT, "bad nuts_init arguments");
-  if (flags & ~(PFN_NUTS_ADAPT_MASS | PFN_NUTS_KEEP_WARMUP)) return fail(PFN_ERR_ARGUMENT, "unknown nuts flags 0x%x", flags);
-  if (n_windows < 0 || n_windows > PFN_NUTS_MAX_WINDOWS || (n_windows > 0 && !window_ends) || window_start < 0) return fail(PFN_ERR_ARGUMENT, "bad adaptation windows");
-  for (int i = 0; i < n_windows; ++i)
-    if (window_ends[i] <= (i ? window_ends[i - 1] : window_start) || window_ends[i] >= num_warmup)
-      return fail(PFN_ERR_ARGUMENT, "adaptation window ends must increase and lie below num_warmup (dual averaging restarts at a window end and needs transitions after it)");
-  NutsInit a{};
-  a.ws = ws; a.C = C; a.D = D; a.depth = max_tree_depth; a.ld = ld; a.W = num_warmup; a.N = num_samples; a.flags = flags; a.window_ends = window_ends; a.n_windows = n_windows;
-  a.window_start = window_start; a.step_size = step_size; a.target = target_accept; a.seed = seed; a.chain_ids = chain_ids; a.theta0 = theta0; a.inv_mass0 = inv_mass0;
-  a.trial = trial; a.done_count = done_count;
-  PFN_TRY(launch_nuts_init(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_nuts_advance(void* ws, int64_t ws_bytes, int C, int D, int64_t ld, int max_tree_depth, int num_warmup, int num_samples, const float* value, const float* grad,
-                     const int32_t* info, const float* scale, const float* shift, float* trial, float* samples, float* stats, float* warm, int32_t* done_count, void* stream) {
-  if (int rc = nuts_check(ws, ws_bytes, C, D, ld, max_tree_depth)) return rc;
-  if (!value || !grad || !trial || !samples || !stats || !done_count || num_warmup < 0 || num_samples < 1) return fail(PFN_ERR_ARGUMENT, "bad nuts_advance arguments");
-  NutsAdvance a{};
-  a.ws = ws; a.C = C; a.D = D; a.depth = max_tree_depth; a.W = num_warmup; a.N = num_samples; a.ld = ld; a.value = value; a.grad = grad; a.info = info; a.scale = scale; a.shift = shift;
-  a.trial = trial; a.samples = samples; a.stats = stats; a.warm = warm; a.done_count = done_count;
-  PFN_TRY(launch_nuts_advance(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// ---- BNN posterior target (bnn_mcmc.hip; ABI 10, additive) ----
-static int bnn_limits(int F, int H, int activation) {      // what the kernels are built for; the checks come shapes first: nothing here touches a pointer or HIP
-  if (F < 1 || F > 16) return fail(PFN_ERR_UNSUPPORTED, "F %d outside 1 .. 16 (a lane keeps its row of W1 in registers)", F);
-  if (H < 1 || H > 64) return fail(PFN_ERR_UNSUPPORTED, "H %d outside 1 .. 64 (lane = hidden unit, one wave per chain at most)", H);
-  if (activation < 0 || activation > 1) return fail(PFN_ERR_UNSUPPORTED, "activation %d (0 identity, 1 tanh)", activation);
-  return PFN_OK;
-}
-static int bnn_batch(int P, int K, int F, int H, int64_t ld) {      // K parameter vectors of D numbers, ld apart, for each of P problems
-  if (P < 1 || K < 1 || (int64_t)P * K > 0x7fffffff) return fail(PFN_ERR_ARGUMENT, "P %d x K %d chains: need P >= 1, K >= 1, P K < 2^31", P, K);
-  if (ld < (int64_t)H * (F + 3) + 2) return fail(PFN_ERR_ARGUMENT, "ld %lld < D = H (F + 3) + 2 = %d", (long long)ld, H * (F + 3) + 2);
-  return PFN_OK;
-}
-static int bnn_check(int P, int K, int F, int H, int activation, int64_t ld) {
-  if (int rc = bnn_limits(F, H, activation)) return rc;
-  return bnn_batch(P, K, F, H, ld);
-}
-// what the two step loops (SVI, SVGD) ask of their common arguments, after the limits: the problem and step counts and the pointers, ld, Adam's numbers
-static int bnn_steps_check(const char* fn, int P, int S, int F, int H, int64_t ld, int64_t step0, int num_steps, const void* x, const void* y, const void* state, float lr,
-                           float beta1, float beta2, float eps) {
-  if (P < 1 || S < 1 || step0 < 0 || num_steps < 0 || !x || !y || !state)
-    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (P %d >= 1, S %d >= 1, step0 %lld >= 0, num_steps %d >= 0, x, y, state not NULL)", fn, P, S, (long long)step0, num_steps);
-  if (int rc = bnn_batch(P, 1, F, H, ld)) return rc;      // ld >= D
-  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
-    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (lr %g >= 0, beta1 %g and beta2 %g in [0, 1), eps %g >= 0)", fn, lr, beta1, beta2, eps);
-  return PFN_OK;
-}
-int pfn_bnn_logp_grad(const float* x, const float* y, const int32_t* n_of, const float* theta, int64_t ld, int P, int K, int S, int F, int H, int activation,
-                      float* value, float* grad, void* stream) {
-  if (int rc = bnn_check(P, K, F, H, activation, ld)) return rc;
-  if (S < 1 || !x || !y || !theta || !value) return fail(PFN_ERR_ARGUMENT, "bad bnn_logp_grad arguments (S %d >= 1, x, y, theta, value not NULL)", S);
-  BnnArgs a{};
-  a.x = x; a.y = y; a.n_of = n_of; a.theta = theta; a.ld = ld; a.P = P; a.K = K; a.S = S; a.F = F; a.H = H; a.activation = activation; a.value = value; a.grad = grad;
-  PFN_TRY(launch_bnn_logp_grad(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_bnn_predict(const float* x_test, const float* theta, int64_t ld, int P, int K, int m, int F, int H, int activation, float* prob1, void* stream) {
-  if (int rc = bnn_check(P, K, F, H, activation, ld)) return rc;
-  if (m < 0 || !theta || (m > 0 && (!x_test || !prob1))) return fail(PFN_ERR_ARGUMENT, "bad bnn_predict arguments (m %d >= 0, x_test, theta, prob1 not NULL)", m);
-  if (m == 0) return PFN_OK;
-  BnnArgs a{};
-  a.theta = theta; a.ld = ld; a.P = P; a.K = K; a.F = F; a.H = H; a.activation = activation; a.x_test = x_test; a.m = m; a.prob1 = prob1;
-  PFN_TRY(launch_bnn_predict(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// ---- SVI on the BNN (bnn_svi.hip; ABI 10, additive) ----
-int pfn_bnn_svi_steps(const float* x, const float* y, const int32_t* n_of, float* state, int64_t ld, int P, int S, int F, int H, int activation, int num_particles,
-                      int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, uint64_t seed, const int64_t* problem_ids, float* loss, void* stream) {
-  if (int rc = bnn_limits(F, H, activation)) return rc;
-  if (int rc = bnn_steps_check("bnn_svi_steps", P, S, F, H, ld, step0, num_steps, x, y, state, lr, beta1, beta2, eps)) return rc;
-  if (num_particles < 1) return fail(PFN_ERR_ARGUMENT, "bad bnn_svi_steps arguments (num_particles %d >= 1)", num_particles);
-  if (step0 > (int64_t)1 << 40 || (step0 + num_steps + 1) * (int64_t)num_particles >= (int64_t)1 << 53)
-    return fail(PFN_ERR_ARGUMENT, "step0 %lld must not exceed 2^40 and (step0 + num_steps + 1) num_particles must stay below 2^53 (the Philox counter of a particle's noise)", (long long)step0);
-  if (num_steps == 0) return PFN_OK;
-  BnnSviArgs a{};
-  a.x = x; a.y = y; a.n_of = n_of; a.state = state; a.ld = ld; a.P = P; a.S = S; a.F = F; a.H = H; a.activation = activation; a.K = num_particles; a.step0 = step0;
-  a.num_steps = num_steps; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.seed = seed; a.problem_ids = problem_ids; a.loss = loss;
-  PFN_TRY(launch_bnn_svi_steps(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// ---- SVGD on the BNN (bnn_svgd.hip; ABI 10, additive) ----
-static int bnn_svgd_limits(int F, int H, int activation, int N) {      // what the kernel is built for: nothing here touches a pointer or HIP
-  if (int rc = bnn_limits(F, H, activation)) return rc;
-  if (N < 2 || N > PFN_BNN_SVGD_MAX_PARTICLES)
-    return fail(PFN_ERR_UNSUPPORTED, "num_particles %d outside 2 .. %d (lane = particle in the Stein step; the median needs a pair)", N, PFN_BNN_SVGD_MAX_PARTICLES);
-  return PFN_OK;
-}
-int64_t pfn_bnn_svgd_workspace_bytes(int P, int num_particles, int F, int H) {
-  if (P < 1 || bnn_svgd_limits(F, H, 0, num_particles)) return -1;
-  return bnn_svgd_workspace_bytes(P, num_particles, H * (F + 3) + 2);
-}
-int pfn_bnn_svgd_steps(const float* x, const float* y, const int32_t* n_of, float* state, int64_t ld, int P, int S, int F, int H, int activation, int num_particles,
-                       int64_t step0, int num_steps, float lr, float beta1, float beta2, float eps, float bandwidth_factor, void* workspace,
-                       int64_t workspace_bytes, float* potential, float* bandwidth, void* stream) {
-  if (int rc = bnn_svgd_limits(F, H, activation, num_particles)) return rc;
-  if (int rc = bnn_steps_check("bnn_svgd_steps", P, S, F, H, ld, step0, num_steps, x, y, state, lr, beta1, beta2, eps)) return rc;
-  if (!(lr <= 3.4e38f) || !(bandwidth_factor > 0.f)) return fail(PFN_ERR_ARGUMENT, "bad bnn_svgd_steps arguments (lr %g finite, bandwidth_factor %g > 0)", lr, bandwidth_factor);
-  const int D = H * (F + 3) + 2;
-  const int64_t need = bnn_svgd_workspace_bytes(P, num_particles, D);
-  if (workspace_bytes < need || (need > 0 && !workspace))
-    return fail(PFN_ERR_ARGUMENT, "workspace_bytes %lld < pfn_bnn_svgd_workspace_bytes = %lld (or a NULL workspace)", (long long)workspace_bytes, (long long)need);
-  if (num_steps == 0) return PFN_OK;
-  BnnSvgdArgs a{};
-  a.x = x; a.y = y; a.n_of = n_of; a.state = state; a.ld = ld; a.P = P; a.S = S; a.F = F; a.H = H; a.activation = activation; a.N = num_particles; a.step0 = step0;
-  a.num_steps = num_steps; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.bandwidth_factor = bandwidth_factor;
-  a.grads = need > 0 ? (float*)workspace : nullptr; a.potential = potential; a.bandwidth = bandwidth;
-  PFN_TRY(launch_bnn_svgd_steps(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// ---- Tabular study (tabular.hip; ABI 10, additive) ----
-int pfn_tabular_windows(const float* X, const float* y, const int32_t* starts, int64_t N, int F, int F_out, int W, int bptt, int sep, float rescale, int mode,
-                        float* x_out, float* y_out, void* stream) {
-  if (F < 1 || F > TAB_MAX_FEATURES || F_out < F)
-    return fail(PFN_ERR_UNSUPPORTED, "F %d outside 1 .. %d or F_out %d < F (a block keeps one window's per-feature statistics in LDS)", F, TAB_MAX_FEATURES, F_out);
-  if (mode != PFN_TAB_NORM_WITH_TEST && mode != PFN_TAB_NORM_TRAIN_ONLY) return fail(PFN_ERR_ARGUMENT, "unknown tabular_windows mode %d", mode);
-  if (N < 1 || W < 1 || sep < 1 || sep > bptt || (mode == PFN_TAB_NORM_WITH_TEST && sep == bptt) || bptt > 65536 || !(rescale > 0.f))
-    return fail(PFN_ERR_ARGUMENT, "bad tabular_windows arguments (N %lld >= 1, W %d >= 1, 1 <= sep %d <%s bptt %d <= 65536, rescale %g > 0)", (long long)N, W, sep,
-                mode == PFN_TAB_NORM_WITH_TEST ? "" : "=", bptt, (double)rescale);
-  if (!X || !y || !starts || !x_out) return fail(PFN_ERR_ARGUMENT, "bad tabular_windows arguments (X, y, starts, x_out not NULL)");
-  if ((uintptr_t)x_out % 16) return fail(PFN_ERR_ALIGNMENT, "tabular_windows: x_out must be 16-byte aligned");
-  TabWindowsArgs a{};
-  a.X = X; a.y = y; a.starts = starts; a.N = N; a.F = F; a.F_out = F_out; a.W = W; a.bptt = bptt; a.sep = sep; a.mode = mode; a.rescale = rescale;
-  a.x_out = x_out; a.y_out = y_out;
-  PFN_TRY(launch_tab_windows(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_auc_counts(const float* scores, const float* labels, int T, int C, int64_t* counts, void* stream) {
-  if (T < 1 || T > 4096) return fail(PFN_ERR_UNSUPPORTED, "auc_counts: T %d outside 1 .. 4096 (a block stages one column in LDS)", T);
-  if (C < 1 || !scores || !labels || !counts) return fail(PFN_ERR_ARGUMENT, "bad auc_counts arguments (C %d >= 1, scores, labels, counts not NULL)", C);
-  PFN_TRY(launch_auc_counts(scores, labels, T, C, counts, (hipStream_t)stream));
-  return PFN_OK;
-}
-// The shape check of the four fold-based entry points (pfn_knn_cv, pfn_logistic_cv, pfn_gpc_lml_grad, pfn_gpc_predict): the ranges (PFN_ERR_UNSUPPORTED; `why` says
-// what sets them) before P, n_splits and the pointers (PFN_ERR_ARGUMENT).  max_nc = 0: a call without candidates, max_splits = 0: one without n_splits (kNN).
-static int fold_shapes(const char* what, const char* why, int P, int n, int max_n, int T, int F, int NC, int max_nc, int n_splits, int max_splits, bool pointers) {
-  char own[48] = "";      // the clause of what only some of the calls have
-  if (n < 4 || n > max_n || T < 1 || T > 128 || F < 1 || F > 128 || (max_nc && (NC < 1 || NC > max_nc))) {
-    if (max_nc) snprintf(own, sizeof own, ", NC %d outside 1 .. %d", NC, max_nc);
-    return fail(PFN_ERR_UNSUPPORTED, "%s: n %d outside 4 .. %d, T %d outside 1 .. 128, F %d outside 1 .. 128%s (%s)", what, n, max_n, T, F, own, why);
-  }
-  if (P < 1 || (max_splits && (n_splits < 2 || n_splits > max_splits)) || !pointers) {
-    if (max_splits) snprintf(own, sizeof own, ", 2 <= n_splits %d <= %d", n_splits, max_splits);
-    return fail(PFN_ERR_ARGUMENT, "bad %s arguments (P %d >= 1%s, no NULL buffer)", what, P, own);
-  }
-  return PFN_OK;
-}
-int pfn_knn_cv(const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F, int32_t* cv_correct, int32_t* test_pos,
-               int32_t* test_nbr, void* stream) {
-  if (const int rc = fold_shapes("knn_cv", "one thread per query, every row in LDS", P, n, 128, T, F, 0, 0, 0, 0,
-                                 train && labels && test && fold && cv_correct && test_pos && test_nbr)) return rc;
-  KnnCvArgs a{};
-  a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.P = P; a.n = n; a.T = T; a.F = F; a.cv_correct = cv_correct; a.test_pos = test_pos; a.test_nbr = test_nbr;
-  PFN_TRY(launch_knn_cv(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// ---- Logistic regression with its grid search (logistic.hip; ABI 10, additive) ----
-int pfn_logistic_cv(const float* train, const float* labels, const float* test, const int32_t* fold, const float* cand_C, const int32_t* cand_kind, int P, int n, int T,
-                    int F, int NC, int n_splits, int32_t* cv_correct, float* test_z, int32_t* status, float* coef, void* stream) {
-  if (const int rc = fold_shapes("logistic_cv", "one block per fit, its rows and its Hessian in LDS", P, n, 128, T, F, NC, PFN_LOGIT_MAX_CANDIDATES, n_splits, PFN_LOGIT_FOLDS,
-                                 train && labels && test && fold && cand_C && cand_kind && cv_correct && test_z && status)) return rc;      // (coef may be NULL)
-  LogitCvArgs a{};
-  a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.cand_C = cand_C; a.cand_kind = cand_kind; a.P = P; a.n = n; a.T = T; a.F = F; a.NC = NC;
-  a.n_splits = n_splits; a.cv_correct = cv_correct; a.test_z = test_z; a.status = status; a.coef = coef;
-  PFN_TRY(launch_logit_cv(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// ---- GP classifier with its grid search (gpc.hip; ABI 10, additive) ----
-static int gpc_shapes(const char* what, int P, int n, int T, int F, int NC, int n_splits, bool pointers) {
-  return fold_shapes(what, "one block per fit, three n x n matrices in LDS", P, n, PFN_GPC_MAX_N, T, F, NC, PFN_GPC_MAX_CANDIDATES, n_splits, PFN_GPC_FOLDS, pointers);
-}
-int pfn_gpc_lml_grad(const float* theta, const float* train, const float* labels, const int32_t* fold, int P, int n, int F, int NC, int n_splits, float* value,
-                     float* grad, int32_t* status, void* stream) {
-  if (const int rc = gpc_shapes("gpc_lml_grad", P, n, 1, F, NC, n_splits, theta && train && labels && fold && value && grad && status)) return rc;
-  GpcArgs a{};
-  a.theta = theta; a.train = train; a.labels = labels; a.fold = fold; a.P = P; a.n = n; a.T = 1; a.F = F; a.NC = NC; a.n_splits = n_splits; a.value = value; a.grad = grad;
-  a.status = status;
-  PFN_TRY(launch_gpc_lml_grad(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_gpc_predict(const float* theta, const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F, int NC, int n_splits,
-                    float* cv_f, float* test_f, float* test_var, int32_t* status, void* stream) {
-  if (const int rc = gpc_shapes("gpc_predict", P, n, T, F, NC, n_splits, theta && train && labels && test && fold && cv_f && test_f && test_var && status)) return rc;
-  GpcArgs a{};
-  a.theta = theta; a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.P = P; a.n = n; a.T = T; a.F = F; a.NC = NC; a.n_splits = n_splits; a.cv_f = cv_f;
-  a.test_f = test_f; a.test_var = test_var; a.status = status;
-  PFN_TRY(launch_gpc_predict(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-// ---- Stroke prior of the few-shot study (stroke_prior.hip; ABI 10, additive) ----
-static int stroke_size(const char* what, int size) {
-  if (size < 8 || size > 64) return fail(PFN_ERR_UNSUPPORTED, "%s: size %d outside 8 .. 64 (one lane per row, a row's mask in 64 bits)", what, size);
-  return PFN_OK;
-}
-int pfn_stroke_render(const int32_t* segs, const int32_t* n_strokes, const int32_t* width, const uint8_t* noise, int64_t N, int size, int normalize,
-                      int64_t image_stride, uint64_t seed, uint64_t offset, float* x, uint8_t* raw, uint8_t* img, void* stream) {
-  if (const int rc = stroke_size("stroke_render", size)) return rc;
-  if (N < 0 || N > (int64_t)1 << 32 || image_stride < (int64_t)size * size)
-    return fail(PFN_ERR_ARGUMENT, "bad stroke_render arguments (0 <= N %lld <= 2^32, image_stride %lld >= size^2)", (long long)N, (long long)image_stride);
-  if (!segs || !n_strokes || !width || !x || (uintptr_t)segs % 16 || (uintptr_t)n_strokes % 4 || (uintptr_t)width % 4 || (uintptr_t)x % 4)
-    return fail(PFN_ERR_ARGUMENT, "bad stroke_render arguments (segs, n_strokes, width, x not NULL; segs 16-byte, the others 4-byte aligned)");
-  if (N == 0) return PFN_OK;
-  StrokeRenderArgs a{};
-  a.segs = segs; a.n_strokes = n_strokes; a.width = width; a.noise = noise; a.N = N; a.size = size; a.normalize = normalize ? 1 : 0; a.image_stride = image_stride;
-  a.vec16 = (size % 4 == 0 && image_stride % 4 == 0 && (uintptr_t)x % 16 == 0) ? 1 : 0;
-  a.seed = seed; a.offset = offset; a.x = x; a.raw = raw; a.img = img;
-  PFN_TRY(launch_stroke_render(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-int pfn_stroke_prior_sample(const int32_t* labels, int B, int T, int num_classes, int size, int normalize, int strokes_lo, int strokes_hi, int len_lo, int len_hi,
-                            int start_lo, int start_hi, int width_lo, int width_hi, int max_offset, int max_target_offset, uint64_t seed, uint64_t offset,
-                            uint64_t first_dataset, float* x, int32_t* cls_n, int32_t* cls_len, int32_t* cls_start, double* cls_dir, int32_t* segs, int32_t* width,
-                            uint8_t* raw, uint8_t* img, int32_t* status, void* stream) {
-  if (const int rc = stroke_size("stroke_prior_sample", size)) return rc;
-  if (num_classes < 1 || num_classes > PFN_STROKE_MAX_CLASSES || strokes_hi > PFN_STROKE_MAX_STROKES || width_hi > PFN_STROKE_MAX_WIDTH || len_hi > 1024 ||
-      start_hi > 1024 || max_offset > 1024 || max_target_offset > 1024)
-    return fail(PFN_ERR_UNSUPPORTED, "stroke_prior_sample: num_classes %d outside 1 .. %d, strokes_hi %d above %d, width_hi %d above %d, or len_hi %d, start_hi %d, "
-                "max_offset %d, max_target_offset %d above 1024", num_classes, PFN_STROKE_MAX_CLASSES, strokes_hi, PFN_STROKE_MAX_STROKES, width_hi, PFN_STROKE_MAX_WIDTH,
-                len_hi, start_hi, max_offset, max_target_offset);
-  if (B < 1 || T < 1 || (int64_t)B * T > 0x7fffffffll || strokes_lo < 0 || strokes_lo > strokes_hi || len_lo < 0 || len_lo > len_hi || start_lo < 0 || start_lo > start_hi ||
-      width_lo < 0 || width_lo > width_hi || max_offset < 0 || max_target_offset < 0)
-    return fail(PFN_ERR_ARGUMENT, "bad stroke_prior_sample arguments (B %d, T %d >= 1, B T < 2^31, 0 <= lo <= hi for strokes %d .. %d, len %d .. %d, start %d .. %d, "
-                "width %d .. %d, max_offset %d, max_target_offset %d >= 0)", B, T, strokes_lo, strokes_hi, len_lo, len_hi, start_lo, start_hi, width_lo, width_hi, max_offset,
-                max_target_offset);
-  if (!labels || !x || !cls_n || !cls_len || !cls_start || !cls_dir || !segs || !width || !status || (uintptr_t)segs % 16 || (uintptr_t)cls_dir % 8 ||
-      (uintptr_t)labels % 4 || (uintptr_t)x % 4 || (uintptr_t)cls_n % 4 || (uintptr_t)cls_len % 4 || (uintptr_t)cls_start % 4 || (uintptr_t)width % 4 || (uintptr_t)status % 4)
-    return fail(PFN_ERR_ARGUMENT, "bad stroke_prior_sample arguments (only raw and img may be NULL; segs 16-byte, cls_dir 8-byte, the others 4-byte aligned)");
-  StrokePriorArgs a{};
-  a.labels = labels; a.B = B; a.T = T; a.C = num_classes; a.size = size; a.normalize = normalize ? 1 : 0; a.vec16 = (size % 4 == 0 && (uintptr_t)x % 16 == 0) ? 1 : 0;
-  a.strokes_lo = strokes_lo; a.strokes_hi = strokes_hi; a.len_lo = len_lo; a.len_hi = len_hi; a.start_lo = start_lo; a.start_hi = start_hi; a.width_lo = width_lo;
-  a.width_hi = width_hi; a.max_off = max_offset; a.max_toff = max_target_offset; a.seed = seed; a.offset = offset; a.first_dataset = first_dataset;
-  a.x = x; a.cls_n = cls_n; a.cls_len = cls_len; a.cls_start = cls_start; a.cls_dir = cls_dir; a.segs = segs; a.width = width; a.raw = raw; a.img = img; a.status = status;
-  PFN_TRY(launch_stroke_prior(a, (hipStream_t)stream));
-  return PFN_OK;
-}
-
-int pfn_mlp_prior_forward(const float* weights, const float* biases, const int32_t* model_of, const int32_t* dims, const float* noise_std,
-                          float* causes, const float* noise, float* y, float* hidden, int B, int T, int HP, int Lmax, int activation, int gen_causes,
-                          uint64_t seed, uint64_t offset, void* stream) {
-  if (!weights || !biases || !model_of || !dims || !noise_std || !causes || !y) return fail(PFN_ERR_ARGUMENT, "bad mlp_prior_forward arguments");
-  if (activation < 0 || activation > 3) return fail(PFN_ERR_UNSUPPORTED, "activation %d (0 identity, 1 relu, 2 tanh, 3 sigmoid)", activation);
-  MlpPriorArgs a;
-  a.weights = weights; a.biases = biases; a.model_of = model_of; a.dims = dims; a.noise_std = noise_std; a.causes = causes; a.noise = noise; a.y = y; a.hidden = hidden;
-  a.B = B; a.T = T; a.HP = HP; a.Lmax = Lmax; a.activation = activation; a.gen_causes = gen_causes; a.seed = seed; a.offset = offset;
-  PFN_TRY(launch_mlp_prior(a, (hipStream_t)stream));
-  return PFN_OK;
 }
 
 // ---- single-op entry points -------------------------------------------------------------------------

@@ -1,41 +1,11 @@
-// Internal (C++) launcher interface between the kernels (*.hip) and the C-ABI layer (pfn_api.hip).
+// Internal (C++) launcher interface between the kernels of the transformer stack (gemm.hip, gemm_tn.hip, attention.hip, rowwise.hip) and its schedules
+// (pfn_api.hip).  Every other .hip file defines its own entry points beside its kernels and needs only pfn_host.h.
 // Nothing here crosses the shared-library boundary; see include/pfn_hip.h for the exported ABI.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <atomic>
-#include "../../include/pfn_hip.h"
+#include "pfn_host.h"
 
 namespace pfn {
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute and setting it costs tens of microseconds of host time, so
-// every launcher keeps one of these per kernel: the largest dynamic-LDS size granted so far on each device.  Lock-free; two host
-// threads racing on a first use at worst both set the attribute (idempotent) -- neither can launch before it is set.
-struct LdsAllowance {
-  std::atomic<size_t> granted[16];   // by device ordinal (a node has 8)
-  template <typename K> void ensure(K kernel, size_t bytes) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::atomic<size_t>& g = granted[dev & 15];
-    if (bytes <= g.load(std::memory_order_acquire)) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    size_t cur = g.load(std::memory_order_relaxed);
-    while (cur < bytes && !g.compare_exchange_weak(cur, bytes, std::memory_order_release)) {}
-  }
-};
-
-// A launch with `bytes` of dynamic LDS that raises the kernel's allowance only above the 64 KB a kernel has by default (the BNN step loops, the fold-based
-// kernels of the tabular study; other launchers call ensure() unconditionally).  `allow`: the call site's own static, one per kernel instantiation.
-template <class... P, class... A>
-int launch_lds(void (*kernel)(P...), LdsAllowance& allow, dim3 grid, dim3 block, size_t bytes, hipStream_t s, const A&... args) {
-  if (bytes > 64 * 1024) allow.ensure(kernel, bytes);
-  kernel<<<grid, block, bytes, s>>>(args...);
-  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-}
-
-// Operand element types (include/pfn_hip.h PFN_PREC_*): two 16-bit formats on the matrix cores at the same rate and bytes, and the exact-f32 parity mode.
-inline bool prec_is16(int p) { return p == PFN_PREC_BF16 || p == PFN_PREC_FP16; }
-inline int prec_esize(int p) { return prec_is16(p) ? 2 : 4; }
 // host-side dispatch of a statement over the operand type T (device code only sees the instantiations)
 #define PFN_DISPATCH_OP(prec, ...)                                                          \
   do {                                                                                      \
@@ -46,32 +16,15 @@ inline int prec_esize(int p) { return prec_is16(p) ? 2 : 4; }
 typedef __bf16 bf16_t;
 typedef _Float16 f16_t;
 
-// In-step kernel timing (test / profiling hook pfn_profile_*, pfn_api.hip): an event pair on the launch stream around the launches inside the scope;
-// a no-op unless profiling is enabled.
-bool prof_enabled();
-void* prof_begin(int slot, hipStream_t s);
-void prof_end(void* token, int slot, hipStream_t s);
-struct ProfScope {
-  void* token; int slot; hipStream_t s;
-  ProfScope(int slot_, hipStream_t s_) : token(prof_begin(slot_, s_)), slot(slot_), s(s_) {}
-  ~ProfScope() { prof_end(token, slot, s); }
-  ProfScope(const ProfScope&) = delete;
-  ProfScope& operator=(const ProfScope&) = delete;
-};
-
 // ---------------------------------------------------------------------------------------------
 // Dropout masks (training with dropout > 0: TransformerEncoderLayer's four sites, reference transformer.py:17 / train.py:22).
 // A mask is a pure function of (site seed, i, j) so the backward regenerates what the forward applied, in whatever register
 // layout a kernel holds the elements, with no mask tensor in HBM:
 //     keep(s, i, j)  <=>  mix32(s ^ i * 0x9E3779B1 ^ j * 0x85EBCA77) >= thr,      thr = p * 2^32
-// (mix32 = the "lowbias32" integer finaliser).  site seed = dropout_site_seed(call seed, layer, site); the attention site mixes the
+// (mix32: pfn_host.h).  site seed = dropout_site_seed(call seed, layer, site); the attention site mixes the
 // (dataset, head) index in as well (dropout_pair_seed).  i, j = (query, key) for the attention probabilities, (token row b * S + t,
 // column) for the three element-wise sites.  oracle/pfn_oracle.py restates the same integers in numpy.
 // ---------------------------------------------------------------------------------------------
-__host__ __device__ inline unsigned mix32(unsigned h) {
-  h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-  return h;
-}
 __host__ __device__ inline unsigned dropout_site_seed(unsigned long long seed, int layer, int site) {
   return mix32(mix32((unsigned)seed ^ (0x9E3779B1u * (unsigned)(layer * 4 + site + 1))) ^ (unsigned)(seed >> 32));
 }
@@ -407,294 +360,5 @@ int launch_gather_rows(const void* src_bs, void* dst_tb, int S, int B, long row_
 int launch_scatter_rows(const void* src_tb, void* dst_bs, int S, int B, long row_bytes, int sep, int zero_from, hipStream_t s);
 // base[b, s, 0 : width_bytes] = 0 for s < nrows
 int launch_zero_row_prefix(void* base, int S, int B, int nrows, long row_bytes, long width_bytes, hipStream_t s);
-
-// ---- bar distribution (bar.hip) ----------------------------------------------------------------
-struct BarArgs {
-  const float* logits; long ld;  // [R, nbars]
-  const float* y;                // [R]
-  const float* borders;          // [nbars+1]
-  float* nll;                    // [R]
-  float* lse;                    // [R] saved for backward
-  int* bucket;                   // [R] saved for backward
-  long R; int nbars; int full_support;
-  // backward
-  const float* gout; float* dlogits;
-  // mean
-  float* mean_out;
-};
-int launch_bar_nll_fwd(const BarArgs& a, hipStream_t s);
-int launch_bar_nll_bwd(const BarArgs& a, hipStream_t s);
-int launch_bar_mean(const BarArgs& a, hipStream_t s);
-int launch_bar_mean_bwd(const BarArgs& a, hipStream_t s);      // dlogits = gout p (c - mean): mean_out holds the forward's means (read only)
-// posterior summaries and draws (definitions: the header of that section of bar.hip)
-struct BarStatsArgs {
-  const float* logits; long ld;  // [R, nbars]
-  const float* borders;          // [nbars+1]
-  long R; int nbars; int full_support;
-  int K; int kinds[PFN_BAR_STATS_MAX];      // PFN_BAR_STAT_*
-  int has_var, has_icdf;                    // any statistic of that kind among the K
-  const float* args; long arg_ld;           // [K] (arg_ld == 0) or [R, arg_ld]
-  float* out;                               // [R, K] (read by the backward)
-  const float* gout; float* dlogits;        // backward: [R, K], [R, nbars] with row stride ld
-  int n_samples; unsigned long long seed; float* samples;      // draws: [n_samples, R]
-};
-int launch_bar_stats(const BarStatsArgs& a, hipStream_t s);
-int launch_bar_stats_bwd(const BarStatsArgs& a, hipStream_t s);
-int launch_bar_sample(const BarStatsArgs& a, hipStream_t s);
-
-// ---- optimizer (optim.hip) ----------------------------------------------------------------------
-struct AdamArgs {
-  float* p; float* g; float* m; float* v; long n;
-  float lr, beta1, beta2, eps, max_norm, grad_scale;
-  int step;
-  int zero_grad;
-  float* scratch;  // >= 1025 floats; scratch[0] receives the pre-clip global grad norm
-};
-int launch_clip_adam(const AdamArgs& a, hipStream_t s);
-
-// ---- GP prior sampler (gp_prior.hip) ------------------------------------------------------------
-struct GpArgs {
-  float* x;        // [B,S,nf] uniform(0,1) features: generated when seed_x != 0, else taken as input
-  const float* z;  // [B,S] base normals: taken as input when non-null, else generated
-  float* y;        // [B,S] output sample
-  float* K;        // [B,S,S] workspace (f32)
-  const float* lengthscale;  // [B,nf] per dataset / per feature
-  const float* outputscale;  // [B]
-  const float* noise;        // [B]
-  int B, S, nf, kernel;      // kernel: 0 RBF, 1 Matern-5/2
-  unsigned long long seed, offset;
-  int gen_x, gen_z;
-  int* info;                 // [B] 0 ok, else index+1 of the first non-positive pivot
-  // posterior mode (launch_gp_posterior): the same factorisation run as a forward solve  w = L^-1 y_data  -- y holds the
-  // running residual (y_data on entry), w the solution, and every panel subtracts L[rows, panel] w[panel] from the
-  // residual below it where the sampler adds L[rows, panel] z[panel] to the draw
-  float* w;                  // [B,S]; null = sampler mode
-  // scratch behind K (gp_workspace_bytes): the two scaled fp16 planes (hi, lo) of the current outer block's solved panel, written by gp_trsm_wide_kernel and
-  // read by gp_syrk_planes_kernel -- [B][2 planes][16 k-chunks][plane_rows][16] fp16.  null = the trailing update splits the f32 panel itself (gp_syrk_kernel)
-  void* planes;
-  long plane_rows;           // rows allocated per slab (>= S - 256, a multiple of 128)
-};
-int64_t gp_workspace_bytes(int B, int S);      // K [B,S,S] f32 + the plane scratch
-void gp_attach_planes(GpArgs& a);               // points a.planes behind a.K (a workspace of gp_workspace_bytes)
-int launch_gp_sample(const GpArgs& a, hipStream_t s);
-int launch_gp_factor(const GpArgs& a, hipStream_t s);      // the blocked Cholesky (+ y = L z / w = L^-1 y) on an a.K that is already filled
-// Sequential exact-GP predictions from ONE factorisation: for every t, the posterior at x_t given points 0..t-1.
-//   mean[b,t], var[b,t] (with observation noise), nll[b,t] = -log N(y_t; mean, var);  resid_ws / w_ws: [B,S] scratch
-int launch_gp_posterior(const GpArgs& a, const float* y_data, float* nll, float* mean, float* var, hipStream_t s);
-
-// ---- GP hyper-parameter fit (gp_fit.hip): marginal likelihood + hyper-prior, its gradient, the fitted posterior ------
-struct GpFitArgs {
-  const float* x;        // [P,S,nf]
-  const float* y;        // [P,S]
-  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [1,S]); null = S
-  const float* theta;    // [P,nf+3]: log lengthscale_d, log outputscale, log(noise - floor), constant mean
-  const float* prior;    // [8]: a_l, b_l, a_o, b_o, a_n, b_n, noise_floor, 0
-  int P, S, nf, kernel, flags;
-  void* ws;              // gp_fit_workspace_bytes(P, S)
-  float* value;          // [P]
-  float* grad;           // [P,nf+3] or null
-  const float* x_test;   // [P,m,nf]   (predict)
-  int m;
-  float* mean;           // [P,m]
-  float* var;            // [P,m]
-  int32_t* info;         // [P]
-};
-int64_t gp_fit_workspace_bytes(int P, int S);
-int launch_gp_mll_grad(const GpFitArgs& a, hipStream_t s);
-int launch_gp_fit_predict(const GpFitArgs& a, hipStream_t s);
-
-// ---- batched NUTS (gp_mcmc.hip): one gradient evaluation of every chain per launch -----------------
-struct NutsInit {
-  void* ws; int C, D, depth; long ld; int W, N, flags;
-  const int32_t* window_ends;   // HOST array [n_windows]
-  int n_windows, window_start;
-  float step_size, target; unsigned long long seed;
-  const int64_t* chain_ids;     // [C] or null (the chain's index)
-  const float* theta0;          // [C, ld]
-  const float* inv_mass0;       // [C, D] or null (ones)
-  float* trial;                 // [C, ld]
-  int32_t* done_count;
-};
-struct NutsAdvance {
-  void* ws; int C, D, depth, W, N; long ld;
-  const float* value; const float* grad; const int32_t* info; const float* scale; const float* shift;
-  float* trial; float* samples; float* stats; float* warm; int32_t* done_count;
-};
-int64_t nuts_workspace_bytes(int C, int D, int depth);
-int launch_nuts_init(const NutsInit& a, hipStream_t s);
-int launch_nuts_advance(const NutsAdvance& a, hipStream_t s);
-
-// ---- BNN posterior target (bnn_mcmc.hip): potential + gradient of every chain in one launch, and the predictive -----
-struct BnnArgs {
-  const float* x;        // [P,S,F]
-  const float* y;        // [P,S]: class = y > 0.5
-  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [0,S]); null = S
-  const float* theta;    // [P*K, ld]: W1 [H,F], b1 [H], W2 [2,H], b2 [2]
-  long ld;
-  int P, K, S, F, H, activation;      // activation: 0 identity, 1 tanh
-  float* value;          // [P*K]
-  float* grad;           // [P*K, ld] or null; columns >= D are never written
-  const float* x_test;   // [P,m,F]   (predict)
-  int m;
-  float* prob1;          // [P*K, m]
-};
-int launch_bnn_logp_grad(const BnnArgs& a, hipStream_t s);
-int launch_bnn_predict(const BnnArgs& a, hipStream_t s);
-
-// ---- SVI on the BNN (bnn_svi.hip): num_steps steps of (noise -> ELBO gradient -> Adam) for every problem in one launch -----
-struct BnnSviArgs {
-  const float* x;        // [P,S,F]
-  const float* y;        // [P,S]: class = y > 0.5
-  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [0,S]); null = S
-  float* state;          // [P,6,ld]: loc, u (scale = softplus(u)), m_loc, v_loc, m_u, v_u; columns >= D are never touched
-  long ld;
-  int P, S, F, H, activation, K;      // K particles per step
-  long step0;
-  int num_steps;
-  float lr, beta1, beta2, eps;
-  unsigned long long seed;
-  const int64_t* problem_ids;   // [P] or null (the problem's index): the Philox stream
-  float* loss;           // [P,num_steps] or null
-};
-int launch_bnn_svi_steps(const BnnSviArgs& a, hipStream_t s);
-
-// ---- SVGD on the BNN (bnn_svgd.hip): num_steps steps of (grad U -> median bandwidth -> Stein direction -> Adam) on N particles per problem in one launch -----
-struct BnnSvgdArgs {
-  const float* x;        // [P,S,F]
-  const float* y;        // [P,S]: class = y > 0.5
-  const int32_t* n_of;   // [P] rows in use per problem (device; clamped to [0,S]); null = S
-  float* state;          // [P,3,N,ld]: particles, m, v; columns >= D are never touched
-  long ld;
-  int P, S, F, H, activation, N;      // N particles per problem
-  long step0;
-  int num_steps;
-  float lr, beta1, beta2, eps, bandwidth_factor;
-  float* grads;          // [P,N,D] (the workspace) when the state is not resident in LDS, else unused
-  float* potential;      // [P,num_steps] or null
-  float* bandwidth;      // [P,ld] or null
-};
-// particles, gradients and both Adam moments ([4][N][D | 1] f32) stay in LDS for the whole launch when they fit this many bytes; otherwise the state stays in
-// the caller's buffer, the gradients go through the workspace and LDS holds a tile of 64 coordinate columns
-constexpr long BNN_SVGD_STATE_BUDGET = 66560;
-inline bool bnn_svgd_resident(int N, int D) { return 16L * N * (D | 1) <= BNN_SVGD_STATE_BUDGET; }
-inline int64_t bnn_svgd_workspace_bytes(int P, int N, int D) { return bnn_svgd_resident(N, D) ? 0 : (int64_t)P * N * D * 4; }
-int launch_bnn_svgd_steps(const BnnSvgdArgs& a, hipStream_t s);
-
-// ---- Tabular study (tabular.hip): the windows of an eval position, ROC-AUC pair counts, kNN with its grid search -----
-constexpr int TAB_MAX_FEATURES = 1024;      // table columns whose statistics one block keeps in LDS
-struct TabWindowsArgs {
-  const float* X;          // [N,F] the table
-  const float* y;          // [N]
-  const int32_t* starts;   // [W] first row of each window (device); a window that leaves the table is written as NaN, never read
-  long N;
-  int F, F_out, W, bptt, sep, mode;
-  float rescale;
-  float* x_out;            // WITH_TEST [sep+1, W T, F_out], TRAIN_ONLY [bptt, W, F_out]
-  float* y_out;            // WITH_TEST [sep, W T], TRAIN_ONLY [bptt, W]; or null
-};
-int launch_tab_windows(const TabWindowsArgs& a, hipStream_t s);
-int launch_auc_counts(const float* scores, const float* labels, int T, int C, int64_t* counts, hipStream_t s);
-struct KnnCvArgs {
-  const float* train;      // [P,n,F]
-  const float* labels;     // [P,n]: class = label > 0.5
-  const float* test;       // [P,T,F]
-  const int32_t* fold;     // [P,n] in 0 .. 4
-  int P, n, T, F;
-  int32_t* cv_correct;     // [P,5,5]
-  int32_t* test_pos;       // [P,T,5]
-  int32_t* test_nbr;       // [P,T,5]
-};
-// rows of both kinds at an odd stride, then the labels and folds of the train rows: 133,120 bytes at n = T = F = 128
-inline size_t knn_cv_lds_bytes(int n, int T, int F) { return (size_t)(n + T) * (F | 1) * 4 + (size_t)n * 8; }
-int launch_knn_cv(const KnnCvArgs& a, hipStream_t s);
-
-// ---- Logistic regression with its grid search (logistic.hip): every (problem, candidate, fold slot) fit of a call in one launch -----
-struct LogitCvArgs {
-  const float* train;        // [P,n,F]
-  const float* labels;       // [P,n]: class = label > 0.5
-  const float* test;         // [P,T,F]
-  const int32_t* fold;       // [P,n]: the CV test fold of each train row
-  const float* cand_C;       // [NC]
-  const int32_t* cand_kind;  // [NC]: penalty code | PFN_LOGIT_FIT_INTERCEPT
-  int P, n, T, F, NC, n_splits;
-  int32_t* cv_correct;       // [P,NC,5]
-  float* test_z;             // [P,NC,T]
-  int32_t* status;           // [P,NC,6,2] = (exit reason, iterations)
-  float* coef;               // [P,NC,6,F+1] or null
-};
-// the n rows at an odd stride of (F + 1) | 1 floats (features, then a column of ones), H [F+1] rows at the same stride, six vectors over the rows, five over
-// the coordinates, eight words of reduction space: 138,296 bytes at n = F = 128, 37,576 at the study's n = 80, F = 60
-inline size_t logit_cv_lds_bytes(int n, int F) { return ((size_t)(n + F + 1) * ((F + 1) | 1) + 6 * (size_t)n + 5 * (size_t)(F + 1) + 8) * 4; }
-int launch_logit_cv(const LogitCvArgs& a, hipStream_t s);
-
-// ---- GP classifier with its grid search (gpc.hip): the Laplace fit of every (problem, candidate, fold slot) of a call in one launch -----
-struct GpcArgs {
-  const float* theta;        // [P,NC,6,2] = (log c, log l) of every fit
-  const float* train;        // [P,n,F]
-  const float* labels;       // [P,n]: class = label > 0.5
-  const float* test;         // [P,T,F] (predict)
-  const int32_t* fold;       // [P,n]: the CV test fold of each train row
-  int P, n, T, F, NC, n_splits;
-  float* value;              // [P,NC,6] = -Z (lml_grad)
-  float* grad;               // [P,NC,6,2] = -dZ/dtheta (lml_grad)
-  int32_t* status;           // [P,NC,6,2] = (exit reason, Newton iterations)
-  float* cv_f;               // [P,NC,n,2] (predict): (m, e) of every held-out row
-  float* test_f;             // [P,NC,T,2] (predict)
-  float* test_var;           // [P,NC,T] (predict)
-};
-// K, the exponent arguments and the factor (inverted in place for the gradient) at the odd stride n | 1, sixteen vectors over the rows, eight words of reduction space:
-// 159,072 bytes at n = 112, 82,912 at the study's n = 80
-inline size_t gpc_lds_bytes(int n) { return ((size_t)3 * n * (n | 1) + 16 * (size_t)n + 8) * 4; }
-int launch_gpc_lml_grad(const GpcArgs& a, hipStream_t s);
-int launch_gpc_predict(const GpcArgs& a, hipStream_t s);
-
-// ---- BNN prior sampler (mlp_prior.hip) -----------------------------------------------------------
-struct MlpPriorArgs {
-  const float* weights;   // [num_models][Lmax][HP][HP]: layer l transposed ([in][out]), zero padded
-  const float* biases;    // [num_models][Lmax][HP], zero padded
-  const int* model_of;    // [B] model index of each dataset
-  const int* dims;        // [num_models][3] = (num_causes, hidden, num_layers)
-  const float* noise_std; // [num_models]
-  float* causes;          // [B][T][HP]: N(0,1) in the first num_causes columns, written when gen_causes != 0, else input
-  const float* noise;     // optional [B][Lmax-1][T][HP] injected standard normals (else generated)
-  float* y;               // [B][T] last layer, column 0
-  float* hidden;          // optional [B][Lmax-1][T][HP]: the outputs (noise included) of layers 1 .. L-1, the node pool of the causal variant
-  int B, T, HP, Lmax, activation, gen_causes;
-  unsigned long long seed, offset;
-};
-int launch_mlp_prior(const MlpPriorArgs& a, hipStream_t s);
-
-// ---- Stroke prior (stroke_prior.hip): glyphs of the few-shot study, one wave per image ------------------------------------------------------
-struct StrokeRenderArgs {
-  const int32_t* segs;       // [N,8,4] = (x0, y0, x1, y1)
-  const int32_t* n_strokes;  // [N]
-  const int32_t* width;      // [N]
-  const uint8_t* noise;      // [N,size^2] or null (Philox)
-  long N;
-  int size, normalize, vec16;      // vec16: size % 4 == 0 and every image of x 16-byte aligned
-  long image_stride;         // floats between two images of x
-  unsigned long long seed, offset;
-  float* x;
-  uint8_t* raw;              // [N,size^2] or null: before the blur
-  uint8_t* img;              // [N,size^2] or null: after the blur
-};
-struct StrokePriorArgs {
-  const int32_t* labels;     // [B,T]
-  int B, T, C, size, normalize, vec16;
-  int strokes_lo, strokes_hi, len_lo, len_hi, start_lo, start_hi, width_lo, width_hi, max_off, max_toff;
-  unsigned long long seed, offset, first_dataset;
-  float* x;                  // [T,B,size^2]
-  int32_t* cls_n;            // [B,C]
-  int32_t* cls_len;          // [B,C,8]
-  int32_t* cls_start;        // [B,C,8,2]
-  double* cls_dir;           // [B,C,8]
-  int32_t* segs;             // [B,T,8,4]
-  int32_t* width;            // [B,T]
-  uint8_t* raw;              // [B,T,size^2] or null
-  uint8_t* img;              // [B,T,size^2] or null
-  int32_t* status;           // [B]
-};
-int launch_stroke_render(const StrokeRenderArgs& a, hipStream_t s);
-int launch_stroke_prior(const StrokePriorArgs& a, hipStream_t s);
 
 }  // namespace pfn

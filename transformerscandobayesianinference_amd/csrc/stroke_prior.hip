@@ -23,9 +23,39 @@
 // and on bytes a pass is out = (c ww + (l + r) fw + 2^23) >> 24 with ww = floor(2^24 / (2a + 1)) = 16553519 and fw = (2^24 - ww) / 2 = 111848, the missing
 // neighbour at a border replaced by the border pixel.  The largest sum is 255 (ww + 2 fw) + 2^23 = 4,286,578,433: it fits uint32_t and not int.
 #include "pfn_device.h"
-#include "pfn_kernels.h"
+#include "pfn_host.h"
 
 namespace pfn {
+
+struct StrokeRenderArgs {
+  const int32_t* segs;       // [N,8,4] = (x0, y0, x1, y1)
+  const int32_t* n_strokes;  // [N]
+  const int32_t* width;      // [N]
+  const uint8_t* noise;      // [N,size^2] or null (Philox)
+  long N;
+  int size, normalize, vec16;      // vec16: size % 4 == 0 and every image of x 16-byte aligned
+  long image_stride;         // floats between two images of x
+  unsigned long long seed, offset;
+  float* x;
+  uint8_t* raw;              // [N,size^2] or null: before the blur
+  uint8_t* img;              // [N,size^2] or null: after the blur
+};
+struct StrokePriorArgs {
+  const int32_t* labels;     // [B,T]
+  int B, T, C, size, normalize, vec16;
+  int strokes_lo, strokes_hi, len_lo, len_hi, start_lo, start_hi, width_lo, width_hi, max_off, max_toff;
+  unsigned long long seed, offset, first_dataset;
+  float* x;                  // [T,B,size^2]
+  int32_t* cls_n;            // [B,C]
+  int32_t* cls_len;          // [B,C,8]
+  int32_t* cls_start;        // [B,C,8,2]
+  double* cls_dir;           // [B,C,8]
+  int32_t* segs;             // [B,T,8,4]
+  int32_t* width;            // [B,T]
+  uint8_t* raw;              // [B,T,size^2] or null
+  uint8_t* img;              // [B,T,size^2] or null
+  int32_t* status;           // [B]
+};
 
 #define STROKE_HD __host__ __device__ inline
 
@@ -431,15 +461,67 @@ __global__ __launch_bounds__(256) void stroke_images_kernel(StrokePriorArgs a) {
   stroke_draw_image(j, buf[wave], tab, a.size, a.normalize, a.vec16 != 0);
 }
 
-int launch_stroke_render(const StrokeRenderArgs& a, hipStream_t s) {
+static int launch_stroke_render(const StrokeRenderArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(stroke_render_kernel, dim3((unsigned)((a.N + STROKE_WAVES - 1) / STROKE_WAVES)), dim3(256), 0, s, a);
   return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
 
-int launch_stroke_prior(const StrokePriorArgs& a, hipStream_t s) {
+static int launch_stroke_prior(const StrokePriorArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(stroke_classes_kernel, dim3(a.B), dim3(64), 0, s, a);
   if (hipGetLastError() != hipSuccess) return PFN_ERR_LAUNCH;
   hipLaunchKernelGGL(stroke_images_kernel, dim3((unsigned)(((long)a.B * a.T + STROKE_WAVES - 1) / STROKE_WAVES)), dim3(256), 0, s, a);
   return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
+
+static int stroke_size(const char* what, int size) {
+  if (size < 8 || size > 64) return fail(PFN_ERR_UNSUPPORTED, "%s: size %d outside 8 .. 64 (one lane per row, a row's mask in 64 bits)", what, size);
+  return PFN_OK;
+}
+
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+int pfn_stroke_render(const int32_t* segs, const int32_t* n_strokes, const int32_t* width, const uint8_t* noise, int64_t N, int size, int normalize,
+                      int64_t image_stride, uint64_t seed, uint64_t offset, float* x, uint8_t* raw, uint8_t* img, void* stream) {
+  if (const int rc = stroke_size("stroke_render", size)) return rc;
+  if (N < 0 || N > (int64_t)1 << 32 || image_stride < (int64_t)size * size)
+    return fail(PFN_ERR_ARGUMENT, "bad stroke_render arguments (0 <= N %lld <= 2^32, image_stride %lld >= size^2)", (long long)N, (long long)image_stride);
+  if (!segs || !n_strokes || !width || !x || (uintptr_t)segs % 16 || (uintptr_t)n_strokes % 4 || (uintptr_t)width % 4 || (uintptr_t)x % 4)
+    return fail(PFN_ERR_ARGUMENT, "bad stroke_render arguments (segs, n_strokes, width, x not NULL; segs 16-byte, the others 4-byte aligned)");
+  if (N == 0) return PFN_OK;
+  StrokeRenderArgs a{};
+  a.segs = segs; a.n_strokes = n_strokes; a.width = width; a.noise = noise; a.N = N; a.size = size; a.normalize = normalize ? 1 : 0; a.image_stride = image_stride;
+  a.vec16 = (size % 4 == 0 && image_stride % 4 == 0 && (uintptr_t)x % 16 == 0) ? 1 : 0;
+  a.seed = seed; a.offset = offset; a.x = x; a.raw = raw; a.img = img;
+  PFN_TRY(launch_stroke_render(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_stroke_prior_sample(const int32_t* labels, int B, int T, int num_classes, int size, int normalize, int strokes_lo, int strokes_hi, int len_lo, int len_hi,
+                            int start_lo, int start_hi, int width_lo, int width_hi, int max_offset, int max_target_offset, uint64_t seed, uint64_t offset,
+                            uint64_t first_dataset, float* x, int32_t* cls_n, int32_t* cls_len, int32_t* cls_start, double* cls_dir, int32_t* segs, int32_t* width,
+                            uint8_t* raw, uint8_t* img, int32_t* status, void* stream) {
+  if (const int rc = stroke_size("stroke_prior_sample", size)) return rc;
+  if (num_classes < 1 || num_classes > PFN_STROKE_MAX_CLASSES || strokes_hi > PFN_STROKE_MAX_STROKES || width_hi > PFN_STROKE_MAX_WIDTH || len_hi > 1024 ||
+      start_hi > 1024 || max_offset > 1024 || max_target_offset > 1024)
+    return fail(PFN_ERR_UNSUPPORTED, "stroke_prior_sample: num_classes %d outside 1 .. %d, strokes_hi %d above %d, width_hi %d above %d, or len_hi %d, start_hi %d, "
+                "max_offset %d, max_target_offset %d above 1024", num_classes, PFN_STROKE_MAX_CLASSES, strokes_hi, PFN_STROKE_MAX_STROKES, width_hi, PFN_STROKE_MAX_WIDTH,
+                len_hi, start_hi, max_offset, max_target_offset);
+  if (B < 1 || T < 1 || (int64_t)B * T > 0x7fffffffll || strokes_lo < 0 || strokes_lo > strokes_hi || len_lo < 0 || len_lo > len_hi || start_lo < 0 || start_lo > start_hi ||
+      width_lo < 0 || width_lo > width_hi || max_offset < 0 || max_target_offset < 0)
+    return fail(PFN_ERR_ARGUMENT, "bad stroke_prior_sample arguments (B %d, T %d >= 1, B T < 2^31, 0 <= lo <= hi for strokes %d .. %d, len %d .. %d, start %d .. %d, "
+                "width %d .. %d, max_offset %d, max_target_offset %d >= 0)", B, T, strokes_lo, strokes_hi, len_lo, len_hi, start_lo, start_hi, width_lo, width_hi, max_offset,
+                max_target_offset);
+  if (!labels || !x || !cls_n || !cls_len || !cls_start || !cls_dir || !segs || !width || !status || (uintptr_t)segs % 16 || (uintptr_t)cls_dir % 8 ||
+      (uintptr_t)labels % 4 || (uintptr_t)x % 4 || (uintptr_t)cls_n % 4 || (uintptr_t)cls_len % 4 || (uintptr_t)cls_start % 4 || (uintptr_t)width % 4 || (uintptr_t)status % 4)
+    return fail(PFN_ERR_ARGUMENT, "bad stroke_prior_sample arguments (only raw and img may be NULL; segs 16-byte, cls_dir 8-byte, the others 4-byte aligned)");
+  StrokePriorArgs a{};
+  a.labels = labels; a.B = B; a.T = T; a.C = num_classes; a.size = size; a.normalize = normalize ? 1 : 0; a.vec16 = (size % 4 == 0 && (uintptr_t)x % 16 == 0) ? 1 : 0;
+  a.strokes_lo = strokes_lo; a.strokes_hi = strokes_hi; a.len_lo = len_lo; a.len_hi = len_hi; a.start_lo = start_lo; a.start_hi = start_hi; a.width_lo = width_lo;
+  a.width_hi = width_hi; a.max_off = max_offset; a.max_toff = max_target_offset; a.seed = seed; a.offset = offset; a.first_dataset = first_dataset;
+  a.x = x; a.cls_n = cls_n; a.cls_len = cls_len; a.cls_start = cls_start; a.cls_dir = cls_dir; a.segs = segs; a.width = width; a.raw = raw; a.img = img; a.status = status;
+  PFN_TRY(launch_stroke_prior(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+}  // extern "C"

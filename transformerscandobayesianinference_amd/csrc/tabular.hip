@@ -3,9 +3,33 @@
 //   auc_counts_kernel    the integer pair counts ROC-AUC is a ratio of, per column;
 //   knn_cv_kernel        k-nearest-neighbour lists (k = 1 .. 5) of every held-out row of every CV fold and of every test row, one block per window.
 // Nothing here uses atomics on global memory or a workspace; every result is a function of its own window / column / problem alone, bit for bit.
-#include "pfn_kernels.h"
+#include "fold_device.h"      // fold_shapes
 
 namespace pfn {
+
+constexpr int TAB_MAX_FEATURES = 1024;      // table columns whose statistics one block keeps in LDS
+struct TabWindowsArgs {
+  const float* X;          // [N,F] the table
+  const float* y;          // [N]
+  const int32_t* starts;   // [W] first row of each window (device); a window that leaves the table is written as NaN, never read
+  long N;
+  int F, F_out, W, bptt, sep, mode;
+  float rescale;
+  float* x_out;            // WITH_TEST [sep+1, W T, F_out], TRAIN_ONLY [bptt, W, F_out]
+  float* y_out;            // WITH_TEST [sep, W T], TRAIN_ONLY [bptt, W]; or null
+};
+struct KnnCvArgs {
+  const float* train;      // [P,n,F]
+  const float* labels;     // [P,n]: class = label > 0.5
+  const float* test;       // [P,T,F]
+  const int32_t* fold;     // [P,n] in 0 .. 4
+  int P, n, T, F;
+  int32_t* cv_correct;     // [P,5,5]
+  int32_t* test_pos;       // [P,T,5]
+  int32_t* test_nbr;       // [P,T,5]
+};
+// rows of both kinds at an odd stride, then the labels and folds of the train rows: 133,120 bytes at n = T = F = 128
+inline size_t knn_cv_lds_bytes(int n, int T, int F) { return (size_t)(n + T) * (F | 1) * 4 + (size_t)n * 8; }
 
 namespace {
 
@@ -255,12 +279,10 @@ __global__ void __launch_bounds__(256) knn_cv_kernel(KnnCvArgs a) {
   if (threadIdx.x < KNN_K * KNN_FOLDS) a.cv_correct[(long)p * KNN_K * KNN_FOLDS + threadIdx.x] = correct[threadIdx.x];
 }
 
-}  // namespace
-
 int launch_tab_windows(const TabWindowsArgs& a, hipStream_t s) {
   const int rows_out = a.mode == PFN_TAB_NORM_WITH_TEST ? a.sep + 1 : a.bptt;
   const dim3 grid((unsigned)a.W, (unsigned)((rows_out + TAB_ROWS - 1) / TAB_ROWS));
-  if (a.F_out % 4 == 0) tab_windows_kernel<4><<<grid, 256, 0, s>>>(a);      // x_out comes 16-byte aligned (pfn_api.hip checks it)
+  if (a.F_out % 4 == 0) tab_windows_kernel<4><<<grid, 256, 0, s>>>(a);      // x_out comes 16-byte aligned (pfn_tabular_windows checks it)
   else tab_windows_kernel<1><<<grid, 256, 0, s>>>(a);
   return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
 }
@@ -275,4 +297,41 @@ int launch_knn_cv(const KnnCvArgs& a, hipStream_t s) {
   return launch_lds(knn_cv_kernel, allowance, dim3((unsigned)a.P), dim3(256), knn_cv_lds_bytes(a.n, a.T, a.F), s, a);
 }
 
+}  // namespace
 }  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+int pfn_tabular_windows(const float* X, const float* y, const int32_t* starts, int64_t N, int F, int F_out, int W, int bptt, int sep, float rescale, int mode,
+                        float* x_out, float* y_out, void* stream) {
+  if (F < 1 || F > TAB_MAX_FEATURES || F_out < F)
+    return fail(PFN_ERR_UNSUPPORTED, "F %d outside 1 .. %d or F_out %d < F (a block keeps one window's per-feature statistics in LDS)", F, TAB_MAX_FEATURES, F_out);
+  if (mode != PFN_TAB_NORM_WITH_TEST && mode != PFN_TAB_NORM_TRAIN_ONLY) return fail(PFN_ERR_ARGUMENT, "unknown tabular_windows mode %d", mode);
+  if (N < 1 || W < 1 || sep < 1 || sep > bptt || (mode == PFN_TAB_NORM_WITH_TEST && sep == bptt) || bptt > 65536 || !(rescale > 0.f))
+    return fail(PFN_ERR_ARGUMENT, "bad tabular_windows arguments (N %lld >= 1, W %d >= 1, 1 <= sep %d <%s bptt %d <= 65536, rescale %g > 0)", (long long)N, W, sep,
+                mode == PFN_TAB_NORM_WITH_TEST ? "" : "=", bptt, (double)rescale);
+  if (!X || !y || !starts || !x_out) return fail(PFN_ERR_ARGUMENT, "bad tabular_windows arguments (X, y, starts, x_out not NULL)");
+  if ((uintptr_t)x_out % 16) return fail(PFN_ERR_ALIGNMENT, "tabular_windows: x_out must be 16-byte aligned");
+  TabWindowsArgs a{};
+  a.X = X; a.y = y; a.starts = starts; a.N = N; a.F = F; a.F_out = F_out; a.W = W; a.bptt = bptt; a.sep = sep; a.mode = mode; a.rescale = rescale;
+  a.x_out = x_out; a.y_out = y_out;
+  PFN_TRY(launch_tab_windows(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_auc_counts(const float* scores, const float* labels, int T, int C, int64_t* counts, void* stream) {
+  if (T < 1 || T > 4096) return fail(PFN_ERR_UNSUPPORTED, "auc_counts: T %d outside 1 .. 4096 (a block stages one column in LDS)", T);
+  if (C < 1 || !scores || !labels || !counts) return fail(PFN_ERR_ARGUMENT, "bad auc_counts arguments (C %d >= 1, scores, labels, counts not NULL)", C);
+  PFN_TRY(launch_auc_counts(scores, labels, T, C, counts, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_knn_cv(const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F, int32_t* cv_correct, int32_t* test_pos,
+               int32_t* test_nbr, void* stream) {
+  if (const int rc = fold_shapes("knn_cv", "one thread per query, every row in LDS", P, n, 128, T, F, 0, 0, 0, 0,
+                                 train && labels && test && fold && cv_correct && test_pos && test_nbr)) return rc;
+  KnnCvArgs a{};
+  a.train = train; a.labels = labels; a.test = test; a.fold = fold; a.P = P; a.n = n; a.T = T; a.F = F; a.cv_correct = cv_correct; a.test_pos = test_pos; a.test_nbr = test_nbr;
+  PFN_TRY(launch_knn_cv(a, (hipStream_t)stream));
+  return PFN_OK;
+}
+}  // extern "C"

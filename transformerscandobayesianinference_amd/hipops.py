@@ -1,5 +1,7 @@
-"""Tensor-level wrappers around the single-op C-ABI entry points (`pfn_op_*`, include/pfn_hip.h): one kernel launch per call on the
-current stream.  Used by the per-kernel parity tests (tests/test_gpu_ops.py), by bench.py's kernel table and by tools/."""
+"""Tensor-level wrappers around the C-ABI entry points that take plain buffers (include/pfn_hip.h), on the current stream: the single-op entry points of the
+transformer stack (`pfn_op_*`: one kernel launch per call; the per-kernel parity tests tests/test_gpu_ops.py, bench.py's kernel table, tools/) and the
+studies' entry points with their tensor checks -- the GP hyper-parameter fit, NUTS, the BNN's potential, SVI and SVGD step loops, the tabular study's windows,
+AUC counts, kNN, logistic-regression and GP-classifier grid searches, and the stroke prior -- which the study modules (mcmc.py, tabular.py, priors/) build on."""
 import ctypes
 import math
 

@@ -106,7 +106,8 @@ const char* pfn_last_error_string(void);
  * PFN_TUNE_GEMM_NT_KERNEL: 0 automatic (default), 1 always the 128x128 register-staged
  * kernel, 2 the 256x256 LDS-DMA kernel whenever the shape is legal for it, 3 the 128x256 one.
  * PFN_TUNE_FUSE_LNBWD: 1 (default) the stack backward runs LayerNorm backward inside the data-gradient GEMMs that feed it
- * (pfn_op_gemm_lnbwd), 0 as separate kernels.  (Key 3, the persistent NT GEMM of round 5, is gone from the product library: csrc/experiments/.) */
+ * (pfn_op_gemm_lnbwd), 0 as separate kernels.  (Key 3, the persistent NT GEMM of round 5, is gone from the product library: csrc/experiments/.)
+ * Retired numbers (3, 10, 11) are refused as unknown keys and are not given to a new key. */
 enum { PFN_TUNE_GEMM_NT_KERNEL = 0,
        PFN_TUNE_GEMM_TN_WRAP = 1, /* profiling only: > 0 makes the grouped TN kernel re-read its first `value` token rows (wrong results, cache-resident operands) */
        PFN_TUNE_FUSE_LNBWD = 2,
@@ -117,9 +118,6 @@ enum { PFN_TUNE_GEMM_NT_KERNEL = 0,
        PFN_TUNE_FUSE_DELTA = 9,    /* 1 (default): on the full-sequence layers of the bf16 stack the attention backward's delta = rowsum(dO . O) is taken in the epilogue of the GEMM that
                                     * produces dO (f32 atomics into a zeroed scratch: two addends per element at head dim 128); 0: a pass of its own over dO and O (attn_delta_kernel) */
        PFN_TUNE_GEMM_LN_ROWS = 7,  /* 1: the LayerNorm-fused GEMMs at emsize 512 run on 64-row tiles, two workgroups per CU (gemm.hip g_ln_rows64); 0 (default): 128-row tiles */
-       PFN_TUNE_ATTN_BWD_GROUP = 10, /* > 0: the attention backward's key-block / query-block pass pair runs for that many datasets at a time, every group through the front of
-                                      * the dS^T scratch (which then stays in the 256 MB memory-side cache between the two passes); 0 (default): one pair per call */
-       PFN_TUNE_WGRAD_SPLITS = 11,   /* > 0: token-axis splits of the grouped weight-gradient launch where the stack leaves them automatic; 0 (default): the occupancy rule */
        PFN_TUNE_WGRAD_WAVES = 14,       /* waves per 256 x 256 tile of the grouped weight-gradient launch: 8 (128 x 64 each) or 4 (128 x 128 each, the whole register file per wave) */
        PFN_TUNE_LOSS_SCALE_TARGET = 15, /* PFN_PREC_FP16 backward: log2 of the value max|dlogits| is scaled to (power-of-two loss scale chosen on the device per call; default 2,
                                          * range -8 .. 12).  16 - target binades of headroom for what the chain adds; overflowing elements saturate at +-65504 */

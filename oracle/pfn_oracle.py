@@ -90,8 +90,8 @@ ROUNDING_SITES = {
     'xaug':      ('Rv', 'emb_t',       'the embedding weight gradient reads x | y from xaug_t :763-764 -> launch_gemm_tn :1321 (the forward embeds the f32 inputs)'),
     'emb_grad':  ('Rg', 'emb_t',       'd(src) leaves layer 0 in gA_t: layer_backward_dx out_f32 = (l == 0 && !emb_t) :1306'),
     'qkv':       ('R',  None,          'q|k|v projection out_t = a.qkv :792 (keys after the f32 shift, EPI_ROWSHIFT :800); gradient at.dqkv = a.dqkv_t :1296'),
-    'P':         ('Rv', None,          'softmax numerators enter P.V and dO^T.P as MFMA operands: attention.hip :13-14 ("P and dS go from the accumulator straight into the operand slots" :791)'),
-    'dS':        ('Rg', None,          'dS = P (dP - delta) in operand precision, the values dK, dQ consume: attention.hip :790-792'),
+    'P':         ('Rv', None,          'softmax numerators enter P.V and dO^T.P as MFMA operands: attention.hip :13-14 ("P and dS go from the accumulator straight into the operand slots" :744)'),
+    'dS':        ('Rg', None,          'dS = P (dP - delta) in operand precision, the values dK, dQ consume: attention.hip :743-745'),
     'ctx':       ('R',  None,          'attention output at.ctx = a.ctx :814; its gradient d(ctx) out_t = dctx_t / top_dctx_t :1263-1264'),
     'y_grad':    ('Rg', None,          'LayerNorm-input gradients dy2_t :545 :528, dy1_t :524 :564 (launch_layernorm_bwd dx_t / GemmLNB::dx_t)'),
     'Y':         ('Rv', 'y16',         'pre-LayerNorm sums in fp16 inside the fused GEMMs, g.y16 :393 :421: the next residual add and the LayerNorm backward read the rounded sum'),

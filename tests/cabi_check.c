@@ -53,6 +53,7 @@ int main(int argc, char** argv) {
   CHECK(top_rows(&d, 32, 2000, 1604, 0) == (int64_t)(2000 - 1604) * 32);
   CHECK(set_tuning(PFN_TUNE_TOP_LAYER_TEST_ROWS, 1) == PFN_OK && default_schedule() == 0);
   CHECK(set_tuning(12345, 0) < 0);
+  CHECK(set_tuning(10, 4) < 0 && set_tuning(11, 2) < 0);      /* retired key numbers stay refused */
   /* error path: head dim 100 (the reference's train() default emsize 200 / nhead 2) is refused with a message, not computed wrongly */
   d.emsize = 200; d.nhead = 2; d.nhid = 200;
   CHECK(param_count(&d) < 0 && strstr(last_error(), "head dim") != 0);

@@ -10,7 +10,7 @@ from transformerscandobayesianinference_amd import _hip
 if os.environ.get('PFN_LIB'):
     _hip.LIB_PATH = os.path.abspath(os.environ['PFN_LIB'])
 ap = argparse.ArgumentParser(); ap.add_argument('--batch', type=int, default=16)
-ap.add_argument('--tune', default='', help='key=value,... for pfn_set_tuning (14=4: four waves of 128 x 128; 11=N: token splits)')
+ap.add_argument('--tune', default='', help='key=value,... for pfn_set_tuning (14=4: four waves of 128 x 128)')
 a = ap.parse_args()
 for kv in a.tune.split(','):
     if kv:

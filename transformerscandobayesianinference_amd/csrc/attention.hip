@@ -142,50 +142,6 @@ PFN_DEV AttnBlock attn_block_ragged_last(int nblk, int nfull, int H) {
   return o;
 }
 
-// Profiling builds only (tools/exp_attn_variants.py): -DPFN_ATTN_ABLATE=<bits> drops, in every main loop, the
-// global tile requests (1), the LDS tile writes (2), the barrier (4).  Results are then garbage; the timing
-// differences price the three parts (MI355X, north-star shape: requests 9-14 %, writes 6-7 %, barrier 4 %).
-#ifndef PFN_ATTN_ABLATE
-#define PFN_ATTN_ABLATE 0
-#endif
-constexpr int ABL = PFN_ATTN_ABLATE;
-// ... and -DPFN_KV_ABLATE=<bits> in the backward key-block pass: no dS^T store (1), the transposed fragments of the dV / dK
-// products read once instead of four times (2), V row fragments not read (4), exponentials replaced by a multiply (8), the Q / dO row
-// fragments read for the first k-steps only (16)
-#ifndef PFN_KV_ABLATE
-#define PFN_KV_ABLATE 0
-#endif
-// fragment prefetch depth (k-steps of 16) of the two row-operand chains of the key-block pass: how far the LDS reads of the Q / dO (and V)
-// row fragments run ahead of their MFMAs.  Round 2 ran both at 2 ("no register left for more" -- true of the dP chain only)
-// s_setprio experiments (guide T5 / MI355X_MICROARCH.md "two waves per SIMD"): bit 0 forward Q.K cluster at priority 1, bit 1 forward
-// waves 4..7 at static priority 1, bit 2 key-block pass S / dP chains, bit 3 key-block pass dV / dK cluster
-#ifndef PFN_ATTN_PRIO
-#define PFN_ATTN_PRIO 0
-#endif
-constexpr int PRIO = PFN_ATTN_PRIO;
-#ifndef PFN_KV_SPLIT_D256
-#define PFN_KV_SPLIT_D256 0
-#endif
-// key-block pass (operand precision 2 bytes): ONE LDS image per Q / dO tile instead of a row image and a column image (BwdKvCfg)
-#ifndef PFN_KV_ONE_IMAGE
-#define PFN_KV_ONE_IMAGE 1
-#endif
-#ifndef PFN_KV_THREE_BUFFERS
-#define PFN_KV_THREE_BUFFERS 1
-#endif
-#ifndef PFN_KV_PD_S
-#define PFN_KV_PD_S 2
-#endif
-#ifndef PFN_KV_PD_DP
-#define PFN_KV_PD_DP 2
-#endif
-constexpr int KVABL = PFN_KV_ABLATE;
-// ... and -DPFN_DQ_ABLATE=1 in the query-block pass: the stored dS^T is not fetched (round 5: with PFN_KV_ABLATE=1 the whole dS^T round trip is gone -- results are
-// garbage, the step time is the UPPER bound of what any form of the backward without that round trip could gain before paying for its own extra work)
-#ifndef PFN_DQ_ABLATE
-#define PFN_DQ_ABLATE 0
-#endif
-constexpr int DQABL = PFN_DQ_ABLATE;
 typedef __attribute__((address_space(3))) void lvoid_t;
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
@@ -335,7 +291,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
   // initial state: the self key for test rows, empty for train rows.  The self K / V rows are only fetched by waves
   // that hold a test row at all (wave-uniform branch): 7 of 8 waves at the north star skip 24 loads per lane.
   const bool is_test = CACHE || qc >= sep;
-  const bool wave_has_test = CACHE ? blockIdx.z == 0 : !(ABL & 8) && wg.blk * C::QBLK + wave * 32 + 31 >= sep;   // ABL 8: profiling without the self-key work
+  const bool wave_has_test = CACHE ? blockIdx.z == 0 : wg.blk * C::QBLK + wave * 32 + 31 >= sep;
   float m = -1e30f, lsum = 0.f;
   f32x16 o[CV::NDB];
 #pragma unroll
@@ -385,6 +341,8 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
   // tile max exceeds it by more than RESCALE_THR (log2 units): P stays below 2^THR, which neither the bf16
   // operand rounding (relative) nor the f32 sums notice, and the O-wide rescale runs on the first tile and then
   // almost never.  The key mask only runs on the ragged last tile.
+  // What the parts of a tile cost at the north-star shape (timed with each taken out, profiles/r01_attention_sq_counters.txt): the global tile
+  // requests 9-14 %, the LDS tile writes 6-7 %, the barrier 4 %.
   constexpr int NPF = C::KVB / 16;
   Frag<T> pf[NPF];                       // P_{t-1}, in the slot order the P.V MFMA consumes
   auto pv_prev = [&](int vb) __attribute__((always_inline)) {
@@ -396,7 +354,6 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
         o[db] = mma32(load_frag_tr_p<T, CV::CS, 2>(vt, c * 16, db * 32), pf[c], o[db]);
   };
   int vb_prev = 0, vb_cur = 0;           // V buffer of tile t-1 / tile t
-  if constexpr (PRIO & 2) { if (__builtin_amdgcn_readfirstlane(wave) >= 4) __builtin_amdgcn_s_setprio(1); }
   for (int t = 0; t < ntiles; ++t) {
     const int k0 = t * C::KVB;
     // all K fragments of the tile are requested before anything else: the LDS round trip (>100 cycles under load)
@@ -413,12 +370,10 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
     for (int kb = 0; kb < C::NKB; ++kb)
 #pragma unroll
       for (int r = 0; r < 16; ++r) st[kb][r] = 0.f;
-    if constexpr (PRIO & 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kk = 0; kk < C::NKK; ++kk)
 #pragma unroll
       for (int kb = 0; kb < C::NKB; ++kb) st[kb] = mma32(kfr[kk][kb], qf[kk], st[kb]);
-    if constexpr (PRIO & 1) __builtin_amdgcn_s_setprio(0);
     PFN_PIN_LDS_MFMA();
     // Global -> LDS staging, one tile ahead with the loads in flight across the barrier: the staged registers hold
     // tile t+1 (requested one iteration ago); they are written to the buffers tile t-1 has released -- the wait for
@@ -426,11 +381,9 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
     // registers are stale and go to buffers nobody reads again (a branch here would split the block and strand the
     // exponentials behind the P.V MFMAs).
     const int vb_next = vb_cur == NVB - 1 ? 0 : vb_cur + 1;   // the slot tile t-3 has released
-    if (!(ABL & 2)) {
-      sk.template commit_p<C::RS>(Kt((t + 1) & 1));
-      sv.template commit_p<CV::CS>(Vt(vb_next));
-    }
-    if (!(ABL & 1) && t + 2 < ntiles) {
+    sk.template commit_p<C::RS>(Kt((t + 1) & 1));
+    sv.template commit_p<CV::CS>(Vt(vb_next));
+    if (t + 2 < ntiles) {
       const long k2 = k0 + 2 * C::KVB;
       sk.issue(Ksrc + k2 * kld, kld, sep - (int)k2, D);
       sv.issue(Vsrc + k2 * kld, kld, sep - (int)k2, DV);
@@ -465,7 +418,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
           for (int e = 0; e < 8; ++e) pf[c].set(e, frag_get(pf[c], e) * alpha);
       }
     }
-    if (lag && !(ABL & 4)) __syncthreads();     // the lagging waves' barrier of this tile (ping-pong, above)
+    if (lag) __syncthreads();     // the lagging waves' barrier of this tile (ping-pong, above)
     if (t > 0) {
       // one basic block: exponentials of tile t + P.V MFMAs of tile t-1
       float rsum = 0.f;
@@ -502,7 +455,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_fwd_kernel(AttnArgs 
     for (int c = 0; c < NPF; ++c) pf[c] = acc_to_frag<T>(st[c >> 1], c & 1);
     vb_prev = vb_cur;
     vb_cur = vb_next;
-    if (!lag && !(ABL & 4)) __syncthreads();
+    if (!lag) __syncthreads();
   }
   if (ntiles > 0) pv_prev(vb_prev);
 
@@ -827,7 +780,7 @@ template <typename T, int D> struct BwdKvCfg {
   // q sits in LDS row perm(q) = 4 (q & 3) + ((q >> 2) & 3) + 16 (q >> 4) (the two 2-bit fields of the row index swapped) under the ROW padding:
   // the transposed read's four consecutive queries are then rows 4 apart = 16 x odd dwords apart, and the row read's 16-lane groups
   // ({0-3, 12-15, 20-27}, ...) still cover every residue mod 16.  Both stay conflict-free; the tile costs half the DMA pieces and half the LDS.
-  static constexpr bool ONE = PFN_KV_ONE_IMAGE && sizeof(T) == 2;
+  static constexpr bool ONE = sizeof(T) == 2;
   // Q / dO tiles go global -> LDS by LDS-DMA in 1-KiB pieces (64 lanes x 16 bytes, lane-linear in LDS): every image is
   // allocated in whole pieces; piece p of an image holds its bytes [1024 p, 1024 p + 1024)
   static constexpr int NPR = (QB * C::RS + 1023) / 1024, NPC = ONE ? 0 : (QB * C::CS + 1023) / 1024;   // pieces of a row / col image
@@ -841,29 +794,25 @@ template <typename T, int D> struct BwdKvCfg {
   // (transposed reads, 16 MFMAs) instead of at the tile's end, so the two waves of a SIMD run half a tile apart and one's vector-heavy half overlaps the
   // other's matrix-heavy half (the forward's schedule, attn_fwd_kernel).  The lagging waves still read tile t's buffer while the leading ones request
   // tile t+2: that request goes to the THIRD buffer (last read in tile t-1, which every wave has left at the barrier in front of the request).
-  static constexpr int NBUF = (PFN_KV_THREE_BUFFERS && ONE && C::NW == 8) ? 3 : 2;
+  static constexpr int NBUF = (ONE && C::NW == 8) ? 3 : 2;
+  // fragment prefetch depth (k-steps of 16) of the two row-operand chains: how far the LDS reads of the Q / dO (and V) row fragments run ahead of their MFMAs
+  static constexpr int PD = 2;
   // the lanes' DMA source offsets (one per piece of the wave) live in an LDS table when there is room (every shipped shape):
   // recomputing them per tile costs ~20 vector instructions per piece, keeping them in registers costs registers this kernel
   // does not have
-  // head dim 256 ran dV and dK as two passes in round 2 (attn_bwd_kv_kernel MODE 2, then MODE 1: six product units): the single pass
-  // spilled 116 bytes per lane.  Round 3: with the transposed fragments of the dV / dK products held one group of four at a time and
-  // P unpacked from its packed registers the single pass fits the register file (508 VGPRs, no scratch) -- 64 MFMAs per tile instead
-  // of 80, one sweep over the Q / dO tiles instead of two.  -DPFN_KV_SPLIT_D256=1 restores the two passes (A/B builds).
-  static constexpr bool SPLIT = PFN_KV_SPLIT_D256 && C::NW == 4 && D > 128;
   static constexpr bool PVLDS = VIMG + NBUF * BUF + NI * C::NT * 4 <= 160 * 1024;
   static constexpr int PVTAB = PVLDS ? NI * C::NT * 4 : 0;
   static constexpr int LDS = VIMG + NBUF * BUF + PVTAB;
 };
 
-// MODE 0: dK and dV in one pass.  Head dim 256 cannot hold both accumulators beside the K and V fragments even in the whole
-// register file without copies and spills inside the loop, so it runs the pass twice: MODE 2 (S, dV) then MODE 1 (S, dP,
-// dK, dS^T) -- six product units for the backward instead of five.
-template <typename T, int D, int MODE, bool DROP = false>
+// dK and dV in ONE pass at every head dim.  At head dim 256 both accumulators fit the whole register file beside the K and V fragments
+// (508 VGPRs, no scratch) because the transposed fragments of the dV / dK products are held one group of four at a time and P is unpacked
+// from its packed registers: 64 MFMAs per tile and one sweep over the Q / dO tiles (two passes, dV then dK, take 80 and two sweeps).
+template <typename T, int D, bool DROP = false>
 __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnArgs a) {
   operand_store_mode<T>();
   using C = AttnCfg<T, D>;
   using K = BwdKvCfg<T, D>;
-  constexpr bool DO_DK = MODE != 2, DO_DV = MODE != 1;
   constexpr int QB = K::QB;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   LdsPtr smem = lds_cast(smem_raw);
@@ -876,7 +825,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
 
   // (ragged batch: the grid has ceil(max position / 256) blocks per (dataset, head); a dataset's blocks past ITS position leave at once)
   const AttnBlock wg = a.sep_of ? attn_block((a.sep + C::QBLK - 1) / C::QBLK, a.H) : attn_block_ragged_last((a.sep + C::QBLK - 1) / C::QBLK, a.sep / C::QBLK, a.H);
-  const int b = wg.b + a.b0, hd = wg.hd;      // (b0: this launch's first dataset, AttnArgs)
+  const int b = wg.b, hd = wg.hd;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, h = lane >> 5, li = lane & 31;
   const long rs = 3L * a.E;
   const T* base = reinterpret_cast<const T*>(a.qkv) + (long)b * a.S * rs;
@@ -907,28 +856,28 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
   // dS^T of this (dataset, head): 32 x 32 blocks, block (key / 32, query / 32) at ((key / 32) * (ds_ld / 32) + query / 32) blocks
   // (store_frag_pair_blocked); the wave owns block row key / 32
   constexpr int DSBLK = 32 * 32;   // elements per block
-  T* dsT = reinterpret_cast<T*>(a.ds) + ((long)(b - a.b0) * a.H + hd) * a.ds_rows * a.ds_ld + (long)(key0 / 32 + wave) * (a.ds_ld / 32) * DSBLK;
+  T* dsT = reinterpret_cast<T*>(a.ds) + ((long)b * a.H + hd) * a.ds_rows * a.ds_ld + (long)(key0 / 32 + wave) * (a.ds_ld / 32) * DSBLK;
   const bool ds_row_live = key0 + wave * 32 < a.ds_rows;   // wave-uniform: this wave's block row exists in the buffer
 
-  Frag<T> kf[C::NKK], vf[(K::VLDS || !DO_DK) ? 1 : C::NKK];
+  Frag<T> kf[C::NKK], vf[K::VLDS ? 1 : C::NKK];
 #pragma unroll
   for (int kk = 0; kk < C::NKK; ++kk) {
     kf[kk] = load_frag_global<T>(Kp + (long)kc * rs + kk * 16 + 8 * h);
-    if constexpr (!K::VLDS && DO_DK) vf[kk] = load_frag_global<T>(Vp + (long)kc * rs + kk * 16 + 8 * h);
+    if constexpr (!K::VLDS) vf[kk] = load_frag_global<T>(Vp + (long)kc * rs + kk * 16 + 8 * h);
   }
-  if constexpr (K::VLDS && DO_DK) {   // the workgroup's V rows -> LDS row image (rows >= S read as zero)
+  if constexpr (K::VLDS) {   // the workgroup's V rows -> LDS row image (rows >= S read as zero)
     TileStageBuf<T, C::QBLK, C::RB, C::NT> sv;
     sv.init((int)(rs * sizeof(T)));
     sv.issue(make_rsrc(Vp, ((long)(a.S - 1) * rs + D) * (long)sizeof(T)), key0 * (int)(rs * sizeof(T)));
     sv.template commit_p<C::RS>(Vimg());
   }
-  f32x16 dk[DO_DK ? C::NDB : 1], dv[DO_DV ? C::NDB : 1];
+  f32x16 dk[C::NDB], dv[C::NDB];
 #pragma unroll
   for (int db = 0; db < C::NDB; ++db)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      if constexpr (DO_DK) dk[db][r] = 0.f;
-      if constexpr (DO_DV) dv[db][r] = 0.f;
+      dk[db][r] = 0.f;
+      dv[db][r] = 0.f;
     }
 
   const int ntiles = (a.S + QB - 1) / QB;
@@ -1008,11 +957,11 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
   stage_stats(0, t0 * QB);
   dma_wait_all();
   __syncthreads();
-  if (!(ABL & 1) && t0 + 1 < ntiles) {     // the second tile -> the second buffer; from here on a tile's successor-but-one is requested at its end
+  if (t0 + 1 < ntiles) {     // the second tile -> the second buffer; from here on a tile's successor-but-one is requested at its end
     dma(1, t0 + 1);
     stage_stats(1, (t0 + 1) * QB);
   }
-  constexpr int DST_TILE_WRITES = DO_DK && !(KVABL & 1) ? (sizeof(T) == 2 ? 2 : 4) : 0;   // store instructions of one tile's dS^T per wave
+  constexpr int DST_TILE_WRITES = sizeof(T) == 2 ? 2 : 4;   // store instructions of one tile's dS^T per wave
   bool stored = false;                // this wave's dS^T stores of the previous tile may still be in flight
 
   auto tile = [&](auto buf_c, int t) {
@@ -1025,8 +974,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
     // Register plan (head dim 128, bf16): 160 registers are pinned (K fragments, dK, dV); S and dP take 32 more; every operand
     // stream therefore runs only PD k-steps ahead of its MFMAs and the two products run one after the other, the second
     // one's first fragments requested under the first one's tail.
-    constexpr int PD = C::NKK < PFN_KV_PD_S ? C::NKK : PFN_KV_PD_S;       // S = Q K^T chain
-    constexpr int PD2 = C::NKK < PFN_KV_PD_DP ? C::NKK : PFN_KV_PD_DP;    // dP = dO V^T chain
+    constexpr int PD = C::NKK < K::PD ? C::NKK : K::PD;      // both chains: S = Q K^T and dP = dO V^T
     // rows of the S / dP tiles are queries: acc_row(r) = 8*(r>>2) + 4h + (r&3)
     Frag<T> pf0, pf1;
     Frag<T> df0, df1;
@@ -1038,8 +986,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
     // one barrier per tile and wave: at the tile's end, or (lagging waves of the ping-pong schedule) between its two halves.  Either way it is passed
     // with this wave's LDS reads done and its pieces of tile t+1 landed (vmcnt = the dS^T stores issued behind them: loads and stores retire in order)
     auto sync_tile = [&]() __attribute__((always_inline)) {
-      if (ABL & 4) dma_wait_all();
-      else if (stored) wait_vm_barrier<DST_TILE_WRITES>();
+      if (stored) wait_vm_barrier<DST_TILE_WRITES>();
       else wait_vm_barrier<0>();
     };
     if (wave_live) {
@@ -1051,14 +998,12 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
 #pragma unroll
       for (int kk = 0; kk < PD; ++kk) qfr[kk] = load_frag_row_p<T, C::RS>(qr, lip, kk * 16);
       PFN_PIN_LDS_MFMA();
-      if constexpr (PRIO & 4) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int kk = 0; kk < C::NKK; ++kk) {
-        if (kk + PD < C::NKK) qfr[kk + PD] = (KVABL & 16) ? qfr[0] : load_frag_row_p<T, C::RS>(qr, lip, (kk + PD) * 16);
+        if (kk + PD < C::NKK) qfr[kk + PD] = load_frag_row_p<T, C::RS>(qr, lip, (kk + PD) * 16);
         s = mma32(qfr[kk], kf[kk], s);
         PFN_PIN_LDS_MFMA();
       }
-      if constexpr (PRIO & 4) __builtin_amdgcn_s_setprio(0);
       // P = exp2(S scale - lse), straight into operand precision: S is dead before the dP chain starts (register plan above)
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
@@ -1067,7 +1012,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * rg + e;
           const float arg = __builtin_fmaf(s[r], scale_log2, -l2[e]);
-          s[r] = (KVABL & 8) ? arg : fast_exp2(arg);
+          s[r] = fast_exp2(arg);
         }
       }
       if constexpr (DROP) {
@@ -1082,25 +1027,24 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
       // see through the packing, hipcc re-rounds every element from the f32 value with a second, single-element conversion + shift
       if constexpr (sizeof(T) == 2) asm volatile("" : "+v"(pf0.v), "+v"(pf1.v));
     }
-    if constexpr (DO_DK) {
+    {
       f32x16 dp;
 #pragma unroll
       for (int r = 0; r < 16; ++r) dp[r] = 0.f;
       Frag<T> ofr[C::NKK], vfr[K::VLDS ? C::NKK : 1];
 #pragma unroll
-      for (int kk = 0; kk < PD2; ++kk) {
+      for (int kk = 0; kk < PD; ++kk) {
         ofr[kk] = load_frag_row_p<T, C::RS>(orow, lip, kk * 16);
-        if constexpr (K::VLDS && !(KVABL & 4)) vfr[kk] = load_frag_row_p<T, C::RS>(Vimg(), wave * 32 + li, kk * 16);
+        if constexpr (K::VLDS) vfr[kk] = load_frag_row_p<T, C::RS>(Vimg(), wave * 32 + li, kk * 16);
       }
       PFN_PIN_LDS_MFMA();
 #pragma unroll
       for (int kk = 0; kk < C::NKK; ++kk) {
-        if (kk + PD2 < C::NKK) {
-          ofr[kk + PD2] = (KVABL & 16) ? ofr[0] : load_frag_row_p<T, C::RS>(orow, lip, (kk + PD2) * 16);
-          if constexpr (K::VLDS && !(KVABL & 4)) vfr[kk + PD2] = load_frag_row_p<T, C::RS>(Vimg(), wave * 32 + li, (kk + PD2) * 16);
+        if (kk + PD < C::NKK) {
+          ofr[kk + PD] = load_frag_row_p<T, C::RS>(orow, lip, (kk + PD) * 16);
+          if constexpr (K::VLDS) vfr[kk + PD] = load_frag_row_p<T, C::RS>(Vimg(), wave * 32 + li, (kk + PD) * 16);
         }
-        if constexpr (K::VLDS && (KVABL & 4)) dp = mma32(ofr[kk], ofr[kk], dp);
-        else if constexpr (K::VLDS) dp = mma32(ofr[kk], vfr[kk], dp);
+        if constexpr (K::VLDS) dp = mma32(ofr[kk], vfr[kk], dp);
         else dp = mma32(ofr[kk], vf[kk], dp);
         PFN_PIN_LDS_MFMA();
       }
@@ -1135,10 +1079,9 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
     // is live: the next step's are requested right behind the MFMAs that consume the current ones (head dim 256 takes its 8 blocks
     // as two groups of 4 -- 16 registers instead of 32, which is what the single-pass variant lacked).
     constexpr int CG = C::NDB > 4 ? 4 : C::NDB, NG = C::NDB / CG;
-    constexpr int P0 = DO_DV ? 0 : 2, P1 = DO_DK ? 4 : 2;       // products [P0, P1)
     Frag<T> cf[CG];
     auto request = [&](int step) __attribute__((always_inline)) {
-      const int prod = P0 + step / NG, grp = step % NG;
+      const int prod = step / NG, grp = step % NG;
       const lds_char* img = prod < 2 ? oc : qc;
 #pragma unroll
       for (int c = 0; c < CG; ++c) {
@@ -1149,19 +1092,17 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
     request(0);
     PFN_PIN_LDS_MFMA();
 #pragma unroll
-    for (int step = 0; step < (P1 - P0) * NG; ++step) {
-      const int prod = P0 + step / NG, grp = step % NG;
-      if constexpr (PRIO & 8) { if (prod == 2 && grp == 0) __builtin_amdgcn_s_setprio(1); }
+    for (int step = 0; step < 4 * NG; ++step) {
+      const int prod = step / NG, grp = step % NG;
 #pragma unroll
       for (int c = 0; c < CG; ++c) {
         const int db = grp * CG + c;
-        if (prod < 2) { if constexpr (DO_DV) dv[db] = mma32(cf[c], prod == 0 ? pf0 : pf1, dv[db]); }
-        else { if constexpr (DO_DK) dk[db] = mma32(cf[c], prod == 2 ? df0 : df1, dk[db]); }
+        if (prod < 2) dv[db] = mma32(cf[c], prod == 0 ? pf0 : pf1, dv[db]);
+        else dk[db] = mma32(cf[c], prod == 2 ? df0 : df1, dk[db]);
       }
-      if (step + 1 < (P1 - P0) * NG && !(KVABL & 2)) request(step + 1);
+      if (step + 1 < 4 * NG) request(step + 1);
       PFN_PIN_LDS_MFMA();
     }
-    if constexpr (PRIO & 8) __builtin_amdgcn_s_setprio(0);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) { df0.set(e, 0.f); df1.set(e, 0.f); }    // its dS^T rows (if the dQ pass reads them at all) are zeros
@@ -1172,22 +1113,20 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
     // consumed) -- and the wait for tile t+1 one tile earlier is vmcnt(stores of the previous tile), which leaves those stores two
     // tile times to be acknowledged instead of stalling every tile on them (with them in front of the DMA: 70 us of 372).
     if (!lag) sync_tile();
-    if (!(ABL & 1) && t + 2 < ntiles) {
+    if (t + 2 < ntiles) {
       constexpr int NXT = (BUF + 2) % K::NBUF;      // two buffers: this tile's own (free behind the barrier); three: the one tile t-1 used
       dma(NXT, t + 2);
       stage_stats(NXT, (t + 2) * QB);
     }
     // keys >= sep of a block row the dQ pass reads (rows < ds_rows) leave as zeros: that pass does not mask rows
-    if constexpr (DST_TILE_WRITES > 0) {
-      if (!wave_all_valid) {      // last key block only (wave-uniform)
-        if (!kvalid) {
+    if (!wave_all_valid) {      // last key block only (wave-uniform)
+      if (!kvalid) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) { df0.set(e, 0.f); df1.set(e, 0.f); }
-        }
+        for (int e = 0; e < 8; ++e) { df0.set(e, 0.f); df1.set(e, 0.f); }
       }
-      if (ds_row_live) store_frag_pair_blocked<T>(dsT + (long)t * DSBLK, df0, df1, li, h, true);
-      stored = ds_row_live;
     }
+    if (ds_row_live) store_frag_pair_blocked<T>(dsT + (long)t * DSBLK, df0, df1, li, h, true);
+    stored = ds_row_live;
   };
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -1212,16 +1151,12 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_kv_kernel(AttnAr
 #pragma unroll
     for (int db = 0; db < C::NDB; ++db) {
       float v[16];
-      if constexpr (DO_DK) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = dk[db][r] * scale;
-        store_row_block<T>(outk + db * 32, v, h2, kvalid);
-      }
-      if constexpr (DO_DV) {
+      for (int r = 0; r < 16; ++r) v[r] = dk[db][r] * scale;
+      store_row_block<T>(outk + db * 32, v, h2, kvalid);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = dv[db][r] * dscale;
-        store_row_block<T>(outv + db * 32, v, h2, kvalid);
-      }
+      for (int r = 0; r < 16; ++r) v[r] = dv[db][r] * dscale;
+      store_row_block<T>(outv + db * 32, v, h2, kvalid);
     }
   }
 }
@@ -1288,7 +1223,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_dq_kernel(AttnAr
 
   AttnBlock wg = attn_block((a.S + C::QBLK - 1) / C::QBLK - a.q_begin / C::QBLK, a.H);
   wg.blk += a.q_begin / C::QBLK;    // (q_begin: AttnArgs; the launcher zero-fills the dQ rows below it)
-  wg.b = a.b0 + a.bg - 1 - wg.b;    // most recently written dS^T first (see above); datasets [b0, b0 + bg) of this launch
+  wg.b = a.B - 1 - wg.b;            // most recently written dS^T first (see above)
   wg.hd = a.H - 1 - wg.hd;
   const int b = wg.b, hd = wg.hd;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, li = lane & 31;
@@ -1317,7 +1252,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_dq_kernel(AttnAr
   // pass stored zeros for them (dS^T), the descriptor's range ends at sep (K).  At the top of tile t the K tile t+1 and then the
   // dS^T tile t+2 are issued; the end of tile t waits for everything EXCEPT that last dS^T tile (vmcnt = its instruction count:
   // loads return in order), so a dS^T fetch has two tile times to arrive.  (One tile ahead, the pass ran at 3.4 TB/s.)
-  const long ds_bh = ((long)(b - a.b0) * a.H + hd) * a.ds_rows * a.ds_ld;
+  const long ds_bh = ((long)b * a.H + hd) * a.ds_rows * a.ds_ld;
   const DmaRsrc rd = make_dma_rsrc(reinterpret_cast<const T*>(a.ds) + ds_bh, (long)a.ds_rows * a.ds_ld * (long)sizeof(T));
   const DmaRsrc rk = make_dma_rsrc(Kp, ((long)(sep - 1) * rs + D) * (long)sizeof(T));   // rows >= sep read as zero
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
@@ -1353,12 +1288,9 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_dq_kernel(AttnAr
     }
   };
   static_assert(Q::NPW <= 10, "piece count per wave exceeds the vmcnt cases above");
-  if constexpr (DQABL & 1) {      // ablation build: nothing is fetched into the ring -- zero it, so that the (wrong) dQ stays finite and the step keeps running on ordinary numbers
-    for (int o = lane * 16; o < Q::NDS * Q::DSW; o += 64 * 16) lds_write16(dsw + o, u32x4{0u, 0u, 0u, 0u});
-  }
   if (ntiles > 0) { dma_k(0, 0); dma_ds(0, 0); }
-  if (ntiles > 1 && !(ABL & 1) && !(DQABL & 1)) dma_ds(1, 1);
-  wait_all_but(ntiles > 1 && !(ABL & 1) && !(DQABL & 1) ? my_ds_pieces : 0);
+  if (ntiles > 1) dma_ds(1, 1);
+  wait_all_but(ntiles > 1 ? my_ds_pieces : 0);
   __syncthreads();
   int sd = 0, sk = 0;                  // ring slots of tile t
   for (int t = 0; t < ntiles; ++t) {
@@ -1366,7 +1298,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_dq_kernel(AttnAr
     const lds_char* kc = Kc(sk);
     constexpr int NKS = C::KVB / 16;     // contraction steps per tile
     const int sd2 = sd == 0 ? 2 : sd - 1;                      // (t + 2) % 3
-    const bool more_ds = !(ABL & 1) && !(DQABL & 1) && t + 2 < ntiles;
+    const bool more_ds = t + 2 < ntiles;
     if (t + 1 < ntiles) dma_k(sk ^ 1, t + 1);                  // slots last read in tile t-1: every wave is past that tile's barrier
     if (more_ds) dma_ds(sd2, t + 2);
     Frag<T> dsf[NKS];
@@ -1387,7 +1319,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_dq_kernel(AttnAr
       PFN_PIN_LDS_MFMA();
     }
     wait_all_but(more_ds ? my_ds_pieces : 0);
-    if (!(ABL & 4)) __syncthreads();
+    __syncthreads();
     sd = sd == 2 ? 0 : sd + 1;
     sk ^= 1;
   }
@@ -1398,7 +1330,7 @@ __global__ __launch_bounds__((AttnCfg<T, D>::NT)) void attn_bwd_dq_kernel(AttnAr
   // 16 bytes each on a row): every load and store instruction covers whole rows -- with one row per lane (the accumulator
   // layout) each instruction touched 32 to 64 different cache lines and this tail cost 32 us of the pass's 144.  ds_i k_i reaches
   // the accumulator layout through a wave-private LDS image (the tile buffers are free after the loop).
-  const bool wave_has_test = !(ABL & 8) && q0 + wave * 32 + 31 >= sep;
+  const bool wave_has_test = q0 + wave * 32 + 31 >= sep;
   constexpr int TS = C::RB + 16;                       // row stride of the self-term image
   LdsPtr tself = smem + wave * 32 * TS;
   if (wave_has_test) {
@@ -1721,8 +1653,6 @@ __global__ __launch_bounds__(256) void attn_bwd_plain_dq_kernel(AttnArgs a) {
 // =============================================================================================
 // launchers
 // =============================================================================================
-static int g_attn_bwd_group = 0;      // PFN_TUNE_ATTN_BWD_GROUP (launch_bwd_k)
-void set_attn_bwd_group(int datasets) { g_attn_bwd_group = datasets; }
 bool attn_fwd_can_fuse_q(int E, int H, int precision) {
   const int D = H > 0 ? E / H : 0;
   return prec_is16(precision) && (D == 32 || D == 64 || D == 128) && E % 128 == 0;
@@ -1790,49 +1720,15 @@ template <typename T, int D, bool DROP> static int launch_bwd_k(const AttnArgs& 
   }
   constexpr size_t lds_kv = BwdKvCfg<T, D>::LDS, lds_dq = BwdDqCfg<T, D>::LDS;
   static_assert(lds_kv <= 160 * 1024 && lds_dq <= 160 * 1024, "attention backward: tile buffers exceed the CU's LDS");
-  static LdsAllowance allow_kv[3], allow_dq;      // (per device; hipFuncSetAttribute costs tens of microseconds of host time per call)
-  auto run_kv = [&](auto kernel, LdsAllowance& allow, const AttnArgs& ac) {
-    allow.ensure(kernel, lds_kv);
-    hipLaunchKernelGGL(kernel, dim3(((ac.sep + C::QBLK - 1) / C::QBLK) * ac.H * ac.bg), dim3(C::NT), lds_kv, s, ac);
-  };
+  static LdsAllowance allow_kv, allow_dq;      // (per device; hipFuncSetAttribute costs tens of microseconds of host time per call)
   // (Launching the pair for a few datasets at a time into one scratch, so that dS^T -- 436 MB per 16 datasets -- stays in the
-  // 256 MB memory-side cache, was measured: 432 vs 436 us with two chunks, slower with more: each launch ends in a partial round.)
-  // PFN_TUNE_ATTN_BWD_GROUP (round 6 experiment): the key-block / query-block pair for `group` datasets at a time, every group through the front of
-  // the dS^T scratch (25.7 MB per dataset at the north star), so that the query-block pass finds what the key-block pass just wrote in the 256 MB memory-side cache
-  // instead of in HBM.  0 = one pair for the whole call.  (Measured: profiles/r06_attention_bwd_groups.txt.)
-  const int group = (g_attn_bwd_group > 0 && g_attn_bwd_group < a.B && (parts & ATTN_BWD_KV) && (parts & ATTN_BWD_DQ)) ? g_attn_bwd_group : a.B;
-  const bool dq_runs = (parts & ATTN_BWD_DQ) && (a.S + C::QBLK - 1) / C::QBLK > a.q_begin / C::QBLK;
-  if (group < a.B) {
-    if (a.q_from_sep) {
-      const int rc = launch_zero_row_prefix_ragged(a.dqkv, a.S, a.B, a.sep_of, 3L * a.E * (long)sizeof(T), (long)a.E * (long)sizeof(T), s);
-      if (rc != PFN_OK) return rc;
-    } else if (a.q_begin > 0) {
-      const int rc = launch_zero_row_prefix(a.dqkv, a.S, a.B, a.q_begin, 3L * a.E * (long)sizeof(T), (long)a.E * (long)sizeof(T), s);
-      if (rc != PFN_OK) return rc;
-    }
-    allow_dq.ensure(attn_bwd_dq_kernel<T, D, DROP>, lds_dq);
-    for (int b0 = 0; b0 < a.B; b0 += group) {
-      AttnArgs ag = a;
-      ag.b0 = b0; ag.bg = std::min(group, a.B - b0);
-      if (a.sep > 0) {
-        ProfScope ps(PFN_PROF_ATTN_BWD_KV + (a.q_begin > 0 ? 1 : 0), s);
-        run_kv(attn_bwd_kv_kernel<T, D, 0, DROP>, allow_kv[0], ag);
-      }
-      if (dq_runs) {
-        ProfScope ps(PFN_PROF_ATTN_BWD_DQ + (a.q_begin > 0 ? 1 : 0), s);
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, DROP>), dim3(((a.S + C::QBLK - 1) / C::QBLK - a.q_begin / C::QBLK) * a.H * ag.bg), dim3(C::NT), lds_dq, s, ag);
-      }
-    }
-    return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-  }
+  // 256 MB memory-side cache, was measured: 432 vs 436 us with two chunks, slower with more: each launch ends in a partial round.
+  // Measured again with every group through the front of the scratch, 25.7 MB per dataset: slower at every group size,
+  // profiles/r06_attention_bwd_groups.txt.)
   if ((parts & ATTN_BWD_KV) && a.sep > 0) {
     ProfScope ps(PFN_PROF_ATTN_BWD_KV + (a.q_begin > 0 ? 1 : 0), s);
-    if constexpr (BwdKvCfg<T, D>::SPLIT && !DROP) {      // (A/B builds only: -DPFN_KV_SPLIT_D256=1)
-      run_kv(attn_bwd_kv_kernel<T, D, 2, false>, allow_kv[2], a);
-      run_kv(attn_bwd_kv_kernel<T, D, 1, false>, allow_kv[1], a);
-    } else {
-      run_kv(attn_bwd_kv_kernel<T, D, 0, DROP>, allow_kv[0], a);
-    }
+    allow_kv.ensure(attn_bwd_kv_kernel<T, D, DROP>, lds_kv);
+    hipLaunchKernelGGL((attn_bwd_kv_kernel<T, D, DROP>), dim3(((a.sep + C::QBLK - 1) / C::QBLK) * a.H * a.B), dim3(C::NT), lds_kv, s, a);
   }
   if (parts & ATTN_BWD_DQ) {
     if (a.q_from_sep) {       // ragged batch: every dataset's own prefix
@@ -2009,7 +1905,6 @@ int launch_attn_bwd(const AttnArgs& a_in, int precision, hipStream_t s) {
   AttnArgs a = a_in;
   attn_bwd_ds_dims(a.S, a.sep, &a.ds_rows, &a.ds_ld);
   a.q_begin = a.q_begin / 256 * 256;
-  a.b0 = 0; a.bg = a.B;
   PFN_ATTN_DISPATCH(launch_bwd_t, return (launch_bwd_plain_f32<256>(a, s)))
 }
 

@@ -168,26 +168,18 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmTN g) {
 // the descriptor's num_records are 32-bit -- token split rows x row pitch x 2 bytes <= 0x7ffffff0 for both operands
 // (launch_gemm_tn_group answers PFN_ERR_UNSUPPORTED otherwise).
 // ---------------------------------------------------------------------------------------------
-// Stage depth / ring length (experiment builds: tools/build_variants.sh with -DPFN_TNB_KT= -DPFN_TNB_NS=).  Measured at the north
+// Stage depth / ring length: two stages of 64 tokens.  Measured at the north
 // star (tools/bench_wgrad.py --batch 16) with the per-stage address arithmetic still in the loop: 64 x 2 950 us, 32 x 3 952, 32 x 4 965,
 // 32 x 5 965; and again without it (--batch 32, profiles/wgrad_stage_issue.txt): 64 x 2 1566-1621 us, 32 x 3 1706-1716, 32 x 4 1743,
 // 32 x 5 1730-1748 -- up to four stages in flight instead of one buy nothing either way: the operand stream is not bound by latency.
 // The address arithmetic itself was 130 us of the 1734-1767 us the launch took with it, its position another 30: requested right behind
 // the stage barrier the issue block (8 DMA instructions and 70 scalar ones) holds up the first fragment reads of all eight waves at once;
-// behind the first 16-token step's MFMAs (PFN_TNB_LATE_ISSUE, the slot it fills is free from the barrier on) it runs under them.
-#ifndef PFN_TNB_KT
-#define PFN_TNB_KT 64
-#define PFN_TNB_NS 2
-#endif
-#ifndef PFN_TNB_LATE_ISSUE
-#define PFN_TNB_LATE_ISSUE 1      // 1: the next stage's DMA is issued behind the first 16-token step's MFMAs (measured faster); 0: right behind the stage barrier
-#endif
-constexpr int TNB_KT = PFN_TNB_KT;               // tokens per stage
-constexpr int TNB_NS = PFN_TNB_NS;               // stages in the LDS ring: TNB_NS - 1 of them in flight under the one being multiplied
+// behind the first 16-token step's MFMAs (the slot it fills is free from the barrier on) it runs under them.
+constexpr int TNB_KT = 64;                       // tokens per stage
+constexpr int TNB_NS = 2;                        // stages in LDS: one in flight under the one being multiplied
 constexpr int TNB_TILE = TNB_KT * 512;           // bytes per operand per stage
-constexpr int TNB_PW = TNB_KT / 16;              // 1-KiB DMA pieces per wave per operand per stage (a piece = 2 token rows x 512 B)
 constexpr int TNB_LDS = TNB_NS * 2 * TNB_TILE;
-static_assert(TNB_LDS <= 160 * 1024 && TNB_KT % 16 == 0 && TNB_NS >= 2 && (TNB_NS - 2) * 2 * TNB_PW < 64, "weight-gradient ring does not fit");
+static_assert(TNB_LDS <= 160 * 1024, "weight-gradient stages do not fit the CU's LDS");
 constexpr long TN_GROUP_MAX_SPLIT_BYTES = 0x7ffffff0L;      // token split rows x row pitch x 2 (TnStager's 32-bit byte range)
 
 // Operand staging of the grouped kernels (NW waves; a 1-KiB DMA piece is 2 token rows x 512 B, wave w moves pieces w, w + NW, ... of each
@@ -260,7 +252,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
 
   TnStager<8> stg;
   stg.init(pr, mbeg, rows_total, p0, q0, wave, lane, g.debug_mask);
-  static_assert(TnStager<8>::NP == TNB_PW, "wait_stage counts 2 TNB_PW DMA instructions per stage");
 
   f32x16 acc[4][2];
 #pragma unroll
@@ -278,33 +269,21 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
   for (int e = 0; e < 8; ++e) ones.v[e] = (T)1.0f;
 
   const int nt = (rows_total + TNB_KT - 1) / TNB_KT;
-  // Ring of TNB_NS stages: stage t is multiplied while stages t+1 .. t+TNB_NS-2 are in flight and stage t+TNB_NS-1 is requested
-  // into the slot stage t-1 has just released.  Loads retire in order, so "stage t has landed" is vmcnt(instructions of the
-  // younger stages) -- explicit s_waitcnt + raw s_barrier (wait_vm_barrier): __syncthreads() carries vmcnt(0).
+  // Two stages: stage t is multiplied while stage t+1 is requested into the slot stage t-1 has just released.  Nothing younger than
+  // stage t is in flight when it is wanted, so "stage t has landed" is vmcnt(0) -- explicit s_waitcnt + raw s_barrier (wait_vm_barrier).
   // (Touching later stages' lines to pull them into L2 instead made the launch slower: 916 us without, 990 / 1030 / 1070 us
   // touching 2 / 3 / 5 stages ahead.)
 #pragma unroll
-  for (int st = 0; st < TNB_NS - 1; ++st)
+  for (int st = 0; st < TNB_NS - 1; ++st)      // (the one stage requested ahead of the loop)
     if (st < nt) stg.issue(smem + st * 2 * TNB_TILE);
-  auto wait_stage = [&](int younger) {     // `younger` stages were requested after the one wanted now (wave-uniform)
-    if constexpr (TNB_NS == 2) { wait_vm_barrier<0>(); return; }      // one stage in flight: nothing to count, no branch
-    switch (younger) {
-      case 0: wait_vm_barrier<0>(); break;
-      case 1: wait_vm_barrier<(TNB_NS > 2 ? 1 : 0) * 2 * TNB_PW>(); break;
-      case 2: wait_vm_barrier<(TNB_NS > 3 ? 2 : 0) * 2 * TNB_PW>(); break;
-      case 3: wait_vm_barrier<(TNB_NS > 4 ? 3 : 0) * 2 * TNB_PW>(); break;
-      default: wait_vm_barrier<(TNB_NS - 2) * 2 * TNB_PW>(); break;
-    }
-  };
-  static_assert(TNB_NS <= 6, "wait_stage cases");
-  // the main loop exists twice (with / without the bias-gradient MFMA) so neither carries a branch
-  auto main_loop = [&](auto with_colsum) {
+  // the main loop exists twice (with / without the bias-gradient MFMA) so neither carries a branch.  (Captures by name, in this order: the order is
+  // the closure's layout, and hipcc's scalar register assignment in the loop follows it.)
+  auto main_loop = [&nt, &stg, &smem, &wq, &wp, &acc, &cs, &ones](auto with_colsum) {
     constexpr bool CS = decltype(with_colsum)::value;
-    int slot = 0, slot_next = TNB_NS - 1;
+    int slot = 0, slot_next = 1;
     for (int t = 0; t < nt; ++t) {
-      wait_stage(min(nt - t - 1, TNB_NS - 2));
-      const bool more = t + TNB_NS - 1 < nt;
-      if (!PFN_TNB_LATE_ISSUE && more) stg.issue(smem + slot_next * 2 * TNB_TILE);
+      wait_vm_barrier<0>();
+      const bool more = t + 1 < nt;
       LdsPtr ta = smem + slot * 2 * TNB_TILE;
       LdsPtr tb = ta + TNB_TILE;
 #pragma unroll
@@ -320,7 +299,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
           for (int j = 0; j < 2; ++j) acc[i][j] = mma32(fa[i], fb[j], acc[i][j]);
         // bias gradient: Q wave wq sums the columns of P sub-tile wq (one more fragment read, one more MFMA)
         if constexpr (CS) cs = mma32(load_frag_tr<T, 512, 1>(ta, ks, wp * 128 + wq * 32), ones, cs);
-        if (PFN_TNB_LATE_ISSUE && ks == 0) {      // the slot is free from the stage barrier on: the issue block goes under the first step's MFMAs
+        if (ks == 0) {      // the other slot is free from the stage barrier on: the issue block goes under the first step's MFMAs
           PFN_PIN_LDS_MFMA();
           if (more) stg.issue(smem + slot_next * 2 * TNB_TILE);
           PFN_PIN_LDS_MFMA();
@@ -372,10 +351,6 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmTNGroup g) {
 // With the staging of gemm_tn_big_kernel (TnStager; the clamp and the 64-bit multiply per piece were in this loop too): 1977-1985 us against 2014-2041 us at the
 // north star's 64 000 tokens, against 1566-1621 us of the eight-wave kernel (profiles/wgrad_stage_issue.txt): eight waves stay the default.
 // ---------------------------------------------------------------------------------------------
-// Written for two 64-token stages: the experiment builds with another stage depth / ring length (PFN_TNB_KT / PFN_TNB_NS above) leave it out, and the launcher then
-// refuses PFN_TUNE_WGRAD_WAVES = 4.
-#define PFN_TNW_BUILT (PFN_TNB_KT == 64 && PFN_TNB_NS == 2)
-#if PFN_TNW_BUILT
 constexpr int TNW_NW = 4;                              // waves: 2 (P) x 2 (Q), each 128 x 128
 template <typename T>
 __global__ __launch_bounds__(TNW_NW * 64, 1) void gemm_tn_wide_kernel(GemmTNGroup g) {
@@ -496,7 +471,6 @@ __global__ __launch_bounds__(TNW_NW * 64, 1) void gemm_tn_wide_kernel(GemmTNGrou
         if (pp < pv) unsafeAtomicAdd(pr.C + (long)pp * pr.ldc + qq, acc[i][j][r] * osc);
       }
 }
-#endif      // PFN_TNW_BUILT
 
 // ---------------------------------------------------------------------------------------------
 // host launchers
@@ -505,8 +479,6 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 static int g_tn_debug_wrap = 0;
 void set_gemm_tn_debug_wrap(int rows) { g_tn_debug_wrap = rows; }
-static int g_tn_group_splits = 0;
-void set_gemm_tn_group_splits(int splits) { g_tn_group_splits = splits; }
 static bool g_tn_wide = false;
 void set_gemm_tn_group_waves(int waves) { g_tn_wide = waves == 4; }
 
@@ -548,7 +520,6 @@ int launch_gemm_tn_group(GemmTNGroup g, int precision, hipStream_t stream) {
   // split the token axis only when the group cannot occupy the chip by itself
   // automatic: the smallest split count (<= 8) whose workgroup count fills whole rounds of the 256 CUs to >= 90 %
   int splits = g.splits;
-  if (splits <= 0 && g_tn_group_splits > 0) splits = g_tn_group_splits;      // (test / profiling knob)
   if (splits <= 0) {
     splits = 8;
     for (int sp = 1; sp <= 8; ++sp) {   // (a 256 x 256 partial tile is 65536 atomics: more than 8 splits cost more than they fill)
@@ -572,7 +543,6 @@ int launch_gemm_tn_group(GemmTNGroup g, int precision, hipStream_t stream) {
   const int wrap = g_tn_debug_wrap;
   g.debug_mask = wrap >= TNB_KT && (wrap & (wrap - 1)) == 0 ? wrap - 1 : 0x7fffffff;
   if (g_tn_wide) {      // PFN_TUNE_WGRAD_WAVES = 4: four waves of 128 x 128 (gemm_tn_wide_kernel)
-#if PFN_TNW_BUILT
     static LdsAllowance allow_w[2];
     if (precision == PFN_PREC_FP16) {
       allow_w[1].ensure(gemm_tn_wide_kernel<f16>, TNB_LDS);
@@ -582,9 +552,6 @@ int launch_gemm_tn_group(GemmTNGroup g, int precision, hipStream_t stream) {
       hipLaunchKernelGGL(gemm_tn_wide_kernel<bf16>, dim3(tiles * splits), dim3(TNW_NW * 64), TNB_LDS, stream, g);
     }
     return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
-#else
-    return PFN_ERR_UNSUPPORTED;
-#endif
   }
   static LdsAllowance allowance[2];
   if (precision == PFN_PREC_FP16) {

@@ -512,23 +512,15 @@ __global__ __launch_bounds__(256, 3) void gp_syrk_kernel(GpArgs a, int r0, int r
 // ---------------------------------------------------------------------------------------------
 constexpr int SYP_SLAB = 128 * PL_ROWB;             // one plane of one 128-row operand chunk in LDS: 4 KiB
 constexpr int SYP_STAGE = 2 * PL_NPL * SYP_SLAB;    // A and B, two planes each: 16 KiB
-#ifndef PFN_SYP_NST
-#define PFN_SYP_NST 3
-#endif
-#ifndef PFN_SYP_WGS
-#define PFN_SYP_WGS 3
-#endif
-#ifndef PFN_SYP_ABLATE      // timing experiments only (results are wrong): 1 = no C read-modify-write, 2 = no MFMAs, 4 = no plane DMA
-#define PFN_SYP_ABLATE 0
-#endif
-constexpr int SYP_NST = PFN_SYP_NST;                // stages in the ring: two in flight under the one being multiplied
+constexpr int SYP_NST = 3;                          // stages in the ring: two in flight under the one being multiplied
+constexpr int SYP_WGS = 3;                          // workgroups per CU
 constexpr int SYP_LDS = SYP_NST * SYP_STAGE;        // 48 KiB, three workgroups per CU
 constexpr int SYP_PPW = 2 * PL_NPL * 4 / 4;         // 1-KiB DMA pieces per wave and stage
 
 
 // One launch applies `nsets` solved panels (rank 256 each) to its region, so the region's C tiles are read and written once for all of them:
 // set s in {set0, set1} holds the panel whose plane row 0 is global row r0 - off_s.
-__global__ __launch_bounds__(256, PFN_SYP_WGS) void gp_syrk_planes_kernel(GpArgs a, int r0, int r1, int nsets, int set0, int off0, int set1, int off1) {
+__global__ __launch_bounds__(256, SYP_WGS) void gp_syrk_planes_kernel(GpArgs a, int r0, int r1, int nsets, int set0, int off0, int set1, int off1) {
   // C[i][j] -= sum_s sum_k X_s[i][k] X_s[j][k] for rows >= r0 and the grid's tile columns from r0 on (lower triangle, 128 x 128 tiles), X_s = a 256-wide solved
   // panel read from its planes
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -564,7 +556,7 @@ __global__ __launch_bounds__(256, PFN_SYP_WGS) void gp_syrk_planes_kernel(GpArgs
       const int o = q / (4 * PL_NPL), p = (q / 4) % PL_NPL, qq = q % 4;
       const long row = (long)((o ? j0 : i0) - r0) + roff + qq * 32;
       const long off = sbase + plane_offset(a.plane_rows, p, kc, row) + lane * 16;
-      if (!(PFN_SYP_ABLATE & 4)) dma16(rp, smem + buf * SYP_STAGE + (o * PL_NPL + p) * SYP_SLAB + qq * 1024, (int)off);
+      dma16(rp, smem + buf * SYP_STAGE + (o * PL_NPL + p) * SYP_SLAB + qq * 1024, (int)off);
     }
   };
   stage(0, 0);
@@ -590,7 +582,6 @@ __global__ __launch_bounds__(256, PFN_SYP_WGS) void gp_syrk_planes_kernel(GpArgs
 #pragma unroll
       for (int j = 0; j < 2; ++j) {   // swapped operands: a lane owns one ROW of the tile; smallest terms first (as gp_syrk_kernel)
         f32x16 c = acc[i][j];
-        if (PFN_SYP_ABLATE & 2) { c[0] += (float)fb[j][1].v[0] + (float)fa[i][0].v[0] + (float)fb[j][0].v[0] + (float)fa[i][1].v[0]; acc[i][j] = c; continue; }
         c = mma32_f16(fb[j][1], fa[i][0], c);
         c = mma32_f16(fb[j][0], fa[i][1], c);
         acc[i][j] = mma32_f16(fb[j][0], fa[i][0], c);
@@ -604,21 +595,10 @@ __global__ __launch_bounds__(256, PFN_SYP_WGS) void gp_syrk_planes_kernel(GpArgs
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] *= inv_s2;
-  if (PFN_SYP_ABLATE & 1) {      // keep the accumulators alive without the 128 KiB of traffic
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum += acc[i][j][r];
-    if (sum == 123.456f) Kb[0] = sum;
-    return;
-  }
   syrk_rmw(Kb, S, acc, i0 + wm * 64, j0 + wn * 64, __builtin_amdgcn_readfirstlane((j0 + 127 < i0 && i0 + 127 < r1) ? 1 : 0) != 0, r1, r1, lane);
 }
 
-// What bounds it now (round 5, profiles/r05_gp_sampler.txt): ablation builds (PFN_SYP_ABLATE) of the rank-256 form gave, per 7 x 320 datasets, 28.3 ms whole,
+// What bounds it now (round 5, profiles/r05_gp_sampler.txt): builds of the rank-256 form with one phase taken out gave, per 7 x 320 datasets, 28.3 ms whole,
 // 19.2 ms with the C read-modify-write alone (4 TB/s: the HBM's mixed read / write rate), 11.1 ms with the products alone and 14.3 without the read-modify-write
 // -- the two phases ADD instead of overlapping, although three workgroups share a CU.  Requesting the C tile two stages before the subtraction (registers, peeled
 // tail; built and measured: 25.79 vs 25.86 ms) changes nothing, so it is not the C round trip of the workgroup itself: a CU's vector memory path returns in

@@ -627,8 +627,6 @@ int pfn_set_tuning(int key, int value) {
     case PFN_TUNE_GEMM_TN_WRAP: set_gemm_tn_debug_wrap(value); return PFN_OK;
     case PFN_TUNE_FUSE_LNBWD: g_default_schedule = value ? (g_default_schedule & ~PFN_SCHED_SEPARATE_LNBWD) : (g_default_schedule | PFN_SCHED_SEPARATE_LNBWD); return PFN_OK;
     case PFN_TUNE_ATTN_PINGPONG: set_attn_pingpong(value); return PFN_OK;
-    case PFN_TUNE_ATTN_BWD_GROUP: set_attn_bwd_group(value); return PFN_OK;
-    case PFN_TUNE_WGRAD_SPLITS: set_gemm_tn_group_splits(value); return PFN_OK;
     case PFN_TUNE_WGRAD_WAVES: set_gemm_tn_group_waves(value); return PFN_OK;
     case PFN_TUNE_LOSS_SCALE_TARGET: return set_loss_scale_target(value);
     case PFN_TUNE_RESIDUAL16: g_default_schedule = value ? (g_default_schedule & ~PFN_SCHED_F32_RESIDUAL) : (g_default_schedule | PFN_SCHED_F32_RESIDUAL); return PFN_OK;

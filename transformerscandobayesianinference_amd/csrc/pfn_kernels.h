@@ -126,7 +126,6 @@ struct GemmTNGroup {
 };
 void set_gemm_tn_debug_wrap(int rows);         // PFN_TUNE_GEMM_TN_WRAP (see GemmTNGroup::debug_mask): powers of two >= 64 only, everything else = off
 void set_gemm_tn_group_waves(int waves);       // PFN_TUNE_WGRAD_WAVES: 8 = gemm_tn_big_kernel (eight waves of 128 x 64), 4 = gemm_tn_wide_kernel (four of 128 x 128)
-void set_gemm_tn_group_splits(int splits);      // PFN_TUNE_WGRAD_SPLITS: token-axis splits of the grouped weight-gradient launch when the caller leaves them automatic (0 = the occupancy rule)
 // GEMM + bias + residual + LayerNorm in one kernel (gemm_nt_ln_kernel): one workgroup owns 128 full rows of the
 // N = emsize columns, so the row statistics are taken straight from the accumulators:
 //     v = A . B^T + bias + r,   y = v (f32, kept for the LayerNorm backward),   x_t = (T) ((v - mean) rstd gamma + beta)
@@ -196,9 +195,6 @@ struct AttnArgs {
     };
   };
   int pingpong;  // filled by the launcher (PFN_TUNE_ATTN_PINGPONG): bit 0 forward, bit 1 key-block pass
-  // filled by the launcher: the backward's key-block / query-block pair may run for a GROUP of datasets at a time (PFN_TUNE_ATTN_BWD_GROUP) -- datasets [b0, b0 + bg) of the
-  // B in this call; every group re-uses the front of the dS^T scratch, so what the key-block pass wrote is still in the 256 MB memory-side cache when the query-block pass reads it
-  int b0, bg;
   // forward with the Q PROJECTION FUSED IN (north_star's "QKV projection + attention as one kernel", the half that can exist: K and V are shared by every query block
   // of a head and stay a GEMM).  xq != nullptr (16-bit operands, head dim <= 128, E % 128 == 0): the workgroup forms its 256 queries' head slice q = x W_q[h]^T + b_q[h]
   // on the matrix cores in the prologue -- W_q[h] through LDS in 128-column chunks, x rows straight from global -- instead of reading them from qkv;
@@ -238,7 +234,6 @@ struct AttnCacheBwdArgs {
 int launch_clamp_sep_of(const int* src, int* dst, int B, int hi, hipStream_t stream);
 int launch_attn_bwd_cache(const AttnCacheBwdArgs& a, int precision, hipStream_t stream);
 void set_attn_pingpong(int mask);
-void set_attn_bwd_group(int datasets);      // 0 = all datasets of a call in one launch pair
 enum : int { ATTN_BWD_DELTA = 1, ATTN_BWD_KV = 2, ATTN_BWD_DQ = 4 };
 int64_t attn_bwd_ds_bytes(int B, int S, int H, int precision);   // size of AttnArgs::ds for any sep <= S
 int launch_attn_fwd(const AttnArgs& a, int precision, hipStream_t stream);

@@ -354,6 +354,7 @@ int launch_embed_fwd(const EmbedArgs& a, int precision, hipStream_t s) {
 // and every gradient element receives one atomic per workgroup -- gridDim.x (<= 32) of them in total instead of
 // one per 128-token chunk.
 constexpr int EMBB_TOK = 128;   // tokens staged per pass
+constexpr int EMBB_WGS = 512;   // workgroups of a launch, over both grid axes
 constexpr int EMBB_MAXF = 32;   // nf + 2 rounded up to 8 must fit (wider encoders take the chunked path below)
 template <int NF8>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbedBwdArgs a) {
@@ -554,11 +555,8 @@ int launch_embed_bwd(const EmbedBwdArgs& a, hipStream_t s) {
   const int nf8 = (a.nf + 2 + 7) / 8 * 8;
   if (nf8 <= EMBB_MAXF) {
     const int ey = (a.E + 63) / 64;
-#ifndef PFN_EMBB_WGS
-#define PFN_EMBB_WGS 512
-#endif
     // (single_block: one workgroup per column block walks every token -- each gradient element then has one writer: PFN_SCHED_DETERMINISTIC)
-    const dim3 grid(a.single_block ? 1u : (unsigned)std::max<long>(1, std::min<long>((ntok + EMBB_TOK - 1) / EMBB_TOK, std::max(1, PFN_EMBB_WGS / ey))), ey);
+    const dim3 grid(a.single_block ? 1u : (unsigned)std::max<long>(1, std::min<long>((ntok + EMBB_TOK - 1) / EMBB_TOK, std::max(1, EMBB_WGS / ey))), ey);
     const size_t lds = std::max((size_t)EMBB_TOK * nf8, (size_t)4 * 64 * (nf8 + 1)) * sizeof(float);
     switch (nf8) {
       case 8: hipLaunchKernelGGL(embed_bwd_kernel<8>, grid, dim3(256), lds, s, a); break;

@@ -664,6 +664,54 @@ int pfn_gpc_lml_grad(const float* theta, const float* train, const float* labels
 int pfn_gpc_predict(const float* theta, const float* train, const float* labels, const float* test, const int32_t* fold, int P, int n, int T, int F, int NC,
                     int n_splits, float* cv_f, float* test_f, float* test_var, int32_t* status, void* stream);
 
+/* ---- BNN classifier with its grid search (ABI 10, additive; csrc/bnn_cv.hip): the reference's bayes_net_metric (tabular.py:372-478) as a batch of independent
+ * SVI fits -- the model, the guide and the step of pfn_bnn_svi_steps at activation = 0 with ONE particle -- followed by their predictive.  f32 data, caller-owned
+ * buffers, stream-ordered, no allocation, no workspace, no host synchronisation, no atomics.
+ *
+ * pfn_bnn_cv: P problems; train [P,n,F], labels [P,n] (class y = label > 0.5), test [P,T,F], fold [P,n] int32 (the CV test fold of each train row), all on the
+ *   device; NC candidates (width H_c, learning rate lr_c): cand_H [NC] int32 and cand_lr [NC] f32 are HOST arrays, read before the call returns.  One block per fit
+ *   (problem p, candidate c, slot s): slot s < n_splits trains on the rows with fold[p,i] != s, slot s = n_splits on all rows (the refit), slots beyond are unused
+ *   (status PFN_BNN_CV_UNUSED, nothing else written).  A row whose fold value is outside 0 .. n_splits - 1 trains every slot and is held out by none.  A training
+ *   part that holds one class is fitted like any other.
+ * Model: theta = (W1 [H,F] row-major, b1 [H], W2 [2,H], b2 [2]), D = H (F + 3) + 2; o = W2 (W1 x + b1) + b2;
+ *   U(theta) = |theta|^2 / 2 + (D / 2) log 2 pi - sum_i m_i log softmax(o_i)[y_i], m_i = 1 on the slot's training rows (a row with m_i = 0 is not read by the
+ *   steps: a NaN there stays there).  Guide q = N(loc, diag(scale^2)), scale = softplus(u); per step theta = loc + scale eps,
+ *   L = U(theta) - sum_i (log scale_i + eps_i^2 / 2) - (D / 2) log 2 pi, g_loc = grad U(theta), g_scale = grad U(theta) * eps - 1 / scale, g_u = g_scale sigmoid(u), then
+ *   torch.optim.Adam without weight decay on loc and u exactly as stated for pfn_bnn_svi_steps (beta^t in f64, t = absolute step index + 1) with lr = lr_c.
+ *   The sums over rows, features and hidden units are accumulated in f64 and rounded once to f32; everything else is f32.
+ * state [P,NC,6 slots,6 rows,ld] f32, caller-owned; rows loc, u, m_loc, v_loc, m_u, v_u; ld >= the largest candidate's D; columns >= that candidate's own D, and the
+ *   unused slots, are never read or written.  The launch runs steps step0 .. step0 + num_steps - 1; loss [P,NC,6,num_steps] (or NULL) receives L of every step,
+ *   evaluated before the step's update.
+ * Predictive: after the steps, skipped when num_pred_samples = S = 0; draws theta_k = loc + scale eps_k, k < S, prob_k(x) = sigmoid(o_1 - o_0).  Slot s < n_splits
+ *   writes cv_prob [P,NC,n] at its held-out rows (fold == s) only -- a row in no fold is never written --, the refit slot writes test_prob [P,NC,T]: the mean over
+ *   the draws, added in draw order in f64 and rounded once.  cv_draw / test_draw (same shapes, NULL to skip) are the reference's estimator, the mean over the draws
+ *   of a Bernoulli observation obs_k = (u_k < prob_k).
+ * Noise: q = (problem_ids[p], int64 [P] on the device, or p when NULL) * 8 + slot; it does not depend on the candidate, so the candidates of a problem share their
+ *   random numbers.  With B(idx) = philox4x32_10(idx, stream = q, key = seed):
+ *     eps of coordinate i at absolute step t  = component i & 3 of normal4(B((t << 12) | (i >> 2)))
+ *     eps of coordinate i in predictive draw k = component i & 3 of normal4(B(((2^41 + k) << 12) | (i >> 2)))
+ *     u of row r in predictive draw k          = (word r & 3 of B(((2^42 + k) << 12) | (r >> 2)) >> 8) * 2^-24;  r = i for train row i, n + j for test row j
+ *   (normal4: Box-Muller on the block's four words, as for pfn_bnn_svi_steps).  D <= 8386 uses the blocks 0 .. 2096 of 4096; the three domains are disjoint.
+ * A fit is a bitwise function of its own problem, candidate (H, lr), slot, q and seed, wherever it sits in the call and however the candidates are grouped into
+ *   calls; steps(0, a + b) equals steps(0, a) followed by steps(a, b); the predictive in a call of its own (num_steps = 0) equals the predictive at the end of a
+ *   stepping call.  A fit whose state is or becomes non-finite stays alone in that.  status [P,NC,6] int32: PFN_BNN_CV_UNUSED, PFN_BNN_CV_DONE, or
+ *   PFN_BNN_CV_NONFINITE where loc or u left the finite numbers during the call (or, in a predictive-only call, were not finite).
+ * 4 <= n <= 128, 1 <= T <= 128, 1 <= F <= 128, 1 <= NC <= PFN_BNN_CV_MAX_CANDIDATES, every 1 <= cand_H <= 64, else PFN_ERR_UNSUPPORTED (a NULL cand_H is an
+ *   argument error); P >= 1, 2 <= n_splits <= 5, ld >= max D, 0 <= step0 <= 2^40, num_steps >= 0, 0 <= num_pred_samples <= 2^20, every lr finite and >= 0, beta1 /
+ *   beta2 in [0, 1), eps >= 0, non-NULL train, labels, test, fold, cand_H, cand_lr, state, status, and non-NULL cv_prob and test_prob when num_pred_samples > 0,
+ *   else PFN_ERR_ARGUMENT; the limits are checked first, all of it before any device pointer is read and before any HIP call.  num_steps = 0 with
+ *   num_pred_samples = 0 returns at once. */
+#define PFN_BNN_CV_FOLDS 5
+#define PFN_BNN_CV_SLOTS 6
+#define PFN_BNN_CV_MAX_CANDIDATES 64
+#define PFN_BNN_CV_UNUSED 0
+#define PFN_BNN_CV_DONE 1
+#define PFN_BNN_CV_NONFINITE 2
+int pfn_bnn_cv(const float* train, const float* labels, const float* test, const int32_t* fold, const int32_t* cand_H, const float* cand_lr, int P, int n, int T,
+               int F, int NC, int n_splits, float* state, int64_t ld, int64_t step0, int num_steps, float beta1, float beta2, float eps, int num_pred_samples,
+               uint64_t seed, const int64_t* problem_ids, float* loss, float* cv_prob, float* test_prob, float* cv_draw, float* test_draw, int32_t* status,
+               void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

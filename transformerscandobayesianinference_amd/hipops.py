@@ -2,6 +2,7 @@
 transformer stack (`pfn_op_*`: one kernel launch per call; the per-kernel parity tests tests/test_gpu_ops.py, bench.py's kernel table, tools/) and the
 studies' entry points with their tensor checks -- the GP hyper-parameter fit, NUTS, the BNN's potential, SVI and SVGD step loops, the tabular study's windows,
 AUC counts, kNN, logistic-regression and GP-classifier grid searches, and the stroke prior -- which the study modules (mcmc.py, tabular.py, priors/) build on."""
+import collections
 import ctypes
 import math
 
@@ -598,6 +599,71 @@ def logistic_cv(train, labels, test, fold, n_splits, cand_C, cand_kind, return_c
                                           int(n_splits), cv_correct.data_ptr(), test_z.data_ptr(), status.data_ptr(), _hip.ptr(coef), _hip.stream_ptr(dev)),
                'pfn_logistic_cv')
     return cv_correct, test_z, status, coef
+
+
+# ---- BNN classifier with its grid search (csrc/bnn_cv.hip; include/pfn_hip.h "BNN classifier with its grid search") ----
+BNN_CV_FOLDS, BNN_CV_SLOTS, BNN_CV_MAX_CANDIDATES = 5, 6, 64      # PFN_BNN_CV_*
+BNN_CV_UNUSED, BNN_CV_DONE, BNN_CV_NONFINITE = 0, 1, 2            # status
+BNN_CV_LIMITS = dict(n=(4, 128), T=(1, 128), F=(1, 128), NC=(1, BNN_CV_MAX_CANDIDATES), H=(1, 64))
+BnnCvOut = collections.namedtuple('BnnCvOut', 'loss cv_prob test_prob cv_draw test_draw status')
+
+
+def bnn_cv_check(n, T, F, cand_H):
+    """The limits of a pfn_bnn_cv launch, raised as ValueError before any launch.  cand_H: the candidates' widths.  Host only."""
+    cand_H = [int(h) for h in cand_H]
+    _limits_check('bnn_cv', BNN_CV_LIMITS, n=n, T=T, F=F, NC=len(cand_H))
+    for h in cand_H:
+        _limits_check('bnn_cv', BNN_CV_LIMITS, H=h)
+
+
+def bnn_cv_state(P, cand_H, F, device, loc0=None, init_scale=0.1):
+    """The state of every fit of a grid search at step 0: [P, NC, 6 slots, 6 rows, ld] f32 with ld the largest candidate's D; loc = loc0 ([P, NC, 6, ld] or None:
+    zeros; a candidate's columns beyond its own D are never read), u = softplus^-1(init_scale) and zero Adam moments, as bnn_svi_state."""
+    cand_H = [int(h) for h in cand_H]
+    ld = max(bnn_num_params(F, h) for h in cand_H)
+    assert init_scale > 0
+    state = torch.zeros(int(P), len(cand_H), BNN_CV_SLOTS, 6, ld, dtype=torch.float32, device=device)
+    if loc0 is not None:
+        assert tuple(loc0.shape) == (int(P), len(cand_H), BNN_CV_SLOTS, ld), 'loc0 [P, NC, 6, ld]'
+        state[:, :, :, 0] = loc0.to(device=device, dtype=torch.float32)
+    state[:, :, :, 1] = math.log(math.expm1(float(init_scale)))
+    return state
+
+
+def bnn_cv(train, labels, test, fold, n_splits, cand_H, cand_lr, state, num_steps, step0=0, num_pred_samples=0, seed=0, problem_ids=None, want_loss=False,
+           sample_obs=False, betas=(0.9, 0.999), eps=1e-8):
+    """The SVI steps and the predictive of every fit of a BNN grid search in one launch (pfn_bnn_cv): train [P,n,F], labels [P,n], test [P,T,F] f32 and fold [P,n]
+    int32 on the GPU; cand_H / cand_lr: the NC candidates' widths and learning rates (host sequences); state [P,NC,6,6,ld] f32 on the GPU, updated in place
+    (bnn_cv_state).  Slot s < n_splits of a candidate is the fit without fold s, slot n_splits the refit on all rows.  The launch covers the absolute steps
+    step0 .. step0 + num_steps - 1 and then, with num_pred_samples > 0, the predictive.  Returns BnnCvOut(loss [P,NC,6,num_steps] with want_loss (NaN in the unused slots), cv_prob [P,NC,n]
+    (written at the held-out rows of the slots in use; NaN elsewhere) and test_prob [P,NC,T] with num_pred_samples > 0, cv_draw / test_draw of the same shapes
+    with sample_obs, status [P,NC,6] int32); what was not asked for is None."""
+    import numpy as np
+    cand_H, cand_lr = [int(h) for h in cand_H], [float(v) for v in cand_lr]
+    NC = len(cand_H)
+    if len(cand_lr) != NC or not all(math.isfinite(v) and v >= 0 for v in cand_lr):
+        raise ValueError('cand_H [NC], cand_lr [NC] finite and >= 0')
+    num_steps, step0, S = int(num_steps), int(step0), int(num_pred_samples)
+    P, n, T, F = _fold_args(lambda n, T, F, NC: bnn_cv_check(n, T, F, cand_H), train, labels, fold, test, NC=NC, splits=(n_splits, BNN_CV_FOLDS), also_f32=(state,))
+    if not (0 <= step0 <= 1 << 40 and num_steps >= 0 and 0 <= S <= 1 << 20):
+        raise ValueError('0 <= step0 <= 2^40, num_steps >= 0, 0 <= num_pred_samples <= 2^20')
+    ld = state.shape[-1]
+    if tuple(state.shape) != (P, NC, BNN_CV_SLOTS, 6, ld) or ld < max(bnn_num_params(F, h) for h in cand_H):
+        raise ValueError('state [P, NC, 6, 6, ld] with ld >= the largest D')
+    dev = train.device
+    if problem_ids is not None:
+        assert problem_ids.dtype == torch.int64 and problem_ids.shape == (P,) and problem_ids.is_contiguous() and problem_ids.device == dev
+    new = lambda *shape: torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
+    loss = new(P, NC, BNN_CV_SLOTS, num_steps) if want_loss else None      # (the unused slots stay NaN)
+    cv_prob, test_prob = (new(P, NC, n), new(P, NC, T)) if S > 0 else (None, None)
+    cv_draw, test_draw = (new(P, NC, n), new(P, NC, T)) if S > 0 and sample_obs else (None, None)
+    status = torch.zeros(P, NC, BNN_CV_SLOTS, dtype=torch.int32, device=dev)
+    h_host, lr_host = np.asarray(cand_H, dtype=np.int32), np.asarray(cand_lr, dtype=np.float32)      # read before the call returns
+    _hip.check(_hip.lib().pfn_bnn_cv(train.data_ptr(), labels.data_ptr(), test.data_ptr(), fold.data_ptr(), h_host.ctypes.data, lr_host.ctypes.data, P, n, T, F, NC,
+                                     int(n_splits), state.data_ptr(), ld, step0, num_steps, float(betas[0]), float(betas[1]), float(eps), S, int(seed),
+                                     _hip.ptr(problem_ids), _hip.ptr(loss), _hip.ptr(cv_prob), _hip.ptr(test_prob), _hip.ptr(cv_draw), _hip.ptr(test_draw),
+                                     status.data_ptr(), _hip.stream_ptr(dev)), 'pfn_bnn_cv')
+    return BnnCvOut(loss, cv_prob, test_prob, cv_draw, test_draw, status)
 
 
 # ---- GP classifier with its grid search (csrc/gpc.hip; include/pfn_hip.h "GP classifier") ----

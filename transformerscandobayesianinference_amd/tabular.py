@@ -22,8 +22,12 @@ arithmetic in f64.
 restates scikit-learn's binary Laplace GaussianProcessClassifier: pfn_gpc_lml_grad gives the log marginal likelihood and its gradient of every candidate and fold
 of every window in one launch per L-BFGS pass (`priors.fast_gp_mix.batched_lbfgs` on the host drives it), pfn_gpc_predict the decision values and variances
 (DESIGN.md 21); folds, scores, selection and the erf-mixture probabilities are host arithmetic in f64.  It needs no library beyond this stack.
-The other baselines of the reference (the BNN classifier, whose grid cannot run in the reference either, XGBoost, CatBoost: :372-677) and the OpenML loaders
-stay out: they need libraries and network access this stack does not carry.  Any callable with the reference's metric-function
+    bayes_net_metric (with its grid search over 8 (width, lr) pairs) :372-478
+runs the 400 SVI steps and the 400 predictive draws of every candidate and fold of every window in one launch (pfn_bnn_cv): the model, the guide
+and the step are those of the BNN study's `eval_svi`; the folds, the starts, the scores and the selection are host arithmetic.  The reference's own grid search
+raises on two keys of param_grid['bayes'] that are no constructor arguments; what it evidently means is built here.
+The gradient-boosting baselines of the reference (XGBoost, CatBoost: :505-677) and the OpenML loaders stay out: they need libraries and network access this stack
+does not carry.  Any callable with the reference's metric-function
 signature still runs through `batch_pred`, one window at a time, as the reference loops.
 
 `get_model` trains through this package's `train()` -- HIP encoder stack, fused optimizer, HIP prior samplers --
@@ -644,3 +648,83 @@ def gp_metric(x, y, test_x, test_y, cat_features):
     """Reference tabular.py:480-503 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (ROC-AUC, proba [T]) of
     the GaussianProcessClassifier that GridSearchCV picks from the 24 kernels c * RBF(l) of param_grid['gp'] by min(5, n // 2)-fold stratified cross-validation
     (INTEGRATION.md).  `gp_metric.batched` is the same for many problems at once; `batch_pred` uses it."""
+
+
+## BNN classifier (reference tabular.py:372-478)
+
+param_grid['bayes'] = {'embed': [5, 10, 30, 64], 'lr': [1e-3, 1e-4], 'num_training_steps': [400], 'num_samples_for_prediction': [400]}
+BAYES_INIT_DRAWS = 15       # pyro's init_to_median: the start is the median of 15 prior draws per coordinate
+BAYES_INIT_SCALE = 0.1      # AutoDiagonalNormal's init_scale
+
+
+def _bayes_grid(grid=None):
+    """The reference's grid as the device runs it: (entries, cands, num_steps, num_draws).  `entries` are the parameter dicts in sklearn's ParameterGrid order
+    (keys sorted, the last key varying fastest: (5, 1e-3), (5, 1e-4), (10, 1e-3), ..., (64, 1e-4)), `cands` their (embed, lr).  'num_training_steps' and
+    'num_samples_for_prediction' are no constructor arguments of the reference's estimator -- its GridSearchCV raises on them --; each holds one
+    value, which is read here and applied as the step count and the draw count of every candidate."""
+    import itertools
+    grid = param_grid['bayes'] if grid is None else grid
+    if len(grid['num_training_steps']) != 1 or len(grid['num_samples_for_prediction']) != 1:
+        raise ValueError("param_grid['bayes']: 'num_training_steps' and 'num_samples_for_prediction' hold one value each")
+    keys = sorted(grid)
+    entries = [dict(zip(keys, values)) for values in itertools.product(*(grid[k] for k in keys))]
+    return entries, [(int(e['embed']), float(e['lr'])) for e in entries], int(grid['num_training_steps'][0]), int(grid['num_samples_for_prediction'][0])
+
+
+def _bayes_select(cv_prob, folds, cls, n_splits, test_prob):
+    """The host half of one problem's grid search, in f64: cv_prob [NC, n] every train row's class-1 probability from the fit that held it out, folds [n] the rows'
+    test folds, cls [n] bool, test_prob [NC, T] of the refits.  As GridSearchCV scores it: a fold's score is the share of its rows with (prob > 0.5) == class
+    (prob exactly 0.5 predicts class 0), a candidate's score the mean over folds, the best candidate the FIRST maximum (NaN ranks last).
+    Returns (mean_test_score [NC] f64, best index, proba [T] f64)."""
+    cv_prob, folds, cls = np.asarray(cv_prob, dtype=np.float64), np.asarray(folds), np.asarray(cls, dtype=bool)
+    right = (cv_prob > 0.5) == cls[None, :]
+    sizes = _fold_sizes(folds, n_splits)
+    scores = np.stack([right[:, folds == s].sum(1) / sizes[s] for s in range(n_splits)], 1)
+    scores[np.stack([np.isnan(cv_prob[:, folds == s]).any(1) for s in range(n_splits)], 1)] = np.nan      # a fit that left the finite numbers
+    mean, best = _first_maximum(scores)
+    return mean, best, np.asarray(test_prob, dtype=np.float64)[best]
+
+
+def _bayes_loc0(seed, problem, cand, D):
+    """The initial loc of the six slots of one (problem, candidate), [6, D] f32 on the host: the median of 15 N(0, 1) draws per coordinate (pyro's init_to_median
+    under this prior, as `fit_bnn_svi`), from a generator of its own, so that a fit's start depends on (seed, problem index, candidate index) alone."""
+    g = torch.Generator().manual_seed((int(seed) * 1000003 + int(problem)) * hipops.BNN_CV_MAX_CANDIDATES + int(cand))
+    return torch.randn(BAYES_INIT_DRAWS, hipops.BNN_CV_SLOTS, int(D), generator=g).median(0).values
+
+
+def _bayes_batched(x, y, test_x, test_y, return_params=False, sample_obs=False, seed=0, details=None):
+    """The BNN classifier with the reference's grid search for W problems at once: x [n, W, F] normalised train rows, y [n, W], test_x [T, W, F], test_y [T, W] on
+    the GPU.  One pfn_bnn_cv launch runs the 400 SVI steps and the 400 predictive draws of all W x 8 x (folds + 1) fits; the folds and the starts (before) and the
+    scores and the selection (after) are host arithmetic.  The returned probability is the mean over the draws of the class-1 probability; sample_obs=True gives
+    the reference's estimator instead, the mean of one sampled observation per draw (the convention of `eval_mcmc` / `eval_svi`); the selection always uses the
+    former.  Returns (ROC-AUC [W], proba [T, W]) numpy, and with return_params the chosen parameter dict of every problem as a third entry.  `details`, a dict,
+    receives the launch's cv_prob, test_prob, status and per-step loss, the folds and every problem's (mean_test_score, best)."""
+    n, W, F = x.shape
+    entries, cands, num_steps, num_draws = _bayes_grid()
+    cand_H, cand_lr = [h for h, _ in cands], [lr for _, lr in cands]
+    hipops.bnn_cv_check(n, test_x.shape[0], F, cand_H)
+    if not x.is_cuda:
+        raise NotImplementedError('bayes_net_metric runs on the GPU only (pfn_bnn_cv); there is no CPU path')
+    n_splits, folds, cls, operands = _fold_problems(x, y, test_x)
+    state = hipops.bnn_cv_state(W, cand_H, F, x.device, init_scale=BAYES_INIT_SCALE)
+    for c, H in enumerate(cand_H):      # candidate by candidate: the host transient is one candidate's draws
+        D = hipops.bnn_num_params(F, H)
+        state[:, c, :, 0, :D] = torch.stack([_bayes_loc0(seed, w, c, D) for w in range(W)]).to(x.device)
+    out = hipops.bnn_cv(*operands, n_splits, cand_H, cand_lr, state, num_steps, num_pred_samples=num_draws, seed=seed, sample_obs=sample_obs,
+                        want_loss=details is not None)
+    cv_prob, test_prob = out.cv_prob.double().cpu().numpy(), out.test_prob.double().cpu().numpy()
+    reported = out.test_draw.double().cpu().numpy() if sample_obs else test_prob
+    chosen = [_bayes_select(cv_prob[w], folds[w], cls[:, w], n_splits, reported[w]) for w in range(W)]
+    if details is not None:
+        details.update(cv_prob=cv_prob, test_prob=test_prob, status=out.status.cpu().numpy(), loss=out.loss.cpu().numpy(), folds=folds, n_splits=n_splits,
+                       scores=[(c[0], c[1]) for c in chosen])
+    metric, proba = _fold_metric(chosen, test_y)
+    return (metric, proba, [entries[c[1]] for c in chosen]) if return_params else (metric, proba)
+
+
+@_single_problem(_bayes_batched)
+def bayes_net_metric(x, y, test_x, test_y, cat_features):
+    """Reference tabular.py:465-478 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (ROC-AUC, proba [T]) of the
+    two-layer Bayesian neural network (fc1 -> fc2, N(0, 1) priors, mean-field Gaussian guide, 400 Adam steps on the ELBO, 400 predictive draws) that a grid search
+    over param_grid['bayes'] picks by min(5, n // 2)-fold stratified cross-validation (DESIGN.md 23, INTEGRATION.md).  `bayes_net_metric.batched` is the same for
+    many problems in one launch; `batch_pred` uses it."""

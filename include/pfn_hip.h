@@ -767,6 +767,34 @@ int pfn_stroke_prior_sample(const int32_t* labels, int B, int T, int num_classes
                             uint64_t first_dataset, float* x, int32_t* cls_n, int32_t* cls_len, int32_t* cls_start, double* cls_dir, int32_t* segs, int32_t* width,
                             uint8_t* raw, uint8_t* img, int32_t* status, void* stream);
 
+/* ---- Class-label embedding of the few-shot study (ABI 10, additive; csrc/class_embed.hip): the embedding of a model whose x-encoder is nn.Linear and whose
+ * y-encoder is encoders.CanEmb(1, C, E) -- an nn.Embedding over class labels -- forward and backward on the matrix cores (reference transformer.py:68-74):
+ *     src[t, b, :] = Wx . x[t, b, :] + bx + (t < sep ? table[labels[t, b], :] : 0)
+ * as ONE GEMM of A_aug [S B, Kp] = [x | onehot(label) on train rows | 0] against W_aug [E, Kp] = [Wx | table^T | 0], Kp = F + C rounded up to a multiple of 64,
+ * the bias in the epilogue; the backward is the transposed GEMM dW_aug = d(src)^T . A_aug and a scatter of its columns.  x [S, B, F] f32 with strides x_st,
+ * x_sb in elements (features contiguous), labels [S, B] int64 with strides l_st, l_sb; wx [E, F], bx [E], table [C, E] f32; src_sbe [S, B, E] f32 contiguous
+ * (token t B + b): the src_sbe operand of pfn_stack_forward.  prec: a PFN_PREC_* value, the operand type both GEMMs run in.
+ *   pfn_class_embed_workspace_bytes: what `workspace` must hold for this call shape (negative: an error code).
+ *   pfn_class_embed_forward: writes src_sbe and leaves A_aug in the workspace.  status: NULL, or two int32 the kernels ADD to (the caller zeroes them):
+ *     [0] train-row labels outside [0, C) -- such a row gets no class row (it equals the x-embedding) and gives the table no gradient, where torch's device
+ *     assert would abort the process; [1] values of x, wx or table beyond +-65504 under PFN_PREC_FP16: they are stored as +-65504, as everywhere in the fp16
+ *     path, and the caller is responsible for scaling inputs that large.  Labels of rows t >= sep are never read into the result.
+ *   pfn_class_embed_backward: reads the A_aug the forward left (same call shape, same workspace, as for the stack's backward) and ACCUMULATES dwx [E, F] +=,
+ *     dbx [E] +=, dtable [C, E] += (any of them NULL: skipped).  wx is accepted for a later input gradient and not read: no gradient reaches x.  Under
+ *     PFN_PREC_FP16 d(src) is cast under a power-of-two scale taken on the device from max|d(src)| and the scatter multiplies it back out, exactly.
+ *     flags bit 0: deterministic -- the weight-gradient GEMM runs without token splits, every gradient element has one writer, two runs are bit-equal.
+ *     sep == 0: dtable is not touched.
+ * Limits, checked before anything is launched: 1 <= F <= 1022, 1 <= C <= 1024, E >= 8 and E % 8 == 0, a PFN_PREC_* prec else PFN_ERR_UNSUPPORTED; B, S >= 0,
+ * B S < 2^31, 0 <= sep <= S, non-NULL pointers, a workspace of at least the stated size else PFN_ERR_ARGUMENT; workspace, src_sbe, dsrc_sbe and bx 16-byte,
+ * labels 8-byte, every other pointer 4-byte aligned else PFN_ERR_ALIGNMENT.  Every shape inside the limits runs in every precision (small or odd ones on the
+ * 128 x 128 register-staged GEMMs).  B S == 0: PFN_OK, nothing launched.  Stream-ordered, no allocation, no host synchronisation. */
+int64_t pfn_class_embed_workspace_bytes(int B, int S, int F, int E, int C, int prec);
+int pfn_class_embed_forward(const float* x, int64_t x_st, int64_t x_sb, const int64_t* labels, int64_t l_st, int64_t l_sb, const float* wx, const float* bx,
+                            const float* table, int B, int S, int F, int E, int C, int sep, int prec, int flags, void* workspace, int64_t workspace_bytes,
+                            float* src_sbe, int32_t* status, void* stream);
+int pfn_class_embed_backward(const float* dsrc_sbe, const float* wx, int B, int S, int F, int E, int C, int sep, int prec, int flags, void* workspace,
+                             int64_t workspace_bytes, float* dwx, float* dbx, float* dtable, void* stream);
+
 /* ---- single-op entry points (unit tests / profiling of individual kernels) --------------------
  * prec selects operand element type T: PFN_PREC_BF16 / PFN_PREC_FP16 (2 bytes) or PFN_PREC_F32; the LDS-DMA kernels (grouped weight gradients,
  * LayerNorm-fused GEMMs) take the two 16-bit formats only. */

@@ -150,6 +150,12 @@ SIGNATURES = {
     # (labels, B, T, num_classes, size, normalize, strokes_lo, strokes_hi, len_lo, len_hi, start_lo, start_hi, width_lo, width_hi, max_offset, max_target_offset, seed, offset,
     #  first_dataset, x, cls_n, cls_len, cls_start, cls_dir, segs, width, raw, img, status, stream)
     'pfn_stroke_prior_sample': (_I, [_P] + [_I] * 15 + [_U64] * 3 + [_P] * 11),
+    # class-label embedding of the few-shot study (ABI 10, additive).  (B, S, F, E, C, prec)
+    'pfn_class_embed_workspace_bytes': (_L, [_I] * 6),
+    # (x, x_st, x_sb, labels, l_st, l_sb, wx, bx, table, B, S, F, E, C, sep, prec, flags, workspace, workspace_bytes, src_sbe, status, stream)
+    'pfn_class_embed_forward': (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _P] + [_I] * 8 + [_P, _L, _P, _P, _P]),
+    # (dsrc_sbe, wx, B, S, F, E, C, sep, prec, flags, workspace, workspace_bytes, dwx, dbx, dtable, stream)
+    'pfn_class_embed_backward': (_I, [_P, _P] + [_I] * 8 + [_P, _L, _P, _P, _P, _P]),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

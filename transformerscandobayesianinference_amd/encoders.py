@@ -1,7 +1,9 @@
 """Input encoders (reference encoders.py). `Linear` is the one on the hot path: when both the x-
 and the y-encoder are plain `nn.Linear`, TransformerModel fuses them into the HIP embedding kernel
-(csrc/rowwise.hip: embed_fwd_kernel). Any other encoder module runs in PyTorch and its output is
-handed to the stack as a pre-embedded [S,B,E] tensor.
+(csrc/rowwise.hip: embed_fwd_kernel). A `Linear` x-encoder with a `CanEmb` over one label feature
+(`get_Canonical`: the few-shot study's model) embeds as one GEMM on the matrix cores
+(csrc/class_embed.hip, `TransformerModel._fused_class_embedding`). Any other encoder module runs
+in PyTorch and its output is handed to the stack as a pre-embedded [S,B,E] tensor.
 """
 import math
 

@@ -792,3 +792,106 @@ def stroke_prior_sample(labels, size, bounds, num_classes, seed, offset=0, first
                                                   r['segs'].data_ptr(), r['width'].data_ptr(), _hip.ptr(r.get('raw')), _hip.ptr(r.get('img')), r['status'].data_ptr(),
                                                   _hip.stream_ptr(dev)), 'pfn_stroke_prior_sample')
     return r
+
+
+# ---- class-label embedding of the few-shot study (csrc/class_embed.hip; include/pfn_hip.h pfn_class_embed_*) ----
+CLASS_EMBED_MAX_FEATURES, CLASS_EMBED_MAX_CLASSES = _hip.MAX_FEATURES, 1024
+
+
+def class_embed_supported(F, E, C):
+    """The shape limits of pfn_class_embed_* (include/pfn_hip.h)."""
+    return 1 <= F <= CLASS_EMBED_MAX_FEATURES and 1 <= C <= CLASS_EMBED_MAX_CLASSES and E >= 8 and E % 8 == 0
+
+
+def class_embed_check(x, labels, weight, bias, table, sep, precision):
+    """The argument checks of `class_embed`, raised as ValueError before the device is asked for anything.  Returns (S, B, F, E, C, sep, PFN_PREC_*)."""
+    if x.dim() != 3 or labels.dim() != 2 or tuple(labels.shape) != tuple(x.shape[:2]):
+        raise ValueError(f'class_embed: x [S, B, F] and labels [S, B], got {tuple(x.shape)} and {tuple(labels.shape)}')
+    if weight.dim() != 2 or table.dim() != 2 or bias is None or bias.dim() != 1:
+        raise ValueError('class_embed: weight [E, F], bias [E], table [C, E]')
+    S, B, F = x.shape
+    E, C = weight.shape[0], table.shape[0]
+    if weight.shape[1] != F or bias.shape[0] != E or table.shape[1] != E:
+        raise ValueError(f'class_embed: weight {tuple(weight.shape)}, bias {tuple(bias.shape)}, table {tuple(table.shape)} do not fit x with F = {F} (weight [E, F], bias [E], table [C, E])')
+    if not class_embed_supported(F, E, C):
+        raise ValueError(f'class_embed: F = {F} outside 1 .. {CLASS_EMBED_MAX_FEATURES}, C = {C} outside 1 .. {CLASS_EMBED_MAX_CLASSES}, or E = {E} below 8 / no multiple of 8')
+    if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+        raise ValueError(f'class_embed: labels are class indices, got {labels.dtype}')
+    sep = int(sep)
+    if not 0 <= sep <= S:
+        raise ValueError(f'class_embed: sep = {sep} outside 0 .. S = {S}')
+    if isinstance(precision, str):
+        if precision not in _hip.PRECISIONS:
+            raise ValueError(f'class_embed: precision {precision!r} is none of {sorted(_hip.PRECISIONS)}')
+        precision = _hip.PRECISIONS[precision]
+    if precision not in TDT:
+        raise ValueError(f'class_embed: precision {precision!r} is no PFN_PREC_* value')
+    return S, B, F, E, C, sep, precision
+
+
+def _f32_aligned(t, align=4):
+    t = t.detach()
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.float().contiguous()
+    return t.clone() if t.data_ptr() % align else t
+
+
+class _ClassEmbedFunction(torch.autograd.Function):
+    """src = class embedding (pfn_class_embed_forward); its backward is pfn_class_embed_backward.  With `model` the gradients are accumulated straight into the
+    parameters' .grad -- views of the model's flat gradient buffer, as the stack's are -- and autograd is handed None; without it they are returned."""
+
+    @staticmethod
+    def forward(ctx, x, labels, weight, bias, table, dims, deterministic, status, model):
+        S, B, F, E, C, sep, prec = dims
+        lib = _hip.lib()
+        dev = x.device
+        stream = _hip.stream_ptr(dev)
+        if x.dtype != torch.float32 or x.stride(-1) != 1 or x.data_ptr() % 4:
+            x = x.float().contiguous()
+        labels = labels.to(dev)
+        if labels.dtype != torch.int64:
+            labels = labels.long()
+        wx, bx, tb = _f32_aligned(weight), _f32_aligned(bias, 16), _f32_aligned(table)
+        ws_bytes = _hip.check(lib.pfn_class_embed_workspace_bytes(B, S, F, E, C, prec), 'pfn_class_embed_workspace_bytes')
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        src = torch.empty((S, B, E), dtype=torch.float32, device=dev)
+        flags = 1 if deterministic else 0
+        _hip.check(lib.pfn_class_embed_forward(x.data_ptr(), x.stride(0), x.stride(1), labels.data_ptr(), labels.stride(0), labels.stride(1), wx.data_ptr(), bx.data_ptr(),
+                                               tb.data_ptr(), B, S, F, E, C, sep, prec, flags, ws.data_ptr(), ws_bytes, src.data_ptr(), _hip.ptr(status), stream),
+                   'pfn_class_embed_forward')
+        ctx.state = (ws, dims, flags, model, wx, (weight, bias, table))
+        return src
+
+    @staticmethod
+    def backward(ctx, dsrc):
+        ws, (S, B, F, E, C, sep, prec), flags, model, wx, params = ctx.state
+        ctx.state = None
+        dev = ws.device
+        need = ctx.needs_input_grad[2:5]
+        dsrc = _f32_aligned(dsrc, 16)
+        if model is not None:
+            model._attach_grads()
+            outs = [p.grad if n else None for p, n in zip(params, need)]
+        else:
+            outs = [torch.zeros(p.shape, dtype=torch.float32, device=dev) if n else None for p, n in zip(params, need)]
+        _hip.check(_hip.lib().pfn_class_embed_backward(dsrc.data_ptr(), wx.data_ptr(), B, S, F, E, C, sep, prec, flags, ws.data_ptr(), ws.numel(), _hip.ptr(outs[0]),
+                                                       _hip.ptr(outs[1]), _hip.ptr(outs[2]), _hip.stream_ptr(dev)), 'pfn_class_embed_backward')
+        if model is not None:
+            outs = [None, None, None]
+        return (None, None, outs[0], outs[1], outs[2], None, None, None, None)
+
+
+def class_embed(x, labels, weight, bias, table, sep, precision, deterministic=False, status=None, _model=None):
+    """The embedding of a (Linear, CanEmb) model on the matrix cores: src [S, B, E] f32 with
+        src[t, b] = weight . x[t, b] + bias + (table[labels[t, b]] if t < sep else 0)
+    for x [S, B, F] f32 (any strides over S and B), labels [S, B] of an integer dtype, weight [E, F], bias [E], table [C, E].  `precision`: 'fp16' / 'bf16' / 'f32'
+    (or a PFN_PREC_* value), the operand type of the GEMMs.  Differentiable in weight, bias and table -- not in x.  deterministic=True: the weight-gradient GEMM
+    runs without token splits, two runs give bit-equal gradients.  status: an int32 tensor [2] on the device that the kernels add to -- [0] train-row labels
+    outside [0, C) (the row gets no class row, the table no gradient from it), [1] values beyond +-65504 stored saturated under fp16."""
+    dims = class_embed_check(x, labels, weight, bias, table, sep, precision)
+    if status is not None and (status.dtype != torch.int32 or status.numel() != 2 or not status.is_contiguous()):
+        raise ValueError('class_embed: status is a contiguous int32 tensor of two elements')
+    _hip.require_gpu_tensor(x, 'x')
+    for t, name in ((weight, 'weight'), (bias, 'bias'), (table, 'table')) + (((status, 'status'),) if status is not None else ()):
+        _hip.require_gpu_tensor(t, name)
+    return _ClassEmbedFunction.apply(x, labels, weight, bias, table, dims, bool(deterministic), status, _model)

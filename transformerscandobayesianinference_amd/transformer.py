@@ -15,7 +15,7 @@ import ctypes
 import torch
 from torch import nn
 
-from transformerscandobayesianinference_amd import _hip
+from transformerscandobayesianinference_amd import _hip, encoders, hipops
 from transformerscandobayesianinference_amd.positional_encodings import NoPositionalEncoding
 from transformerscandobayesianinference_amd.utils import SeqBN
 
@@ -298,6 +298,8 @@ class PredictContext:
 
 class TransformerModel(nn.Module):
     requires_gpu = True   # train() checks this before building anything (the host-plumbing tests substitute a CPU stand-in)
+    # (Linear, CanEmb) models -- the few-shot study's -- embed on the matrix cores (hipops.class_embed); False restores the PyTorch embedding of custom encoders
+    fuse_class_embedding = True
 
     def __init__(self, encoder, n_out, ninp, nhead, nhid, nlayers, dropout=0.0, y_encoder=None, pos_encoder=None,
                  decoder=None, input_normalization=False, precision='fp16', eval_precision='f32', deterministic=False):
@@ -400,6 +402,30 @@ class TransformerModel(nn.Module):
     def _fused_embedding(self):
         return (type(self.encoder) is nn.Linear and type(self.y_encoder) is nn.Linear and self.input_ln is None
                 and (self.pos_encoder is None or isinstance(self.pos_encoder, NoPositionalEncoding)))
+
+    def _fused_class_embedding(self):
+        """True for the few-shot study's model: an nn.Linear x-encoder and a plain encoders.CanEmb over one label feature (what `get_Canonical` builds), no SeqBN,
+        no positional encoding, a shape inside the limits of pfn_class_embed_* (include/pfn_hip.h) -- and `fuse_class_embedding` left True.  Such a model's
+        embedding runs in csrc/class_embed.hip; its parameters stay "extras" of the flat buffers (`_flatten`)."""
+        y = self.y_encoder
+        return (bool(self.fuse_class_embedding) and type(self.encoder) is nn.Linear and type(y) is encoders.CanEmb and self.encoder.bias is not None
+                and self.encoder.out_features == self.ninp and y.embedding_dim == self.ninp and y.padding_idx is None and y.max_norm is None
+                and not y.scale_grad_by_freq and not y.sparse and self.input_ln is None
+                and (self.pos_encoder is None or isinstance(self.pos_encoder, NoPositionalEncoding))
+                and hipops.class_embed_supported(self.encoder.in_features, self.ninp, y.num_embeddings))
+
+    def class_embedding_status(self):
+        """(train-row labels outside [0, C), values stored saturated under fp16) counted by the class embedding's kernels since the model was built -- the one
+        place that synchronises.  Such a label gets no class row and gives the table no gradient (include/pfn_hip.h pfn_class_embed_forward)."""
+        status = self.__dict__.get('_class_embed_status')
+        return (0, 0) if status is None else tuple(int(v) for v in status.tolist())
+
+    def _class_embed_counters(self, device):
+        status = self.__dict__.get('_class_embed_status')
+        if status is None or status.device != device:      # (a plain attribute, not a buffer: the state dict stays the reference's; a moved model carries its counts along)
+            status = torch.zeros(2, dtype=torch.int32, device=device) if status is None else status.to(device)
+            self.__dict__['_class_embed_status'] = status
+        return status
 
     def _stack_parameters(self):
         """Parameters in the order of pfn_param_layout (state-dict order of the reference model)."""
@@ -733,6 +759,14 @@ class TransformerModel(nn.Module):
             flat = flat.detach().requires_grad_(True)  # connects the node to autograd; grads go to the flat buffer directly
         if self._fused_embedding():
             out = _StackFunction.apply(flat, self, x_src, y_src.to(x_src.device), None, sep, inference)
+            return self.decoder(out) if self._custom_decoder else out
+        if self._fused_class_embedding() and not (torch.is_grad_enabled() and x_src.requires_grad):
+            # (Linear, CanEmb): the embedding as one GEMM on the matrix cores, its gradients accumulated into the flat gradient buffer (csrc/class_embed.hip); in the
+            # precision of the pass, as the stack.  An x that asks for its own gradient keeps the PyTorch embedding below.
+            prec = self.eval_precision if inference else self.precision
+            emb = hipops.class_embed(x_src, y_src.to(x_src.device), self.encoder.weight, self.encoder.bias, self.y_encoder.weight, sep, prec,
+                                     deterministic=self.deterministic, status=self._class_embed_counters(x_src.device), _model=self)
+            out = _StackFunction.apply(flat, self, None, None, emb, sep, inference)
             return self.decoder(out) if self._custom_decoder else out
         # custom encoders / positional encodings / SeqBN: PyTorch computes the embedding, HIP runs the stack
         x_emb = self.encoder(x_src)

@@ -767,6 +767,56 @@ int pfn_stroke_prior_sample(const int32_t* labels, int B, int T, int num_classes
                             uint64_t first_dataset, float* x, int32_t* cls_n, int32_t* cls_len, int32_t* cls_start, double* cls_dir, int32_t* segs, int32_t* width,
                             uint8_t* raw, uint8_t* img, int32_t* status, void* stream);
 
+/* ---- Omniglot episode loader of the few-shot study (ABI 10, additive; csrc/episode.hip): replaces the per-image loop of priors/omniglot.py:13-35 and the
+ * numpy loops of datasets/omniglotNshot.py:31-77, :172-230 over an IMAGE BANK on the device, bank [n_classes, n_img, size, size]: f32 (table == NULL) or uint8
+ * with a 256-entry f32 table (a pixel's value is table[byte]); the background is the value 0.0f in both.  Stream-ordered, no allocation, no host
+ * synchronisation, no atomics.  Every output image is: source image src = class * n_img + image; rotated by k quarter turns exactly as np.rot90(a, k,
+ * axes=(-2, -1)); the bounding box (c0, c1, r0, r1) of the pixels != 0 of the rotated image; a shift tx in [-c0, size-1-c1], ty in [-r0, size-1-r1];
+ * out[y][x] = rot[y - ty][x - tx] where that lies inside the image, else 0.0f.  The output value is the source value bit for bit.  An image without content has
+ * bbox (0, -1, 0, -1), gets tx = ty = 0 and is counted in status (the reference raises an IndexError there).
+ * Randomness: Philox4x32-10, counter = a global index, stream word = offset * 8 + purpose, key = seed; an integer in [lo, hi] is lo + mulhi(u32, hi - lo + 1),
+ * whose bias is below (hi - lo + 1) 2^-32.  Word m of a run is component m % 4 of the block at base + m / 4.
+ * pfn_episode_gather: N images from explicit parameters.  src [N], rot [N] (NULL: none) int32 -- DEVICE arrays, so the call cannot refuse their values: the
+ *   kernel clamps them to 0 .. n_classes n_img - 1 and 0 .. 3 (hipops.episode_gather checks them first).  shift_in [N,2] = (tx, ty) or NULL; given shifts are
+ *   applied as they are (clamped to +-size: content may leave the frame).  With shift_in == NULL and translate != 0 image n draws (tx, ty) from words .x, .y of
+ *   the block at counter first_image + n, purpose 5; with translate == 0 the shift is (0, 0).  Image n is written at x + n * image_stride floats (image_stride >=
+ *   size^2; floats between images are left untouched).  Returned: bbox [N,4] = (c0, c1, r0, r1), shift [N,2] as used; status [1] or NULL: images without content.
+ * pfn_episode_sample: the loader's draw for B datasets of T = n_way k_shot + 1 positions: x [T,B,size^2] f32, labels [B,T], targets [B,T] (-100 except at the
+ *   last position) and, for tests and replay, classes [B,n_way] (bank class of label j), rotations [B,n_way], src [B,T], shift [B,T,2], bbox [B,T,4],
+ *   status [B] (images without content), all int32.  Every draw is a function of (seed, offset, d = first_dataset + b): dataset b of a batch equals a call with
+ *   B = 1, first_dataset = b; image (b, t) is pfn_episode_gather's image n with first_image + n = d T + t.
+ *   A k-subset of n is drawn by the rank rule: draw j takes r = mulhi(word j, n - j), the rank of the pick among the values not yet taken (walking the taken
+ *   values in ascending order, r += 1 for each one <= r): every ordered selection has probability prod_j 1 / (n - j), each factor within (n - j) 2^-32.  A
+ *   permutation of n is Fisher-Yates: for i = n-1 .. 1 swap(a[i], a[mulhi(word n-1-i, i+1)]).
+ *   mode PFN_EPISODE_STANDARD (OmniglotNShot.load_data_cache, datasets/omniglotNshot.py:184-212): classes = the n_way-subset of the pool [pool_lo, pool_hi)
+ *     (purpose 0, base 4 d; :190); label j = position in the selection (:192); class j takes the k_shot-subset of n_img (purpose 1, base 16 (16 d + j)) and the
+ *     query class one more draw of that run (:194 draws k_shot + 1 for every class; only one query is used); rotation of class j = mulhi(word j, 4) (purpose 3,
+ *     base 4 d), applied to support and query alike (:196-202); the support positions are one permutation of the class-major list (purpose 4, base 256 d;
+ *     :207-209); the query class is mulhi(.x, n_way) of the block at counter d, purpose 2 (:210-212 permutes n_way queries of which priors/omniglot.py:61 keeps
+ *     the first).  The reference's cache of ten batches (:184) only amortises its loop: draws here are fresh on every call.
+ *   mode PFN_EPISODE_JONAS (OmniglotNShotJonas.next, :38-75): the alphabet is mulhi(.y, n_alphabets) of the block at counter d, purpose 2 (:38); the classes are
+ *     alphabet_offsets[alphabet] + a permutation of range(n_way) (purpose 0) -- the FIRST n_way classes of the alphabet, as the reference permutes range(n_way)
+ *     (:43); train != 0: images as in standard mode (:49-51); train == 0: the support is a permutation of images 0 .. k_shot-1 (purpose 1, k_shot - 1 words) and
+ *     the query class's query k_shot + mulhi(word k_shot-1, n_img - k_shot) (:53-54); no rotation; the support stays class-major and unshuffled (:68); the query
+ *     class as above (:72-75).  alphabet_offsets [n_alphabets + 1] int32 is a DEVICE array: the caller guarantees offsets[a] + n_way <= offsets[a+1] <= n_classes
+ *     (hipops checks it on the host when the bank is built; the kernel clamps a class to the bank).
+ *   PFN_ERR_UNSUPPORTED: size outside 8 .. 64, n_img outside 1 .. 64, n_way outside 1 .. 16, an unknown mode.  PFN_ERR_ARGUMENT: k_shot outside 1 .. n_img-1,
+ *   a pool outside [0, n_classes) or with fewer than n_way classes, B < 0, N < 0, B T or N or n_classes n_img >= 2^31, image_stride < size^2, jonas mode without
+ *   offsets, a NULL or misaligned buffer (4 bytes; the uint8 bank 1).  All of it before any launch; B == 0 or N == 0: PFN_OK, nothing launched. */
+#define PFN_EPISODE_MIN_SIZE 8
+#define PFN_EPISODE_MAX_SIZE 64
+#define PFN_EPISODE_MAX_WAY 16
+#define PFN_EPISODE_MAX_IMAGES 64
+#define PFN_EPISODE_STANDARD 0
+#define PFN_EPISODE_JONAS 1
+int pfn_episode_gather(const void* bank, const float* table, int n_classes, int n_img, int size, const int32_t* src, const int32_t* rot, const int32_t* shift_in,
+                       int64_t N, int translate, int64_t image_stride, uint64_t seed, uint64_t offset, uint64_t first_image, float* x, int32_t* bbox, int32_t* shift,
+                       int32_t* status, void* stream);
+int pfn_episode_sample(const void* bank, const float* table, int n_classes, int n_img, int size, int B, int n_way, int k_shot, int mode, int train, int translate,
+                       int pool_lo, int pool_hi, const int32_t* alphabet_offsets, int n_alphabets, uint64_t seed, uint64_t offset, uint64_t first_dataset, float* x,
+                       int32_t* labels, int32_t* targets, int32_t* classes, int32_t* rotations, int32_t* src, int32_t* shift, int32_t* bbox, int32_t* status,
+                       void* stream);
+
 /* ---- Class-label embedding of the few-shot study (ABI 10, additive; csrc/class_embed.hip): the embedding of a model whose x-encoder is nn.Linear and whose
  * y-encoder is encoders.CanEmb(1, C, E) -- an nn.Embedding over class labels -- forward and backward on the matrix cores (reference transformer.py:68-74):
  *     src[t, b, :] = Wx . x[t, b, :] + bx + (t < sep ? table[labels[t, b], :] : 0)

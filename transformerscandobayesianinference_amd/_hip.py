@@ -156,6 +156,12 @@ SIGNATURES = {
     'pfn_class_embed_forward': (_I, [_P, _L, _L, _P, _L, _L, _P, _P, _P] + [_I] * 8 + [_P, _L, _P, _P, _P]),
     # (dsrc_sbe, wx, B, S, F, E, C, sep, prec, flags, workspace, workspace_bytes, dwx, dbx, dtable, stream)
     'pfn_class_embed_backward': (_I, [_P, _P] + [_I] * 8 + [_P, _L, _P, _P, _P, _P]),
+    # Omniglot episode loader of the few-shot study (ABI 10, additive).  (bank, table, n_classes, n_img, size, src, rot, shift_in, N, translate, image_stride, seed,
+    #  offset, first_image, x, bbox, shift, status, stream)
+    'pfn_episode_gather': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _L, _I, _L, _U64, _U64, _U64, _P, _P, _P, _P, _P]),
+    # (bank, table, n_classes, n_img, size, B, n_way, k_shot, mode, train, translate, pool_lo, pool_hi, alphabet_offsets, n_alphabets, seed, offset, first_dataset,
+    #  x, labels, targets, classes, rotations, src, shift, bbox, status, stream)
+    'pfn_episode_sample': (_I, [_P, _P] + [_I] * 11 + [_P, _I] + [_U64] * 3 + [_P] * 10),
     'pfn_mlp_prior_forward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _U64, _U64, _P]),
     'pfn_op_gemm_nt': (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _P]),
     'pfn_op_gemm_tn': (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P]),

@@ -1,7 +1,7 @@
 """Tensor-level wrappers around the C-ABI entry points that take plain buffers (include/pfn_hip.h), on the current stream: the single-op entry points of the
 transformer stack (`pfn_op_*`: one kernel launch per call; the per-kernel parity tests tests/test_gpu_ops.py, bench.py's kernel table, tools/) and the
 studies' entry points with their tensor checks -- the GP hyper-parameter fit, NUTS, the BNN's potential, SVI and SVGD step loops, the tabular study's windows,
-AUC counts, kNN, logistic-regression and GP-classifier grid searches, and the stroke prior -- which the study modules (mcmc.py, tabular.py, priors/) build on."""
+AUC counts, kNN, logistic-regression and GP-classifier grid searches, the stroke prior and the Omniglot episode loader -- which the study modules (mcmc.py, tabular.py, priors/) build on."""
 import collections
 import ctypes
 import math
@@ -791,6 +791,127 @@ def stroke_prior_sample(labels, size, bounds, num_classes, seed, offset=0, first
                                                   r['x'].data_ptr(), r['cls_n'].data_ptr(), r['cls_len'].data_ptr(), r['cls_start'].data_ptr(), r['cls_dir'].data_ptr(),
                                                   r['segs'].data_ptr(), r['width'].data_ptr(), _hip.ptr(r.get('raw')), _hip.ptr(r.get('img')), r['status'].data_ptr(),
                                                   _hip.stream_ptr(dev)), 'pfn_stroke_prior_sample')
+    return r
+
+
+# ---- Omniglot episode loader of the few-shot study (csrc/episode.hip; include/pfn_hip.h PFN_EPISODE_*) ----
+EPISODE_MIN_SIZE, EPISODE_MAX_SIZE, EPISODE_MAX_WAY, EPISODE_MAX_IMAGES = 8, 64, 16, 64
+EPISODE_STANDARD, EPISODE_JONAS = 0, 1
+EPISODE_MODES = {'standard': EPISODE_STANDARD, 'jonas': EPISODE_JONAS}
+
+
+def episode_lds_bytes(size):
+    """Dynamic LDS of one block of the image kernel: the 256-entry table and four images with rows padded to the odd stride size | 1."""
+    return (256 + 4 * size * (size | 1)) * 4
+
+
+def episode_check(size, n_img=1, n_classes=1, n_way=1, k_shot=None, pool=None, alphabet_offsets=None):
+    """The limits of the episode kernels, raised as ValueError before the device is asked for anything.  pool: (lo, hi) of standard mode; alphabet_offsets: the
+    HOST list [A + 1] of jonas mode (the kernel gets them as a device array and cannot refuse them)."""
+    if not EPISODE_MIN_SIZE <= size <= EPISODE_MAX_SIZE:
+        raise ValueError(f'episode: size = {size} outside {EPISODE_MIN_SIZE} .. {EPISODE_MAX_SIZE} (one lane per row, a row\'s mask in 64 bits)')
+    if not 1 <= n_img <= EPISODE_MAX_IMAGES:
+        raise ValueError(f'episode: n_img = {n_img} outside 1 .. {EPISODE_MAX_IMAGES}')
+    if n_classes < 1 or n_classes * n_img >= 2 ** 31:
+        raise ValueError(f'episode: n_classes = {n_classes} below 1, or n_classes n_img >= 2^31')
+    if not 1 <= n_way <= EPISODE_MAX_WAY:
+        raise ValueError(f'episode: n_way = {n_way} outside 1 .. {EPISODE_MAX_WAY}')
+    if k_shot is not None and not 1 <= k_shot < n_img:
+        raise ValueError(f'episode: k_shot = {k_shot} outside 1 .. n_img - 1 = {n_img - 1}')
+    if pool is not None and not (0 <= pool[0] and pool[1] <= n_classes and pool[1] - pool[0] >= n_way):
+        raise ValueError(f'episode: the pool [{pool[0]}, {pool[1]}) must lie in [0, {n_classes}) and hold at least n_way = {n_way} classes')
+    if alphabet_offsets is not None:
+        o = [int(v) for v in alphabet_offsets]
+        if len(o) < 2 or o[0] < 0 or o[-1] > n_classes or any(b - a < n_way for a, b in zip(o, o[1:])):
+            raise ValueError(f'episode: alphabet offsets {o} must ascend inside [0, {n_classes}] with at least n_way = {n_way} classes per alphabet')
+
+
+def _episode_bank(bank, table=None):
+    """(images [C, n_img, size, size] on the GPU, table or None) of an ImageBank-like object (fields images, table) or of a plain tensor."""
+    images = getattr(bank, 'images', bank)
+    table = getattr(bank, 'table', table)
+    if images.dim() != 4 or images.shape[2] != images.shape[3] or images.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('bank [n_classes, n_img, size, size], uint8 (with a table) or float32')
+    if (images.dtype == torch.uint8) != (table is not None):
+        raise ValueError('a uint8 bank needs its 256-entry f32 table, an f32 bank takes none')
+    episode_check(images.shape[2], images.shape[1], images.shape[0])
+    assert images.is_contiguous(), 'bank: contiguous'
+    if table is not None:
+        assert table.dtype == torch.float32 and tuple(table.shape) == (256,) and table.is_contiguous() and table.device == images.device, 'table: [256] f32 beside the bank'
+    return images, table
+
+
+def episode_gather(bank, src, rot=None, shift=None, table=None, out=None, seed=0, offset=0, first_image=0, check=True, want_status=True):
+    """N images of the bank, rotated and shifted (pfn_episode_gather): src [N] (class * n_img + image), rot [N] quarter turns or None, int32 on the GPU;
+    shift: None (no shift), 'draw' (the kernel draws it inside each image's range from Philox at counter first_image + n) or [N, 2] int32 = (tx, ty).  Returns a
+    dict: x [N, size^2] f32 -- image n written to out[n] when `out` ([N, >= size^2] f32, rows contiguous) is given --, bbox [N, 4] = (c0, c1, r0, r1), shift
+    [N, 2] as used, status [1] (images without content; None without `want_status`, which saves the counting launch).  `check` reads back the range of src
+    and rot first (one synchronisation) and raises ValueError outside the bank / 0 .. 3; without it the kernel clamps them."""
+    images, table = _episode_bank(bank, table)
+    C, n_img, size = images.shape[0], images.shape[1], images.shape[2]
+    dev, px = images.device, size * size
+    if src.dim() != 1 or (rot is not None and rot.shape != src.shape):
+        raise ValueError('src [N], rot [N]')
+    N = src.shape[0]
+    draw = isinstance(shift, str)
+    if draw and shift != 'draw':
+        raise ValueError("shift: None, 'draw' or [N, 2] int32")
+    shift_in = None if (draw or shift is None) else shift
+    if shift_in is not None and tuple(shift_in.shape) != (N, 2):
+        raise ValueError('shift [N, 2]')
+    _hip.require_gpu_tensor(images, 'bank')
+    for t, name in ((src, 'src'), (rot, 'rot'), (shift_in, 'shift')):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.device == dev), f'{name}: contiguous int32 on {dev}'
+    if check and N:
+        probe = [src.min(), src.max()] + ([rot.min(), rot.max()] if rot is not None else [])
+        lo_hi = [int(v) for v in torch.stack(probe).tolist()]
+        if lo_hi[0] < 0 or lo_hi[1] >= C * n_img:
+            raise ValueError(f'episode: src outside 0 .. {C * n_img - 1}')
+        if rot is not None and (lo_hi[2] < 0 or lo_hi[3] > 3):
+            raise ValueError('episode: rot outside 0 .. 3')
+    if out is None:
+        out = torch.empty(N, px, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.device == dev and out.dim() == 2 and out.shape[0] == N and out.shape[1] >= px and (N == 0 or out.stride(1) == 1), \
+        'out: [N, >= size^2] f32 with contiguous rows'
+    i32 = dict(dtype=torch.int32, device=dev)
+    r = dict(x=out, bbox=torch.empty(N, 4, **i32), shift=torch.empty(N, 2, **i32), status=torch.zeros(1, **i32) if want_status else None)
+    _hip.check(_hip.lib().pfn_episode_gather(images.data_ptr(), _hip.ptr(table), C, n_img, size, src.data_ptr(), _hip.ptr(rot), _hip.ptr(shift_in), N, int(draw),
+                                             out.stride(0) if N > 1 else out.shape[1], int(seed) & (2 ** 64 - 1), int(offset), int(first_image), out.data_ptr(),
+                                             r['bbox'].data_ptr(), r['shift'].data_ptr(), _hip.ptr(r['status']), _hip.stream_ptr(dev)), 'pfn_episode_gather')
+    return r
+
+
+def episode_sample(bank, B, n_way, k_shot, mode, train, translate, seed, offset=0, first_dataset=0, num_classes_used=None):
+    """One batch of the episode loader (pfn_episode_sample) from an ImageBank (priors.omniglot.ImageBank: images, table, n_train_classes and the alphabet
+    offsets of both splits, on the host and on the device).  mode: 'standard' or 'jonas'.  standard: the train pool is [0, num_classes_used) (default:
+    n_train_classes), the test pool [n_train_classes, n_classes).  Returns a dict: x [T, B, size^2] f32, labels, targets [B, T], classes, rotations [B, n_way],
+    src [B, T], shift [B, T, 2], bbox [B, T, 4], status [B], the integers int32."""
+    images, table = _episode_bank(bank)
+    C, n_img, size = images.shape[0], images.shape[1], images.shape[2]
+    mode_id = EPISODE_MODES[mode] if isinstance(mode, str) else int(mode)
+    pool, offsets, offsets_host = (0, 0), None, None
+    if mode_id == EPISODE_STANDARD:
+        pool = (0, min(int(bank.n_train_classes if num_classes_used is None else num_classes_used), C)) if train else (int(bank.n_train_classes), C)
+    else:
+        offsets = bank.train_alphabet_offsets if train else bank.test_alphabet_offsets
+        offsets_host = bank.alphabet_offsets_host(train)
+        if offsets is None:
+            raise ValueError('episode: jonas mode needs the alphabet offsets of the split (ImageBank.from_arrays(..., train_alphabet_offsets, test_alphabet_offsets))')
+        assert offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.device == images.device and offsets.numel() == len(offsets_host)
+    episode_check(size, n_img, C, n_way, k_shot, pool if mode_id == EPISODE_STANDARD else None, offsets_host)
+    T, dev, px = n_way * k_shot + 1, images.device, size * size
+    if B < 0 or B * T >= 2 ** 31:
+        raise ValueError(f'episode: B = {B} below 0 or B T >= 2^31')
+    _hip.require_gpu_tensor(images, 'bank')
+    i32 = dict(dtype=torch.int32, device=dev)
+    r = dict(x=torch.empty(T, B, px, dtype=torch.float32, device=dev), labels=torch.empty(B, T, **i32), targets=torch.empty(B, T, **i32),
+             classes=torch.empty(B, n_way, **i32), rotations=torch.empty(B, n_way, **i32), src=torch.empty(B, T, **i32), shift=torch.empty(B, T, 2, **i32),
+             bbox=torch.empty(B, T, 4, **i32), status=torch.empty(B, **i32))
+    _hip.check(_hip.lib().pfn_episode_sample(images.data_ptr(), _hip.ptr(table), C, n_img, size, B, n_way, k_shot, mode_id, int(bool(train)), int(bool(translate)),
+                                             pool[0], pool[1], _hip.ptr(offsets), 0 if offsets is None else offsets.numel() - 1, int(seed) & (2 ** 64 - 1), int(offset),
+                                             int(first_dataset), r['x'].data_ptr(), r['labels'].data_ptr(), r['targets'].data_ptr(), r['classes'].data_ptr(),
+                                             r['rotations'].data_ptr(), r['src'].data_ptr(), r['shift'].data_ptr(), r['bbox'].data_ptr(), r['status'].data_ptr(),
+                                             _hip.stream_ptr(dev)), 'pfn_episode_sample')
     return r
 
 

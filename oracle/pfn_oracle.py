@@ -232,7 +232,7 @@ class _Sites(_NoSites):
         """_linear(x, w, b) whose WEIGHT gradient contracts the rounded x (site 'xaug'): value, d/dx and d/db of the plain product"""
         if not self.on('xaug'):
             return _linear(x, w, b)
-        shadow = self('xaug', x) @ w.t()
+        shadow = self('xaug', x.detach()) @ w.t()      # (detached: an x that asks for its own gradient gets it from the plain product alone)
         return _linear(x, w.detach(), b) + (shadow - shadow.detach())
 
     def softmax(self, scores):

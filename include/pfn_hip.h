@@ -887,7 +887,9 @@ int pfn_op_attention_fwd(const void* qkv, void* ctx, float* lse, int B, int S, i
 /* Attention backward = three launches: delta = rowsum(dO * O); the key-block pass (dK, dV and dS^T into ds_ws); the
  * query-block pass (dQ from ds_ws, plus the self-key terms of the test rows).  ds_ws: pfn_op_attention_bwd_ws_bytes(B, S, H,
  * prec) bytes of scratch; delta_ws: 2 * B * H * S floats (the first launch leaves [delta | lse in log2 units] there).  parts: 0 = all, else a bit mask (1 delta, 2 key-block pass, 4 query-block pass) that lets bench.py
- * time every launch on its own; a partial run leaves the outputs of the skipped launches untouched. */
+ * time every launch on its own; a partial run leaves the outputs of the skipped launches untouched.
+ * sep == 0 (no train rows, no dropout): one launch instead, under the query-block bit -- dV = dO, dQ = dK = 0 exactly.  delta_ws is then NOT written (parts = 1
+ * alone launches nothing): without keys no launch reads it. */
 int64_t pfn_op_attention_bwd_ws_bytes(int B, int S, int H, int prec);
 int pfn_op_attention_bwd(const void* qkv, const void* ctx, const float* lse, const void* dctx,
                          void* dqkv, float* delta_ws, void* ds_ws, int B, int S, int E, int H, int sep,

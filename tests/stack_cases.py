@@ -52,6 +52,7 @@ def _matrix():
     add('e256', ['default', 'deterministic'])
     add('e1024', ['default', 'fuse_ln_wide', 'deterministic'], only={'fuse_ln_wide': ('bf16', 'fp16')})
     add('e128', ['default'], t=300, seps=(257,))                                  # q_begin 256: a skipped query block, scatter_rows with zero_from
+    add('e128', ['default', 'deterministic'], seps=(0,))                          # no train rows: attn_bwd_self_only_kernel after the fused delta (zero_delta) / in place of attn_delta_kernel
     add('e128', ['default', 'deterministic'], kind='ragged', seps=RAGGED_SEPS)    # ragged sep_of: gather, scatter and zero prefix per dataset
     add('e256', ['default', 'deterministic'], kind='ragged', seps=RAGGED_SEPS)
     add('e64', ['default'], seps=(64,), dropout=0.3)                              # the three element-wise dropout sites and the attention masks
@@ -64,7 +65,8 @@ MATRIX = _matrix()
 
 def case_id(row):
     shape, prec, sched, kind, t, seps, dropout = row
-    return '-'.join([shape, prec, sched] + ([kind] if kind != 'single' else []) + ([f'T{t}'] if t != T else []) + ([f'p{dropout}'] if dropout else []))
+    return '-'.join([shape, prec, sched] + ([kind] if kind != 'single' else []) + ([f'T{t}'] if t != T else []) + ([f'p{dropout}'] if dropout else []) +
+                    (['sep0'] if seps == (0,) else []))
 
 
 def dims(shape, precision):

@@ -9,6 +9,7 @@ import math
 import pytest
 import torch
 
+from attn_probe_cases import attention_reference      # dense masked attention in f64 (shared with the planted-key suite)
 from transformerscandobayesianinference_amd import _hip
 from transformerscandobayesianinference_amd import hipops
 
@@ -396,22 +397,6 @@ def test_layernorm(rows, E, prec):
     none32, dxt2, dg2, db2, _ = hipops.layernorm_bwd(dy_t, x, gamma, mean, rstd, prec, want_f32=False)
     assert none32 is None and relerr(dxt2, xd2.grad) < tol(prec, 4e-3, 5e-4, 1e-5)
     assert relerr(db2, dy_t.double().sum(0)) < 1e-5
-
-
-def attention_reference(qkv, H, sep):
-    """Dense masked attention in f64 with the mask of generate_D_q_matrix (transformer.py:34-41)."""
-    B, S, E3 = qkv.shape
-    E = E3 // 3
-    D = E // H
-    q, k, v = [t.view(B, S, H, D).transpose(1, 2) for t in qkv.double().split(E, dim=-1)]  # [B,H,S,D]
-    scores = q @ k.transpose(-1, -2) / math.sqrt(D)
-    allowed = torch.zeros(S, S, dtype=torch.bool, device=qkv.device)
-    allowed[:, :sep] = True
-    allowed |= torch.eye(S, dtype=torch.bool, device=qkv.device)
-    scores = scores.masked_fill(~allowed, float('-inf'))
-    lse = torch.logsumexp(scores, -1)
-    out = torch.softmax(scores, -1) @ v
-    return out.transpose(1, 2).reshape(B, S, E), lse
 
 
 ATTN_CASES = [  # B, S, E, H, sep

@@ -1898,10 +1898,41 @@ int64_t attn_bwd_ds_bytes(int B, int S, int H, int precision) {
   attn_bwd_ds_dims(S, S, &rows, &ld);
   return (int64_t)B * H * rows * ld * prec_esize(precision);
 }
+// No train rows at all (sep = 0, one eval position, no dropout): every query sees its own key alone, P = 1, and the backward is dV = dO, dQ = dK = 0 EXACTLY.
+// The general kernels return dS = P (dP - delta) there, a difference of two f32 sums of the same products in different orders: ~2^-24 |dP| of noise in dQ and dK
+// (tests/test_gpu_attn_probe.py, S130-sep0).  This pass stands in for the query-block pass, which at sep = 0 writes all of dqkv (the key-block pass has no keys
+// and is not launched); delta and lse2 have no reader then, so attn_delta_kernel is not launched either, and AttnArgs::zero_delta is honoured as that pass
+// honours it.  One sweep over dqkv, 16 bytes per thread step; row widths are multiples of 16 bytes (check_attn).
+__global__ void attn_bwd_self_only_kernel(const uint4* __restrict__ dctx, uint4* __restrict__ dqkv, long rows, int chunks, float* __restrict__ delta, long ndelta) {
+  const long total = rows * 3 * chunks;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long row = i / (3 * chunks);
+    const int c = (int)(i - row * 3 * chunks);
+    dqkv[i] = c >= 2 * chunks ? dctx[row * chunks + (c - 2 * chunks)] : make_uint4(0u, 0u, 0u, 0u);
+  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < ndelta; i += (long)gridDim.x * blockDim.x) delta[i] = 0.f;      // (ndelta = 0 unless zero_delta)
+}
+static int launch_bwd_self_only(const AttnArgs& a, int precision, hipStream_t s) {
+  const int parts = a.parts ? a.parts : ~0;
+  if (!(parts & ATTN_BWD_DQ)) return PFN_OK;
+  if (!a.dctx || !a.dqkv || (a.zero_delta && !a.delta)) return PFN_ERR_ARGUMENT;
+  const long rows = (long)a.B * a.S;
+  const int chunks = a.E * prec_esize(precision) / 16;
+  const int grid = (int)std::min<long>((rows * 3 * chunks + 255) / 256, 4096);
+  ProfScope ps(PFN_PROF_ATTN_BWD_DQ, s);
+  hipLaunchKernelGGL(attn_bwd_self_only_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const uint4*>(a.dctx), reinterpret_cast<uint4*>(a.dqkv), rows, chunks,
+                     a.delta, a.zero_delta ? (long)a.B * a.H * a.S : 0L);
+  return hipGetLastError() == hipSuccess ? PFN_OK : PFN_ERR_LAUNCH;
+}
 int launch_attn_bwd(const AttnArgs& a_in, int precision, hipStream_t s) {
   int rc = check_attn(a_in, precision);
   if (rc != PFN_OK) return rc;
   if (!a_in.ds) return PFN_ERR_ARGUMENT;
+  if (a_in.sep == 0 && !a_in.sep_of && a_in.q_begin == 0 && a_in.p_drop == 0.f) {
+    const int D = a_in.E / a_in.H;
+    if (D != 32 && D != 64 && D != 128 && D != 256) return PFN_ERR_UNSUPPORTED;      // (the head dims of PFN_ATTN_DISPATCH: no shape gains support here)
+    return launch_bwd_self_only(a_in, precision, s);
+  }
   AttnArgs a = a_in;
   attn_bwd_ds_dims(a.S, a.sep, &a.ds_rows, &a.ds_ld);
   a.q_begin = a.q_begin / 256 * 256;

@@ -712,6 +712,54 @@ int pfn_bnn_cv(const float* train, const float* labels, const float* test, const
                uint64_t seed, const int64_t* problem_ids, float* loss, float* cv_prob, float* test_prob, float* cv_draw, float* test_draw, int32_t* status,
                void* stream);
 
+/* ---- Gradient-boosted trees with their grid search (ABI 10, additive; csrc/xgb_cv.hip): the reference's xgb_metric (tabular.py:599-626) as a batch of
+ * independent fits of the exact greedy algorithm on logistic loss.  f32 data, caller-owned buffers, stream-ordered, no allocation, no host synchronisation, no
+ * atomics.  No boosting library is carried or compared against: this text is the specification.
+ *
+ * pfn_xgb_cv: P problems; train [P,n,F], labels [P,n] (class y = label > 0.5), test [P,T,F], fold [P,n] int32 (the CV test fold of each train row), all on the
+ *   device; NC candidates as HOST arrays read before the call returns: cand_depth int32, cand_lr f32 (eta), cand_mcw, cand_subsample, cand_colsample f64, cand_ids
+ *   int32 or NULL (0 .. NC-1).  Two launches: the sort orders, then one block per fit (problem p, candidate c, slot s): slot s < n_splits trains on the rows with
+ *   fold[p,i] != s, slot s = n_splits on all rows (the refit), slots beyond are unused (status PFN_XGB_CV_UNUSED, nothing else written).  A row whose fold value
+ *   is outside 0 .. n_splits - 1 trains every slot and is held out by none.
+ * order [P,F,n] uint8, caller-owned workspace: the first launch writes the stable argsort of every column over all n rows, key (value, row index).
+ * A fit: every margin starts at 0.  Round t = 0 .. num_rounds - 1:
+ *   p = sigmoid(margin), g = p - y, h = p (1 - p) in f32, then gi = rint(g 2^23), hi = rint(h 2^23) as int32; every sum of them is an integer sum.
+ *   Row sample: train row i of the slot is in iff its word < floor(subsample 2^32).  Column sample: the k = max(1, floor(colsample F)) features of smallest
+ *   (word, feature index).  With B(idx) = philox4x32_10(idx, stream = ((problem_ids[p] or p) * 64 + (cand_ids[c] or c)) * 8 + s, key = seed):
+ *     word of row i     = component i & 3 of B((t << 6) | (i >> 2))                 (i: the row's index among the n rows of the window)
+ *     word of feature f = component f & 3 of B(2^32 | (t << 6) | (f >> 2))
+ *   The tree grows level by level to cand_depth.  A node's candidates: for every sampled feature, between two consecutive DISTINCT values a < b in the feature's
+ *   sorted order of the node's sampled rows.  With the integer sums of the two sides scaled by 2^-23 (int -> f32 conversion, then the product), lambda = 1:
+ *     legal iff HLi >= mcwi and HRi >= mcwi,  mcwi = rint(min_child_weight 2^23)  (formed in f64 on the host, compared as integers)
+ *     gain = (GL^2 / (HL + 1) + GR^2 / (HR + 1)) - G^2 / (H + 1) in f32, every operation rounded once
+ *   The node splits on the legal candidate of largest gain if that gain > 1e-6; among bit-equal gains the lowest feature index, then the lowest position wins.
+ *   Threshold thr = 0.5f (a + b) in f32, and b where that equals a; a row goes left iff x < thr.  Leaf value -eta G / (H + 1) = eta * -(G / (H + 1)) over the
+ *   leaf's sampled rows (0 with none).  Every train row (sampled or not, held out or not) and, in the refit slot, every test row takes margin += leaf value.
+ * Outputs: slot s < n_splits writes the final margins of its held-out rows (fold == s) into cv_margin [P,NC,n] -- a row in no fold is never written --, the refit
+ *   slot those of the test rows into test_margin [P,NC,T].  status [P,NC,6] int32: PFN_XGB_CV_UNUSED, PFN_XGB_CV_DONE, or PFN_XGB_CV_NONFINITE where a value the
+ *   fit read or a final margin is not finite (NaN is refused, not treated as missing: such a fit's numbers mean nothing).
+ *   tree_feature / tree_threshold [P,NC,6,num_rounds,3] and tree_leaf [P,NC,6,num_rounds,4] (all three or all NULL): per round the root and its left and right
+ *   child (feature, or -1 where the node does not split, then threshold 0), and the leaf values by code 2 (right of the root) + (right of the child); a node
+ *   that does not split keeps its rows at the code of its left side.  The unused slots are never written.
+ * A fit is a bitwise function of its own problem, candidate parameters, slot, ids and seed, wherever it sits in the call and however problems and candidates
+ *   are grouped into calls.
+ * 4 <= n <= 128, 1 <= T <= 128, 1 <= F <= 128, 1 <= NC <= PFN_XGB_CV_MAX_CANDIDATES, 0 <= num_rounds <= PFN_XGB_CV_MAX_ROUNDS, every 1 <= cand_depth <=
+ *   PFN_XGB_CV_MAX_DEPTH, subsample and colsample in (0, 1], min_child_weight >= 0, learning rate > 0, else PFN_ERR_UNSUPPORTED; P >= 1, 2 <= n_splits <= 5,
+ *   non-NULL train, labels, test, fold, the five candidate arrays, order, cv_margin, test_margin, status, the tree buffers all or none, every candidate number
+ *   finite, 0 <= cand_ids < 64, else PFN_ERR_ARGUMENT; the limits are checked first, all of it before any device pointer is read and before any HIP call. */
+#define PFN_XGB_CV_FOLDS 5
+#define PFN_XGB_CV_SLOTS 6
+#define PFN_XGB_CV_MAX_CANDIDATES 64
+#define PFN_XGB_CV_MAX_DEPTH 2
+#define PFN_XGB_CV_MAX_ROUNDS 4096
+#define PFN_XGB_CV_UNUSED 0
+#define PFN_XGB_CV_DONE 1
+#define PFN_XGB_CV_NONFINITE 2
+int pfn_xgb_cv(const float* train, const float* labels, const float* test, const int32_t* fold, const int32_t* cand_depth, const float* cand_lr,
+               const double* cand_mcw, const double* cand_subsample, const double* cand_colsample, const int32_t* cand_ids, int P, int n, int T, int F, int NC,
+               int n_splits, int num_rounds, uint64_t seed, const int64_t* problem_ids, uint8_t* order, float* cv_margin, float* test_margin, int32_t* status,
+               int32_t* tree_feature, float* tree_threshold, float* tree_leaf, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

@@ -141,6 +141,9 @@ SIGNATURES = {
     # BNN classifier with its grid search (ABI 10, additive).  (train, labels, test, fold, cand_H (host), cand_lr (host), P, n, T, F, NC, n_splits, state, ld, step0,
     #  num_steps, beta1, beta2, eps, num_pred_samples, seed, problem_ids, loss, cv_prob, test_prob, cv_draw, test_draw, status, stream)
     'pfn_bnn_cv': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _L, _I, _F, _F, _F, _I, _U64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # Gradient-boosted trees with their grid search (ABI 10, additive).  (train, labels, test, fold, cand_depth, cand_lr, cand_mcw, cand_subsample, cand_colsample,
+    # cand_ids, P, n, T, F, NC, n_splits, num_rounds, seed, problem_ids, order, cv_margin, test_margin, status, tree_feature, tree_threshold, tree_leaf, stream)
+    'pfn_xgb_cv': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # GP classifier with its grid search (ABI 10, additive).  (theta, train, labels, fold, P, n, F, NC, n_splits, value, grad, status, stream)
     'pfn_gpc_lml_grad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     # (theta, train, labels, test, fold, P, n, T, F, NC, n_splits, cv_f, test_f, test_var, status, stream)

@@ -666,6 +666,56 @@ def bnn_cv(train, labels, test, fold, n_splits, cand_H, cand_lr, state, num_step
     return BnnCvOut(loss, cv_prob, test_prob, cv_draw, test_draw, status)
 
 
+# ---- Gradient-boosted trees with their grid search (csrc/xgb_cv.hip; include/pfn_hip.h "Gradient-boosted trees with their grid search") ----
+XGB_CV_FOLDS, XGB_CV_SLOTS, XGB_CV_MAX_CANDIDATES, XGB_CV_MAX_DEPTH, XGB_CV_MAX_ROUNDS = 5, 6, 64, 2, 4096      # PFN_XGB_CV_*
+XGB_CV_UNUSED, XGB_CV_DONE, XGB_CV_NONFINITE = 0, 1, 2            # status
+XGB_CV_LIMITS = dict(n=(4, 128), T=(1, 128), F=(1, 128), NC=(1, XGB_CV_MAX_CANDIDATES), max_depth=(1, XGB_CV_MAX_DEPTH), num_rounds=(0, XGB_CV_MAX_ROUNDS))
+XgbCvOut = collections.namedtuple('XgbCvOut', 'cv_margin test_margin status tree_feature tree_threshold tree_leaf')
+
+
+def xgb_cv_check(n, T, F, cand_depth, num_rounds=0):
+    """The limits of a pfn_xgb_cv launch, raised as ValueError before any launch.  cand_depth: the candidates' max_depth.  Host only."""
+    cand_depth = [int(d) for d in cand_depth]
+    _limits_check('xgb_cv', XGB_CV_LIMITS, n=n, T=T, F=F, NC=len(cand_depth), num_rounds=int(num_rounds))
+    for d in cand_depth:
+        _limits_check('xgb_cv', XGB_CV_LIMITS, max_depth=d)
+
+
+def xgb_cv(train, labels, test, fold, n_splits, cand_depth, cand_lr, cand_mcw, cand_subsample, cand_colsample, num_rounds, seed=0, problem_ids=None,
+           want_trees=False, cand_ids=None):
+    """Every boosting round of every fit of a gradient-boosting grid search in one launch (pfn_xgb_cv, after a small launch that sorts the columns): train [P,n,F],
+    labels [P,n], test [P,T,F] f32 and fold [P,n] int32 on the GPU; cand_*: the NC candidates' max_depth, learning_rate, min_child_weight, subsample and
+    colsample_bytree (host sequences), cand_ids their ids in the noise addressing (None: 0 .. NC-1).  Slot s < n_splits of a candidate is the fit without fold
+    s, slot n_splits the refit on all rows.  Returns XgbCvOut(cv_margin [P,NC,n] (written at the held-out rows of the slots in use; NaN elsewhere), test_margin
+    [P,NC,T], status [P,NC,6] int32, and with want_trees tree_feature int32 / tree_threshold f32 [P,NC,6,num_rounds,3] and tree_leaf [P,NC,6,num_rounds,4], else
+    None)."""
+    import numpy as np
+    cand_depth, cand_lr = [int(d) for d in cand_depth], [float(v) for v in cand_lr]
+    cand_mcw, cand_subsample, cand_colsample = ([float(v) for v in seq] for seq in (cand_mcw, cand_subsample, cand_colsample))
+    NC, num_rounds = len(cand_depth), int(num_rounds)
+    cand_ids = list(range(NC)) if cand_ids is None else [int(v) for v in cand_ids]
+    if not all(len(seq) == NC for seq in (cand_lr, cand_mcw, cand_subsample, cand_colsample, cand_ids)) or \
+            not all(math.isfinite(v) and v > 0 for v in cand_lr) or not all(math.isfinite(v) and v >= 0 for v in cand_mcw) or \
+            not all(0 < v <= 1 for v in cand_subsample + cand_colsample) or not all(0 <= v < XGB_CV_MAX_CANDIDATES for v in cand_ids):
+        raise ValueError('cand_depth, cand_lr > 0, cand_mcw >= 0, cand_subsample and cand_colsample in (0, 1], cand_ids in 0 .. 63: [NC] each, all finite')
+    P, n, T, F = _fold_args(lambda n, T, F, NC: xgb_cv_check(n, T, F, cand_depth, num_rounds), train, labels, fold, test, NC=NC, splits=(n_splits, XGB_CV_FOLDS))
+    dev = train.device
+    if problem_ids is not None:
+        assert problem_ids.dtype == torch.int64 and problem_ids.shape == (P,) and problem_ids.is_contiguous() and problem_ids.device == dev
+    new = lambda *shape: torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
+    cv_margin, test_margin = new(P, NC, n), new(P, NC, T)
+    status = torch.zeros(P, NC, XGB_CV_SLOTS, dtype=torch.int32, device=dev)
+    order = torch.zeros(P, F, n, dtype=torch.uint8, device=dev)
+    tree_feature = torch.full((P, NC, XGB_CV_SLOTS, num_rounds, 3), -1, dtype=torch.int32, device=dev) if want_trees else None
+    tree_threshold, tree_leaf = (new(P, NC, XGB_CV_SLOTS, num_rounds, 3), new(P, NC, XGB_CV_SLOTS, num_rounds, 4)) if want_trees else (None, None)
+    host = [np.asarray(cand_depth, dtype=np.int32), np.asarray(cand_lr, dtype=np.float32), np.asarray(cand_mcw, dtype=np.float64),
+            np.asarray(cand_subsample, dtype=np.float64), np.asarray(cand_colsample, dtype=np.float64), np.asarray(cand_ids, dtype=np.int32)]      # read before the call returns
+    _hip.check(_hip.lib().pfn_xgb_cv(train.data_ptr(), labels.data_ptr(), test.data_ptr(), fold.data_ptr(), *(h.ctypes.data for h in host), P, n, T, F, NC, int(n_splits),
+                                     num_rounds, int(seed), _hip.ptr(problem_ids), order.data_ptr(), cv_margin.data_ptr(), test_margin.data_ptr(), status.data_ptr(),
+                                     _hip.ptr(tree_feature), _hip.ptr(tree_threshold), _hip.ptr(tree_leaf), _hip.stream_ptr(dev)), 'pfn_xgb_cv')
+    return XgbCvOut(cv_margin, test_margin, status, tree_feature, tree_threshold, tree_leaf)
+
+
 # ---- GP classifier with its grid search (csrc/gpc.hip; include/pfn_hip.h "GP classifier") ----
 GPC_FOLDS, GPC_SLOTS, GPC_MAX_CANDIDATES, GPC_MAX_N, GPC_MAX_NEWTON = 5, 6, 64, 112, 100
 GPC_UNUSED, GPC_CONVERGED, GPC_CAPPED, GPC_ONE_CLASS, GPC_NONPOSITIVE, GPC_NONFINITE = 0, 1, 2, 3, 4, 5      # status[..., 0]

@@ -26,7 +26,11 @@ of every window in one launch per L-BFGS pass (`priors.fast_gp_mix.batched_lbfgs
 runs the 400 SVI steps and the 400 predictive draws of every candidate and fold of every window in one launch (pfn_bnn_cv): the model, the guide
 and the step are those of the BNN study's `eval_svi`; the folds, the starts, the scores and the selection are host arithmetic.  The reference's own grid search
 raises on two keys of param_grid['bayes'] that are no constructor arguments; what it evidently means is built here.
-The gradient-boosting baselines of the reference (XGBoost, CatBoost: :505-677) and the OpenML loaders stay out: they need libraries and network access this stack
+    xgb_metric (with its grid search over 16 boosting parameter sets) :599-626
+restates the exact greedy algorithm of gradient-boosted trees on logistic loss (depth 1 or 2, 100 rounds, row and column sampling from Philox) and runs every
+round of every candidate and fold of every window in one launch (pfn_xgb_cv); the grid, the 5 folds, the scores and the selection are host
+arithmetic in f64.  No boosting library is carried, so nothing is pinned to one: include/pfn_hip.h is the specification.
+CatBoost (:505-596) and the OpenML loaders stay out: they need libraries and network access this stack
 does not carry.  Any callable with the reference's metric-function
 signature still runs through `batch_pred`, one window at a time, as the reference loops.
 
@@ -352,12 +356,13 @@ def batch_pred(metric_function, eval_xs, eval_ys, categorical_feats, start=2, ta
 ## What the baseline arms share (kNN, logistic regression, GP classifier), each arm handing in what is its own: the problems before the launch, GridSearchCV's
 ## ranking, the tail after the selection, the single-problem form
 
-def _fold_problems(x, y, test_x, one_class_error=None):
+def _fold_problems(x, y, test_x, one_class_error=None, n_splits=None):
     """Before the launch, for W problems: x [n, W, F] normalised train rows, y [n, W], test_x [T, W, F] -> (n_splits = min(CV, n // 2), folds [W, n] int32: every
     row's test fold, cls [n, W] bool: label > 0.5, both on the host, and the kernels' operands on x's device: (train [W, n, F], labels [W, n], test [W, T, F] f32,
-    fold [W, n] int32)).  one_class_error: the arm's name where a window whose train rows hold one class raises ValueError, as scikit-learn's fit does."""
+    fold [W, n] int32)).  one_class_error: the arm's name where a window whose train rows hold one class raises ValueError, as scikit-learn's fit does.
+    n_splits: the number of folds where the arm does not take min(CV, n // 2) (xgb_metric passes cv=5 whatever n is)."""
     n, W, _ = x.shape
-    n_splits = min(CV, n // 2)
+    n_splits = min(CV, n // 2) if n_splits is None else int(n_splits)
     cls = y.detach().cpu().numpy() > 0.5
     if one_class_error is not None:
         for w in range(W):
@@ -728,3 +733,70 @@ def bayes_net_metric(x, y, test_x, test_y, cat_features):
     two-layer Bayesian neural network (fc1 -> fc2, N(0, 1) priors, mean-field Gaussian guide, 400 Adam steps on the ELBO, 400 predictive draws) that a grid search
     over param_grid['bayes'] picks by min(5, n // 2)-fold stratified cross-validation (DESIGN.md 23, INTEGRATION.md).  `bayes_net_metric.batched` is the same for
     many problems in one launch; `batch_pred` uses it."""
+
+
+## Gradient-boosted trees (reference tabular.py:599-626)
+
+param_grid['xgb'] = {'min_child_weight': [0.5, 1.0], 'learning_rate': [0.02, 0.2], 'subsample': [0.5, 0.8], 'max_depth': [1, 2], 'colsample_bytree': [0.8],
+                     'eval_metric': ['logloss'], 'n_estimators': [100]}
+XGB_FOLDS = 5      # the reference passes cv=5, not min(CV, n // 2)
+
+
+def _xgb_grid(grid=None):
+    """The reference's grid as the device runs it: (entries, num_rounds).  `entries` are the parameter dicts in sklearn's ParameterGrid order (keys sorted, the
+    last key varying fastest: subsample, then min_child_weight, max_depth, learning_rate).  'n_estimators' and 'colsample_bytree' are read from the entry --
+    'n_estimators' holds one value, a launch has one round count --, 'eval_metric' is accepted and ignored: it scores nothing here."""
+    import itertools
+    grid = param_grid['xgb'] if grid is None else grid
+    if len(grid['n_estimators']) != 1:
+        raise ValueError("param_grid['xgb']: 'n_estimators' holds one value")
+    keys = sorted(grid)
+    entries = [dict(zip(keys, values)) for values in itertools.product(*(grid[k] for k in keys))]
+    return entries, int(grid['n_estimators'][0])
+
+
+def _xgb_select(cv_margin, folds, cls, n_splits, test_margin):
+    """The host half of one problem's grid search, in f64: cv_margin [NC, n] every train row's final margin from the fit that held it out, folds [n] the rows'
+    test folds, cls [n] bool, test_margin [NC, T] of the refits.  As GridSearchCV scores an XGBClassifier: a fold's score is the share of its rows with
+    (margin > 0) == class (proba exactly 0.5 predicts class 0), a candidate's score the mean over folds, the best candidate the FIRST maximum (NaN ranks last).
+    Returns (mean_test_score [NC] f64, best index, proba [T] f64 = sigmoid(margin) of the best candidate's refit)."""
+    cv_margin, folds, cls = np.asarray(cv_margin, dtype=np.float64), np.asarray(folds), np.asarray(cls, dtype=bool)
+    right = (cv_margin > 0) == cls[None, :]
+    sizes = _fold_sizes(folds, n_splits)
+    scores = np.stack([right[:, folds == s].sum(1) / sizes[s] for s in range(n_splits)], 1)
+    scores[np.stack([np.isnan(cv_margin[:, folds == s]).any(1) for s in range(n_splits)], 1)] = np.nan      # a fit that left the finite numbers
+    mean, best = _first_maximum(scores)
+    return mean, best, 1. / (1. + np.exp(-np.asarray(test_margin, dtype=np.float64)[best]))
+
+
+def _xgb_batched(x, y, test_x, test_y, return_params=False, seed=0, details=None):
+    """Gradient-boosted trees with the reference's grid search for W problems at once: x [n, W, F] normalised train rows, y [n, W], test_x [T, W, F], test_y [T, W]
+    on the GPU.  One pfn_xgb_cv launch runs the 100 rounds of all W x 16 x 6 fits; the 5 stratified folds (before) and the scores and the selection (after) are
+    host arithmetic.  Returns (accuracy [W] -- ((proba > 0.5) == test_y).mean() as the reference's xgb_metric computes it, not ROC-AUC --, proba [T, W]) numpy, and
+    with return_params the chosen parameter dict of every problem as a third entry.  `details`, a dict, receives the launch's margins, status and trees, the folds
+    and every problem's (mean_test_score, best)."""
+    n, W, F = x.shape
+    entries, num_rounds = _xgb_grid()
+    depth = [int(e['max_depth']) for e in entries]
+    hipops.xgb_cv_check(n, test_x.shape[0], F, depth, num_rounds)
+    if not x.is_cuda:
+        raise NotImplementedError('xgb_metric runs on the GPU only (pfn_xgb_cv); there is no CPU path')
+    n_splits, folds, cls, operands = _fold_problems(x, y, test_x, n_splits=XGB_FOLDS)
+    out = hipops.xgb_cv(*operands, n_splits, depth, [e['learning_rate'] for e in entries], [e['min_child_weight'] for e in entries],
+                        [e['subsample'] for e in entries], [e['colsample_bytree'] for e in entries], num_rounds, seed=seed, want_trees=details is not None)
+    cv_margin, test_margin = out.cv_margin.double().cpu().numpy(), out.test_margin.double().cpu().numpy()
+    chosen = [_xgb_select(cv_margin[w], folds[w], cls[:, w], n_splits, test_margin[w]) for w in range(W)]
+    if details is not None:
+        details.update(cv_margin=cv_margin, test_margin=test_margin, status=out.status.cpu().numpy(), folds=folds, n_splits=n_splits,
+                       trees=tuple(t.cpu().numpy() for t in out[3:]), scores=[(c[0], c[1]) for c in chosen])
+    proba = np.stack([c[2] for c in chosen], 1)
+    metric = ((proba > 0.5) == (test_y.detach().cpu().numpy() > 0.5)).astype(np.float64).mean(0)
+    return (metric, proba, [entries[c[1]] for c in chosen]) if return_params else (metric, proba)
+
+
+@_single_problem(_xgb_batched)
+def xgb_metric(x, y, test_x, test_y, cat_features):
+    """Reference tabular.py:610-626 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (accuracy, proba [T]) of the
+    gradient-boosted trees (exact greedy splits, logistic loss, 100 rounds) that a grid search over param_grid['xgb'] picks by 5-fold stratified cross-validation
+    (INTEGRATION.md).  cat_features is accepted and ignored, as in the reference's call.  `xgb_metric.batched` is the same for many problems in one
+    launch; `batch_pred` uses it."""

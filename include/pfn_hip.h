@@ -760,6 +760,66 @@ int pfn_xgb_cv(const float* train, const float* labels, const float* test, const
                int n_splits, int num_rounds, uint64_t seed, const int64_t* problem_ids, uint8_t* order, float* cv_margin, float* test_margin, int32_t* status,
                int32_t* tree_feature, float* tree_threshold, float* tree_leaf, void* stream);
 
+/* ---- Oblivious boosted trees with their grid search (ABI 10, additive; csrc/catboost_cv.hip): the reference's catboost_metric (tabular.py:556-596) as a batch
+ * of independent fits of symmetric (oblivious) trees on logistic loss.  f32 data, caller-owned buffers, stream-ordered, no allocation, no host synchronisation,
+ * no atomics.  No boosting library is carried or compared against: this text is the specification (INTEGRATION.md lists what it restates from memory).
+ *
+ * pfn_catboost_cv: P problems; train [P,n,F], labels [P,n] (class y = label > 0.5), test [P,T,F], fold [P,n] int32, all on the device; NC candidates as HOST
+ *   arrays read before the call returns: cand_depth int32, cand_lr f32, cand_l2 f32, cand_ids int32 or NULL (0 .. NC-1); checkpoints: a HOST array of
+ *   1 <= NK <= 8 ascending tree counts >= 1, the last equal to num_rounds.  Two launches: the sort orders, then one block per fit (problem p, candidate c,
+ *   slot s): slot 0, the search fit, learns on the rows with fold != 0; slot 1, the refit, learns on all rows.
+ * order [P,F,n] uint8, caller-owned workspace: the first launch writes the stable argsort of every column over all n rows, key (value, row index).
+ * A fit, m its number of learn rows: every margin starts at 0; no row or column sampling.  sig(z) = (z >= 0 ? 1 : e) / (1 + e) with e = exp(-|z|).  Every f32
+ *   operation below is rounded once (no fused multiply-add).
+ * Borders: for every feature, between two consecutive distinct values a < b of the fit's learn rows in the column's sorted order: thr = 0.5f (a + b) in f32,
+ *   and a where that equals b; a row's bit is 1 iff x > thr.  The border's position j is the sorted position (over all n rows) of the last learn row that holds a.
+ * Tree t = 0 .. num_rounds - 1: p = sig(margin), g = y - p in f32, gi = rint(g 2^23) as int32 over the learn rows; every per-leaf sum of gi and every count is
+ *   an integer sum.  S2 = sum gi^2 (an integer).  The tree grows level by level, d = 0 .. depth - 1; one (feature, border) splits all leaves of a level and the
+ *   row's leaf code gains bit d.  A candidate is every (feature, border) not already used in this tree; with none left the tree ends at the levels it has.
+ *   Score of a candidate: over the leaves of the level so far in ascending code, those without learn rows left out, the two children low (bit 0) and high (bit
+ *   1) with integer sums Gi and counts c:  G = (float)Gi * 2^-23, avg = c > 0 ? G / ((float)c + l2) : 0, and four running f32 sums from 0,
+ *     num_lo += avg G, den_lo += (avg avg) c over the low children, num_hi, den_hi over the high ones (an empty child adds nothing);
+ *     num = num_lo + num_hi, den = den_lo + den_hi, score = den > 0 ? num / sqrt(den) : 0.
+ *   Noise: sigma_t = sqrt(((float)S2 * 2^-46) / (float)m) * (L / (1 + L)), L = exp(log((float)m) - (float)t * lr), in f32.  With B(idx) = philox4x32_10(idx,
+ *     stream = ((problem_ids[p] or p) * 64 + (cand_ids[c] or c)) * 8 + s, key = seed) and (w0, w1) the first two words of B((t << 17) | (d << 14) | (f << 7) | j):
+ *     u1 = ((w0 >> 9) + 0.5) 2^-23, u2 = (w1 >> 8) 2^-24 (both exact in f32), z = sqrt(-2 log u1) * cos(pi * (2 u2)).  The compared value is score + sigma_t * z;
+ *     the largest wins, among bit-equal values the lowest feature, then the lowest position.
+ *   Leaf values, over the leaves that hold learn rows (any other leaf has value 0): v = 0, obj = objective(v), then at most 10 Newton iterations:
+ *     per learn row z = margin + v_leaf, r = y ? sig(-z) : -sig(z) (that is y - sig(z), without the cancellation), h = sig(z) sig(-z); ri = rint(r 2^40),
+ *     hi = rint(h 2^40) as int64 (2^40, not 2^23: a saturated leaf's h is a few units of 2^-23, and a step would stand on their rounding); per leaf the integer
+ *     sums R, H:  den = (float)H * 2^-40 + l2,  step = den > 0 ? ((float)R * 2^-40) / den : 0.
+ *     Backtracking ("AnyImprovement"): for scale = 1, 1/2, .., 2^-10:  try_leaf = v_leaf + scale * step_leaf;  the first scale with objective(try) <= obj is
+ *     taken (v = try, obj = objective(try)); with none the iteration loop ends with v as it was.
+ *     objective(v) = (float)(sum over the learn rows of rint(loss 2^40) as int64) * 2^-40 + (0.5f * l2) * pen,  loss = max(y ? -z : z, 0) + log1p(exp(-|z|)) at
+ *     z = margin + v_leaf,  pen = the f32 sum of v_leaf^2 from 0 over the leaves with learn rows in ascending code.
+ *   Then every row of the window (learn or held out) and, in the refit slot, every test row takes margin += lr * v_leaf (its leaf by its own bits).
+ * Outputs: after tree checkpoints[k] - 1, slot 0 writes the margins of the rows with fold == 0 into hold_margin [P,NC,NK,n] (the other rows are never written),
+ *   slot 1 those of the test rows into test_margin [P,NC,NK,T].  status [P,NC,2] int32: PFN_CATBOOST_CV_DONE; PFN_CATBOOST_CV_NONFINITE where a value of the
+ *   window's rows (or, in slot 1, the test rows) is not finite -- NaN is refused, not treated as missing -- or a final margin is not; PFN_CATBOOST_CV_ONE_CLASS
+ *   where the learn rows hold one class (the library raises there).  A fit that is NONFINITE by its inputs or ONE_CLASS writes nothing but its status.
+ *   tree_feature int32 / tree_threshold f32 [P,NC,2,num_rounds,7] and tree_leaf [P,NC,2,num_rounds,128] (all three or all NULL): per tree and level the chosen
+ *   feature and threshold (-1 and 0 for a level the tree does not have), and lr * v by leaf code (0 for a leaf without learn rows).
+ * Nothing in a fit depends on the trees after it: the margins at checkpoint k are those of a launch with num_rounds = checkpoints[k].  A fit is a bitwise
+ *   function of its own problem, candidate parameters, slot, ids and seed, wherever it sits in the call and however problems and candidates are grouped.
+ * 4 <= n <= 128, 1 <= T <= 128, 1 <= F <= 128, 1 <= NC <= PFN_CATBOOST_CV_MAX_CANDIDATES, 1 <= num_rounds <= PFN_CATBOOST_CV_MAX_ROUNDS, every 1 <= cand_depth
+ *   <= PFN_CATBOOST_CV_MAX_DEPTH, else PFN_ERR_UNSUPPORTED; P >= 1, non-NULL train, labels, test, fold, the three candidate arrays, checkpoints, order,
+ *   hold_margin, test_margin, status, the tree buffers all or none, 1 <= NK <= 8 with the checkpoints as above, every l2 >= 0 and finite, every learning rate
+ *   > 0 and finite, 0 <= cand_ids < 64, else PFN_ERR_ARGUMENT; the limits are checked first, all of it before any device pointer is read and before any HIP
+ *   call. */
+#define PFN_CATBOOST_CV_SLOTS 2
+#define PFN_CATBOOST_CV_MAX_CANDIDATES 64
+#define PFN_CATBOOST_CV_MAX_DEPTH 7
+#define PFN_CATBOOST_CV_MAX_LEAVES 128
+#define PFN_CATBOOST_CV_MAX_ROUNDS 1024
+#define PFN_CATBOOST_CV_MAX_CHECKPOINTS 8
+#define PFN_CATBOOST_CV_DONE 1
+#define PFN_CATBOOST_CV_NONFINITE 2
+#define PFN_CATBOOST_CV_ONE_CLASS 3
+int pfn_catboost_cv(const float* train, const float* labels, const float* test, const int32_t* fold, const int32_t* cand_depth, const float* cand_lr,
+                    const float* cand_l2, const int32_t* cand_ids, const int32_t* checkpoints, int P, int n, int T, int F, int NC, int NK, int num_rounds,
+                    uint64_t seed, const int64_t* problem_ids, uint8_t* order, float* hold_margin, float* test_margin, int32_t* status, int32_t* tree_feature,
+                    float* tree_threshold, float* tree_leaf, void* stream);
+
 /* ---- BNN prior sampler: replaces the per-dataset module forwards of priors.mlp.get_batch (priors/mlp.py:116-124
  * network, :150-157 forward of the non-causal branch, :195-197 Python loop over datasets).  For dataset b with model
  * m = model_of[b]:  h_0 = causes W_0^T + b_0;  h_l = act(h_{l-1}) W_l^T + b_l + noise_std[m] * eps_l  (1 <= l < L_m);

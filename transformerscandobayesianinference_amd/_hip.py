@@ -144,6 +144,9 @@ SIGNATURES = {
     # Gradient-boosted trees with their grid search (ABI 10, additive).  (train, labels, test, fold, cand_depth, cand_lr, cand_mcw, cand_subsample, cand_colsample,
     # cand_ids, P, n, T, F, NC, n_splits, num_rounds, seed, problem_ids, order, cv_margin, test_margin, status, tree_feature, tree_threshold, tree_leaf, stream)
     'pfn_xgb_cv': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # Oblivious boosted trees with their grid search (ABI 10, additive).  (train, labels, test, fold, cand_depth, cand_lr, cand_l2, cand_ids, checkpoints, P, n, T, F,
+    # NC, NK, num_rounds, seed, problem_ids, order, hold_margin, test_margin, status, tree_feature, tree_threshold, tree_leaf, stream)
+    'pfn_catboost_cv': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     # GP classifier with its grid search (ABI 10, additive).  (theta, train, labels, fold, P, n, F, NC, n_splits, value, grad, status, stream)
     'pfn_gpc_lml_grad': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     # (theta, train, labels, test, fold, P, n, T, F, NC, n_splits, cv_f, test_f, test_var, status, stream)

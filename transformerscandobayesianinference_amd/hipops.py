@@ -716,6 +716,61 @@ def xgb_cv(train, labels, test, fold, n_splits, cand_depth, cand_lr, cand_mcw, c
     return XgbCvOut(cv_margin, test_margin, status, tree_feature, tree_threshold, tree_leaf)
 
 
+# ---- Oblivious boosted trees with their grid search (csrc/catboost_cv.hip; include/pfn_hip.h "Oblivious boosted trees with their grid search") ----
+CATBOOST_CV_SLOTS, CATBOOST_CV_MAX_CANDIDATES, CATBOOST_CV_MAX_DEPTH, CATBOOST_CV_MAX_LEAVES = 2, 64, 7, 128      # PFN_CATBOOST_CV_*
+CATBOOST_CV_MAX_ROUNDS, CATBOOST_CV_MAX_CHECKPOINTS = 1024, 8
+CATBOOST_CV_DONE, CATBOOST_CV_NONFINITE, CATBOOST_CV_ONE_CLASS = 1, 2, 3      # status
+CATBOOST_CV_LIMITS = dict(n=(4, 128), T=(1, 128), F=(1, 128), NC=(1, CATBOOST_CV_MAX_CANDIDATES), depth=(1, CATBOOST_CV_MAX_DEPTH),
+                          num_rounds=(1, CATBOOST_CV_MAX_ROUNDS))
+CatboostCvOut = collections.namedtuple('CatboostCvOut', 'hold_margin test_margin status tree_feature tree_threshold tree_leaf')
+
+
+def catboost_cv_check(n, T, F, cand_depth, num_rounds=1):
+    """The limits of a pfn_catboost_cv launch, raised as ValueError before any launch.  cand_depth: the candidates' depths.  Host only."""
+    cand_depth = [int(d) for d in cand_depth]
+    _limits_check('catboost_cv', CATBOOST_CV_LIMITS, n=n, T=T, F=F, NC=len(cand_depth), num_rounds=int(num_rounds))
+    for d in cand_depth:
+        _limits_check('catboost_cv', CATBOOST_CV_LIMITS, depth=d)
+
+
+def catboost_cv(train, labels, test, fold, cand_depth, cand_lr, cand_l2, num_rounds, checkpoints=None, seed=0, problem_ids=None, want_trees=False, cand_ids=None):
+    """Every tree of every fit of an oblivious-tree grid search in one launch (pfn_catboost_cv, after a small launch that sorts the columns): train [P,n,F],
+    labels [P,n], test [P,T,F] f32 and fold [P,n] int32 (0: held out of the search fit) on the GPU; cand_*: the NC candidates' depth, learning_rate and
+    l2_leaf_reg (host sequences), cand_ids their ids in the noise addressing (None: 0 .. NC-1); checkpoints: ascending tree counts, the last num_rounds (None:
+    num_rounds alone).  Slot 0 of a candidate learns on the rows with fold != 0, slot 1 on all rows.  Returns CatboostCvOut(hold_margin [P,NC,NK,n] (written at
+    the rows with fold == 0; NaN elsewhere), test_margin [P,NC,NK,T], status [P,NC,2] int32, and with want_trees tree_feature int32 / tree_threshold f32
+    [P,NC,2,num_rounds,7] and tree_leaf [P,NC,2,num_rounds,128], else None).  A fit whose status is not CATBOOST_CV_DONE leaves its margins NaN."""
+    import numpy as np
+    cand_depth, cand_lr, cand_l2 = [int(d) for d in cand_depth], [float(v) for v in cand_lr], [float(v) for v in cand_l2]
+    NC, num_rounds = len(cand_depth), int(num_rounds)
+    cand_ids = list(range(NC)) if cand_ids is None else [int(v) for v in cand_ids]
+    checkpoints = [num_rounds] if checkpoints is None else [int(k) for k in checkpoints]
+    if not all(len(seq) == NC for seq in (cand_lr, cand_l2, cand_ids)) or not all(math.isfinite(v) and v > 0 for v in cand_lr) or \
+            not all(math.isfinite(v) and v >= 0 for v in cand_l2) or not all(0 <= v < CATBOOST_CV_MAX_CANDIDATES for v in cand_ids):
+        raise ValueError('cand_depth, cand_lr > 0, cand_l2 >= 0, cand_ids in 0 .. 63: [NC] each, all finite')
+    NK = len(checkpoints)
+    if not 1 <= NK <= CATBOOST_CV_MAX_CHECKPOINTS or checkpoints[0] < 1 or any(b <= a for a, b in zip(checkpoints, checkpoints[1:])) or checkpoints[-1] != num_rounds:
+        raise ValueError(f'checkpoints: 1 .. {CATBOOST_CV_MAX_CHECKPOINTS} ascending tree counts >= 1, the last equal to num_rounds = {num_rounds}')
+    P, n, T, F = _fold_args(lambda n, T, F, NC: catboost_cv_check(n, T, F, cand_depth, num_rounds), train, labels, fold, test, NC=NC)
+    dev = train.device
+    if problem_ids is not None:
+        assert problem_ids.dtype == torch.int64 and problem_ids.shape == (P,) and problem_ids.is_contiguous() and problem_ids.device == dev
+    new = lambda *shape: torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
+    hold_margin, test_margin = new(P, NC, NK, n), new(P, NC, NK, T)
+    status = torch.zeros(P, NC, CATBOOST_CV_SLOTS, dtype=torch.int32, device=dev)
+    order = torch.zeros(P, F, n, dtype=torch.uint8, device=dev)
+    tree_feature = torch.full((P, NC, CATBOOST_CV_SLOTS, num_rounds, CATBOOST_CV_MAX_DEPTH), -1, dtype=torch.int32, device=dev) if want_trees else None
+    tree_threshold = new(P, NC, CATBOOST_CV_SLOTS, num_rounds, CATBOOST_CV_MAX_DEPTH) if want_trees else None
+    tree_leaf = new(P, NC, CATBOOST_CV_SLOTS, num_rounds, CATBOOST_CV_MAX_LEAVES) if want_trees else None
+    host = [np.asarray(cand_depth, dtype=np.int32), np.asarray(cand_lr, dtype=np.float32), np.asarray(cand_l2, dtype=np.float32),
+            np.asarray(cand_ids, dtype=np.int32), np.asarray(checkpoints, dtype=np.int32)]      # read before the call returns
+    _hip.check(_hip.lib().pfn_catboost_cv(train.data_ptr(), labels.data_ptr(), test.data_ptr(), fold.data_ptr(), *(h.ctypes.data for h in host), P, n, T, F, NC, NK,
+                                          num_rounds, int(seed), _hip.ptr(problem_ids), order.data_ptr(), hold_margin.data_ptr(), test_margin.data_ptr(),
+                                          status.data_ptr(), _hip.ptr(tree_feature), _hip.ptr(tree_threshold), _hip.ptr(tree_leaf), _hip.stream_ptr(dev)),
+               'pfn_catboost_cv')
+    return CatboostCvOut(hold_margin, test_margin, status, tree_feature, tree_threshold, tree_leaf)
+
+
 # ---- GP classifier with its grid search (csrc/gpc.hip; include/pfn_hip.h "GP classifier") ----
 GPC_FOLDS, GPC_SLOTS, GPC_MAX_CANDIDATES, GPC_MAX_N, GPC_MAX_NEWTON = 5, 6, 64, 112, 100
 GPC_UNUSED, GPC_CONVERGED, GPC_CAPPED, GPC_ONE_CLASS, GPC_NONPOSITIVE, GPC_NONFINITE = 0, 1, 2, 3, 4, 5      # status[..., 0]

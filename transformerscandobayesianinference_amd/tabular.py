@@ -30,7 +30,12 @@ raises on two keys of param_grid['bayes'] that are no constructor arguments; wha
 restates the exact greedy algorithm of gradient-boosted trees on logistic loss (depth 1 or 2, 100 rounds, row and column sampling from Philox) and runs every
 round of every candidate and fold of every window in one launch (pfn_xgb_cv); the grid, the 5 folds, the scores and the selection are host
 arithmetic in f64.  No boosting library is carried, so nothing is pinned to one: include/pfn_hip.h is the specification.
-CatBoost (:505-596) and the OpenML loaders stay out: they need libraries and network access this stack
+    catboost_metric (with its grid search over 81 parameter sets)    :556-596
+restates CatBoost's symmetric trees on logistic loss (Cosine score with its random strength, Newton leaf values with backtracking, depth 2, 4 or 7) and grows
+every tree of every distinct fit of every window in one launch (pfn_catboost_cv): 'iterations' only cuts a fit short, so the 81 entries are 27
+fits read at three checkpoints.  The grid, the stratified 80/20 hold-out that the library's grid_search scores the entries on, the log losses and the selection
+are host arithmetic in f64; everything about the library is restated from memory and pinned to nothing.
+The OpenML loaders stay out: they need libraries and network access this stack
 does not carry.  Any callable with the reference's metric-function
 signature still runs through `batch_pred`, one window at a time, as the reference loops.
 
@@ -800,3 +805,111 @@ def xgb_metric(x, y, test_x, test_y, cat_features):
     gradient-boosted trees (exact greedy splits, logistic loss, 100 rounds) that a grid search over param_grid['xgb'] picks by 5-fold stratified cross-validation
     (INTEGRATION.md).  cat_features is accepted and ignored, as in the reference's call.  `xgb_metric.batched` is the same for many problems in one
     launch; `batch_pred` uses it."""
+
+
+## CatBoost (reference tabular.py:556-596)
+
+param_grid['catboost'] = {'learning_rate': [0.1, 0.5, 1.0], 'depth': [2, 4, 7], 'l2_leaf_reg': [0.0, 0.5, 1], 'iterations': [10, 40, 70]}
+CATBOOST_HOLDOUT = 0.2      # grid_search's train_size = 0.8
+
+
+def _catboost_grid(grid=None):
+    """The reference's grid as the device runs it: (entries, fits, where, checkpoints).  `entries` are the 81 parameter dicts in the order CatBoost's grid_search
+    walks them: the dict's key order, the last key ('iterations') varying fastest.  Nothing in a fit depends on 'iterations' -- tree t is grown from the margins
+    after tree t - 1 and from draws addressed by t --, so a fit of 70 trees contains those of 10 and 40 as prefixes: `fits` are the 27 distinct (learning_rate,
+    depth, l2_leaf_reg) in order of first appearance, `where[e]` = (fit, checkpoint) of entry e, `checkpoints` the ascending tree counts (10, 40, 70)."""
+    import itertools
+    grid = param_grid['catboost'] if grid is None else grid
+    keys = list(grid)
+    entries = [dict(zip(keys, values)) for values in itertools.product(*(grid[k] for k in keys))]
+    checkpoints = sorted({int(v) for v in grid['iterations']})
+    fits, where = [], []
+    for e in entries:
+        key = (float(e['learning_rate']), int(e['depth']), float(e['l2_leaf_reg']))
+        if key not in fits:
+            fits.append(key)
+        where.append((fits.index(key), checkpoints.index(int(e['iterations']))))
+    return entries, fits, where, checkpoints
+
+
+def _philox4x32_10(idx, stream, seed):
+    """Philox4x32-10 on the host, as csrc/pfn_device.h: counter (idx, stream) as two 64-bit halves, key = seed.  Returns four 32-bit words."""
+    M = 0xFFFFFFFF
+    c0, c1, c2, c3 = idx & M, (idx >> 32) & M, stream & M, (stream >> 32) & M
+    k0, k1 = seed & M, (seed >> 32) & M
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & M, p1 & M, ((p0 >> 32) ^ c3 ^ k1) & M, p0 & M
+        k0, k1 = (k0 + 0x9E3779B9) & M, (k1 + 0xBB67AE85) & M
+    return c0, c1, c2, c3
+
+
+def _catboost_holdout(y, seed, window):
+    """CatBoost's grid_search as recalled: by default it does NOT cross-validate the candidates; it trains each on a shuffled stratified 80 % of
+    the rows and scores it on the other 20 % by the loss function -- `cv=5` only feeds statistics the reference discards -- and refits the best on all rows.  The
+    library's own shuffle is not restated: per class, floor(0.2 count + 0.5) rows are held out, at least 1 where the class has 2 or more, namely those of smallest
+    (word, row index), row i's word being component i & 3 of philox4x32_10(i >> 2, stream = window, key = seed).  Returns fold [n] int32: 0 = held out, 1 = kept."""
+    cls = np.asarray(y).reshape(-1) > 0.5
+    words = np.array([_philox4x32_10(i >> 2, int(window), int(seed))[i & 3] for i in range(len(cls))], dtype=np.int64)
+    fold = np.ones(len(cls), dtype=np.int32)
+    for k in (False, True):
+        idx = np.flatnonzero(cls == k)
+        count = int(np.floor(CATBOOST_HOLDOUT * len(idx) + 0.5))
+        if len(idx) >= 2:
+            count = max(count, 1)
+        fold[idx[np.lexsort((idx, words[idx]))[:count]]] = 0
+    return fold
+
+
+def _catboost_select(hold_margin, fold, cls, where, test_margin):
+    """The host half of one problem's grid search, in f64: hold_margin [fits, NK, n] the margins of the search fits at every checkpoint, fold [n] (0 = held out),
+    cls [n] bool, where = every entry's (fit, checkpoint), test_margin [fits, NK, T] of the refits.  An entry's score is the mean log loss of the held-out rows;
+    a NaN (a fit that did not run or left the finite numbers) ranks last, the FIRST minimum wins.  Returns (log loss [entries] f64, best entry, proba [T] f64 =
+    sigmoid(margin) of the best entry's refit at its checkpoint)."""
+    hold_margin, cls = np.asarray(hold_margin, dtype=np.float64), np.asarray(cls, dtype=bool)
+    held = np.asarray(fold) == 0
+    z = np.where(cls[held], -1., 1.) * hold_margin[:, :, held]
+    with np.errstate(invalid='ignore'):      # (a NaN margin is a NaN loss: it ranks last)
+        per_fit = np.logaddexp(0., z).mean(-1) if held.any() else np.full(hold_margin.shape[:2], np.nan)
+    loss = np.array([per_fit[c, k] for c, k in where], dtype=np.float64)
+    best = int(np.argmin(np.where(np.isnan(loss), np.inf, loss)))
+    c, k = where[best]
+    return loss, best, 1. / (1. + np.exp(-np.asarray(test_margin, dtype=np.float64)[c, k]))
+
+
+def _catboost_batched(x, y, test_x, test_y, return_params=False, seed=0, details=None):
+    """CatBoost with the reference's grid search for W problems at once: x [n, W, F] normalised train rows, y [n, W], test_x [T, W, F], test_y [T, W] on the GPU.
+    One pfn_catboost_cv launch grows the 70 trees of all W x 27 x 2 fits (the search fit on the kept 80 %, the refit on all rows) and writes their margins at 10,
+    40 and 70 trees; the hold-out (before) and the 81 log losses and the selection (after) are host arithmetic.  Returns (ROC-AUC [W], proba [T, W]) numpy, and
+    with return_params the chosen parameter dict of every problem as a third entry.  `details`, a dict, receives the launch's margins, status and trees, the
+    folds and every problem's (log losses, best)."""
+    n, W, F = x.shape
+    entries, fits, where, checkpoints = _catboost_grid()
+    depth = [d for _, d, _ in fits]
+    hipops.catboost_cv_check(n, test_x.shape[0], F, depth, checkpoints[-1])
+    if not x.is_cuda:
+        raise NotImplementedError('catboost_metric runs on the GPU only (pfn_catboost_cv); there is no CPU path')
+    cls = y.detach().cpu().numpy() > 0.5
+    for w in range(W):
+        if cls[:, w].all() or not cls[:, w].any():
+            raise ValueError(f'catboost_metric: the train rows of window {w} hold one class only')
+    folds = np.stack([_catboost_holdout(cls[:, w], seed, w) for w in range(W)])
+    out = hipops.catboost_cv(x.float().transpose(0, 1).contiguous(), y.float().t().contiguous(), test_x.float().transpose(0, 1).contiguous(),
+                             torch.from_numpy(folds).to(x.device), depth, [lr for lr, _, _ in fits], [l2 for _, _, l2 in fits], checkpoints[-1],
+                             checkpoints=checkpoints, seed=seed, want_trees=details is not None)
+    hold_margin, test_margin = out.hold_margin.double().cpu().numpy(), out.test_margin.double().cpu().numpy()
+    chosen = [_catboost_select(hold_margin[w], folds[w], cls[:, w], where, test_margin[w]) for w in range(W)]
+    if details is not None:
+        details.update(hold_margin=hold_margin, test_margin=test_margin, status=out.status.cpu().numpy(), folds=folds,
+                       trees=tuple(t.cpu().numpy() for t in out[3:]), scores=[(c[0], c[1]) for c in chosen])
+    metric, proba = _fold_metric(chosen, test_y)
+    return (metric, proba, [entries[c[1]] for c in chosen]) if return_params else (metric, proba)
+
+
+@_single_problem(_catboost_batched)
+def catboost_metric(x, y, test_x, test_y, categorical_feats):
+    """Reference tabular.py:561-596 for one problem: x [n, F] (normalised) train rows, y [n], test_x [T, F], test_y [T] on the GPU -> (ROC-AUC, proba [T]) of the
+    boosted symmetric trees (logistic loss, Cosine score, Newton leaves) that a grid search over the 81 entries of param_grid['catboost'] picks by the log loss on
+    a stratified 20 % hold-out and refits on all rows.  categorical_feats is accepted and ignored: the reference casts those
+    columns to int and never passes them as cat_features, so every column is numeric.  `catboost_metric.batched` is the same for many problems in one launch;
+    `batch_pred` uses it."""

@@ -1011,6 +1011,15 @@ int pfn_op_attention_fwd_from(const void* qkv, void* ctx, float* lse, int B, int
 int pfn_op_attention_bwd_from(const void* qkv, const void* ctx, const float* lse, const void* dctx,
                               void* dqkv, float* delta_ws, void* ds_ws, int B, int S, int E, int H, int sep, int q_begin,
                               int prec, int parts, void* stream);
+/* TEST ONLY: pfn_op_attention_fwd / pfn_op_attention_bwd with dropout on the attention probabilities, P' = P keep / (1 - p_drop), the way a training step with
+ * dropout > 0 runs them.  drop_seed is the SITE seed of the layer's attention (what the stack derives from its call seed and the layer); the kernels mix the
+ * (dataset, head) index b * H + h in themselves and regenerate keep(seed, query, key) from indices in every pass.  p_drop == 0 is exactly the pair above;
+ * p_drop outside [0, 1) is PFN_ERR_ARGUMENT.  (ABI 10, additive: detect by symbol.) */
+int pfn_op_attention_fwd_dropout(const void* qkv, void* ctx, float* lse, int B, int S, int E, int H, int sep,
+                                 int prec, float p_drop, uint32_t drop_seed, void* stream);
+int pfn_op_attention_bwd_dropout(const void* qkv, const void* ctx, const float* lse, const void* dctx,
+                                 void* dqkv, float* delta_ws, void* ds_ws, int B, int S, int E, int H, int sep,
+                                 int prec, int parts, float p_drop, uint32_t drop_seed, void* stream);
 /* Rows of [B, S] token order <-> the decoder's compact test-row order [(S - sep), B] (row bytes a multiple of 4); the scatter
  * writes zeros into rows [zero_from, sep) and leaves rows below zero_from alone. */
 int pfn_op_gather_rows(const void* src_bs, void* dst_tb, int B, int S, int64_t row_bytes, int sep, void* stream);

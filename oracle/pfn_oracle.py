@@ -64,6 +64,11 @@ def dropout_site_seed(seed, layer, site):
     return int(_mix32(int(_mix32((seed & _M32) ^ ((0x9E3779B1 * (layer * 4 + site + 1)) & _M32))) ^ (seed >> 32)))
 
 
+def dropout_pair_seed(site_seed, pair):
+    """the seed of one (dataset, head) pair's attention mask, pair = b * H + h"""
+    return int(_mix32((site_seed & _M32) ^ ((0xC2B2AE35 * (pair + 1)) & _M32)))
+
+
 def dropout_keep_mask(site_seed, rows, cols, p):
     """keep[i, j] (bool tensor [len(rows), len(cols)]) for integer index vectors rows / cols; p as the kernels see it (float32)."""
     import numpy as np
@@ -93,6 +98,11 @@ ROUNDING_SITES = {
     'P':         ('Rv', None,          'softmax numerators enter P.V and dO^T.P as MFMA operands: attention.hip :13-14 ("P and dS go from the accumulator straight into the operand slots" :744)'),
     'dS':        ('Rg', None,          'dS = P (dP - delta) in operand precision, the values dK, dQ consume: attention.hip :743-745'),
     'ctx':       ('R',  None,          'attention output at.ctx = a.ctx :814; its gradient d(ctx) out_t = dctx_t / top_dctx_t :1263-1264'),
+    'delta':     ('Rv', None,          'dS = P (dP - delta) takes delta = rowsum(dO o) from the STORED, rounded attention output, not from sum_k P_k dP_k: attention.hip '
+                                       'attn_delta_kernel :719-724, "delta = rowsum(dO O) already is sum_k P\'_k dP\'_k" :850.  Applied by _Sites.stored_delta, which the '
+                                       'single-launch graph of tests/attn_probe_cases.py calls UNDER DROPOUT, where it decides a bound (a row with one key has '
+                                       'o = v / (1 - p), inexact, and dS = 0 in the reference); without dropout that graph and `forward` below leave it out, and '
+                                       'their bounds, which hold without it, stay what they were'),
     'y_grad':    ('Rg', None,          'LayerNorm-input gradients dy2_t :545 :528, dy1_t :524 :564 (launch_layernorm_bwd dx_t / GemmLNB::dx_t)'),
     'Y':         ('Rv', 'y16',         'pre-LayerNorm sums in fp16 inside the fused GEMMs, g.y16 :393 :421: the next residual add and the LayerNorm backward read the rounded sum'),
     'Yu':        ('Rv', 'y16u',        'fp16 sums ahead of a separate LayerNorm: EPI_RESID_T | EPI_OUT_T :401 :429 -- residual from the operand copy, the rounded sum is what is normalised'),
@@ -119,6 +129,19 @@ class _StraightThrough(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return (ctx.rnd(g) if ctx.rnd is not None else g), None, None, None
+
+
+class _StoredDelta(torch.autograd.Function):
+    """out [B, H, S, D] -> out, with the backward of the flash kernels' delta: they form dS = P (dP - delta) with delta = rowsum(dO rnd(out)) from the stored output,
+    which is sum_k P_k dP_k + c, c = rowsum(dO (rnd(out) - out)).  d(lse) / d(score) is P, so -c leaves through lse [B, H, S] as the missing -c P of dS."""
+    @staticmethod
+    def forward(ctx, out, lse, rnd):
+        ctx.save_for_backward(rnd(out) - out)
+        return out.view_as(out)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return dout, -(dout * ctx.saved_tensors[0]).sum(-1), None
 
 
 class _GeluStoredDerivative(torch.autograd.Function):
@@ -198,11 +221,14 @@ class _NoSites:
     def linear_grad_operand(self, x, w, b):
         return _linear(x, w, b)
 
-    def softmax(self, scores):
+    def softmax(self, scores, ds_site=True):
         return torch.softmax(scores, -1)
 
     def gelu(self, x, keep=None):
         return _gelu(x) if keep is None else _gelu(x) * keep
+
+    def stored_delta(self, out, lse):
+        return out
 
     def layer_norm(self, v, w, b, grad_site, layer=None):
         o = _layer_norm(v, w, b)
@@ -235,14 +261,20 @@ class _Sites(_NoSites):
         shadow = self('xaug', x.detach()) @ w.t()      # (detached: an x that asks for its own gradient gets it from the plain product alone)
         return _linear(x, w.detach(), b) + (shadow - shadow.detach())
 
-    def softmax(self, scores):
-        """the flash kernel's form: the numerators are the MFMA operand (site 'P'), the division by their f32 sum comes last; the scores' gradient is dS"""
-        scores = self('dS', scores)
+    def softmax(self, scores, ds_site=True):
+        """the flash kernel's form: the numerators are the MFMA operand (site 'P'), the division by their f32 sum comes last; the scores' gradient is dS
+        (ds_site=False: the caller has put the 'dS' site on the scores itself, because more than the softmax hangs on them -- stored_delta)"""
+        if ds_site:
+            scores = self('dS', scores)
         pu = torch.exp(scores - scores.amax(-1, keepdim=True))
         return self('P', pu) / pu.sum(-1, keepdim=True)
 
     def gelu(self, x, keep=None):
         return _GeluStoredDerivative.apply(self('pre_grad', x), self.rnd.round, keep)
+
+    def stored_delta(self, out, lse):
+        """site 'delta': out [B, H, S, D] ahead of its 'ctx' site, lse [B, H, S] = logsumexp of the scores that carry the 'dS' site (softmax(..., ds_site=False))"""
+        return _StoredDelta.apply(out, lse, self.rnd.round) if self.on('delta') else out
 
     def layer_norm(self, v, w, b, grad_site, layer=None):
         """(the LayerNorm output the next GEMM operand is cut from, the same rows as the next residual add reads them) of the pre-LayerNorm sum v"""
@@ -297,7 +329,7 @@ def forward(sd, x, y, sep, nhead, dtype=torch.float64, return_hidden=False, drop
             import numpy as np
             keep_scale = 1.0 / (1.0 - float(np.float32(pd)))
             s0 = dropout_site_seed(seed, l, 0)
-            pm = torch.stack([torch.stack([dropout_keep_mask(int(_mix32(s0 ^ ((0xC2B2AE35 * (bb * nhead + hh + 1)) & _M32))), range(T), range(T), pd)
+            pm = torch.stack([torch.stack([dropout_keep_mask(dropout_pair_seed(s0, bb * nhead + hh), range(T), range(T), pd)
                                            for hh in range(nhead)]) for bb in range(B)])                       # [B,H,T,T]
             probs = probs * pm.to(dtype) * keep_scale
             rows = [bb * T + t for t in range(T) for bb in range(B)]                                        # token row of element [t, b]

@@ -91,9 +91,11 @@ class _FlashF32(torch.autograd.Function):
       backward, :583 :601 :733 :1015   P = exp2(fma(S, c, -lse2)), lse2 = f32(lse log2 e): every P of a row is off by the factor 2^(rounding of lse2);
                :743                    dS = P (dP - delta), delta = sum(dO o) from the stored output: two f32 sums of the same products in different orders, so a
                                        row with one visible key has dS ~ 2^-24 |dP|, not 0.
-    The 16-bit formats have the same roundings, 8 - 60 x below their unit roundoff."""
+    The 16-bit formats have the same roundings, 8 - 60 x below their unit roundoff.
+    Dropout (masks = Masks in f32, or None), :447-453 :478: the numerators are masked after the row sums, which stay those of the unmasked softmax, and so does lse;
+    the backward takes dV from P keep / (1 - p), dP = (dO V^T) keep / (1 - p) and delta from the stored (masked) output :849-850 :1058 :1506."""
     @staticmethod
-    def forward(ctx, raw, v, allowed, self_rows):
+    def forward(ctx, raw, v, allowed, self_rows, masks=None):
         D = v.shape[-1]
         c = (torch.tensor(float(D)).rsqrt() * torch.tensor(LOG2E_F32)).double()
         s2 = (raw.double() * c).masked_fill(~allowed, float('-inf'))      # the fma's exact product
@@ -102,9 +104,10 @@ class _FlashF32(torch.autograd.Function):
         m = rounded.amax(-1, keepdim=True)
         p = torch.exp2((torch.where(eye, rounded, s2) - m).float())
         l = p.sum(-1, keepdim=True)
-        out = (p @ v) / l
+        out = ((p if masks is None else p * masks.fwd) @ v) / l
         lse = (m.float() + torch.log2(l)) * LN2_F32
         ctx.save_for_backward(s2, lse * LOG2E_F32, v, out)
+        ctx.masks = masks
         return out, lse.squeeze(-1)
 
     @staticmethod
@@ -112,14 +115,36 @@ class _FlashF32(torch.autograd.Function):
         s2, lse2, v, out = ctx.saved_tensors
         p = torch.exp2((s2 - lse2.double()).float())
         delta = (dout * out).sum(-1, keepdim=True)
-        ds = p * (dout @ v.transpose(-1, -2) - delta)
-        return ds / math.sqrt(v.shape[-1]), p.transpose(-1, -2) @ dout, None, None
+        dp = dout @ v.transpose(-1, -2)
+        if ctx.masks is None:
+            return p * (dp - delta) / math.sqrt(v.shape[-1]), p.transpose(-1, -2) @ dout, None, None, None
+        return p * (dp * ctx.masks.dp - delta) / math.sqrt(v.shape[-1]), (p * ctx.masks.dv).transpose(-1, -2) @ dout, None, None, None
 
 
-def attention_graph(qkv, H, sep, sites=None, allowed=None, bias=None, roll=None, flash_f32=False):
+Masks = namedtuple('Masks', 'fwd dv dp')      # keep / (1 - p) as [B, H, S, S] in the graph's dtype, once per use of the mask: the forward's P', the P' of dV, and dP
+
+
+class _DropPV(torch.autograd.Function):
+    """(P, V) -> P' V with P' = P keep / (1 - p), the backward written out, so that each of its uses of the mask can be faulted on its own:
+        dV = P'^T dO,   dP = (dO V^T) keep / (1 - p);   dS = P (dP - rowsum(dP o P)) is then the softmax's own backward."""
+    @staticmethod
+    def forward(ctx, probs, v, masks):
+        ctx.save_for_backward(probs, v)
+        ctx.masks = masks
+        return (probs * masks.fwd) @ v
+
+    @staticmethod
+    def backward(ctx, dout):
+        probs, v = ctx.saved_tensors
+        return (dout @ v.transpose(-1, -2)) * ctx.masks.dp, (probs * ctx.masks.dv).transpose(-1, -2) @ dout, None
+
+
+def attention_graph(qkv, H, sep, sites=None, allowed=None, bias=None, roll=None, flash_f32=False, masks=None):
     """Dense masked attention on qkv [B, S, 3 E] in qkv's own dtype: (ctx [B, S, E], lse [B, H, S], probabilities [B, H, S, S]).  sites: the rounding hook
     (oracle.pfn_oracle._Sites; None = the plain graph).  allowed [S, S] bool, bias [S, S] added to the scores, roll = the [B, H, ...] dimension along which K and V
-    are read from the next index: the planted faults.  flash_f32 (qkv in f32): softmax and lse as the exact-f32 kernels form them (_FlashF32)."""
+    are read from the next index: the planted faults.  flash_f32 (qkv in f32): softmax and lse as the exact-f32 kernels form them (_FlashF32).
+    masks (Masks in qkv's dtype): dropout on the probabilities, P' = P keep / (1 - p) behind the 'P' site (the kernels zero the numerators in the accumulator and
+    round what is left into the operand slots, attention.hip :447-453); lse and the returned probabilities are those of the unmasked softmax."""
     B, S, E3 = qkv.shape
     E = E3 // 3
     D = E // H
@@ -128,21 +153,27 @@ def attention_graph(qkv, H, sep, sites=None, allowed=None, bias=None, roll=None,
     if roll is not None:
         k, v = k.roll(-1, roll), v.roll(-1, roll)
     if flash_f32:
-        out, lse = _FlashF32.apply(q @ k.transpose(-1, -2), v, visible(S, sep), torch.arange(S) >= sep)
+        out, lse = _FlashF32.apply(q @ k.transpose(-1, -2), v, visible(S, sep), torch.arange(S) >= sep, masks)
         return out.transpose(1, 2).reshape(B, S, E), lse, None
     scores = q @ k.transpose(-1, -2) / math.sqrt(D)
     if bias is not None:
         scores = scores + bias
     scores = scores.masked_fill(~(visible(S, sep, qkv.device) if allowed is None else allowed), float('-inf'))
-    lse = torch.logsumexp(scores, -1)
-    probs = st.softmax(scores)
-    out = probs @ v
+    if masks is None:      # (the graph, hence e and every bound without dropout, as they were before the 'delta' site was found: see the site's entry)
+        lse = torch.logsumexp(scores, -1)
+        probs = st.softmax(scores)
+        out = probs @ v
+    else:
+        scores = st('dS', scores)      # one rounding of all of dS: the softmax's share and the 'delta' site's, which reaches the scores through lse
+        lse = torch.logsumexp(scores, -1)
+        probs = st.softmax(scores, ds_site=False)
+        out = st.stored_delta(_DropPV.apply(probs, v, masks), lse)
     return st('ctx', out.transpose(1, 2).reshape(B, S, E)), lse, probs
 
 
-def attention_reference(qkv, H, sep):
+def attention_reference(qkv, H, sep, masks=None):
     """Dense masked attention in f64 with the mask of generate_D_q_matrix (transformer.py:34-41)."""
-    out, lse, _ = attention_graph(qkv.double(), H, sep)
+    out, lse, _ = attention_graph(qkv.double(), H, sep, masks=masks)
     return out, lse
 
 
@@ -226,16 +257,19 @@ def probabilities(name, rnd, rows=None, fault=None):
     return torch.softmax(scores.masked_fill(~allowed[rows], float('-inf')), -1)
 
 
-def run(name, rnd, fmt, mode, fault=None):
-    """{ctx, dQ, dK, dV: [B, H, S, D], lse: [B, H, S], smax: the largest visible |score|} in f64.  mode 'ref': the f64 graph; 'emul': the format's emulation."""
+def run(name, rnd, fmt, mode, fault=None, drop=None):
+    """{ctx, dQ, dK, dV: [B, H, S, D], lse: [B, H, S], smax: the largest visible |score|} in f64.  mode 'ref': the f64 graph; 'emul': the format's emulation.
+    drop = (p, site seed): dropout on the probabilities; fault is then a DropFault (or None)."""
     case = CASES[name]
     qkv, dctx = inputs(name, rnd, fmt)
-    sites, kw = None, fault_kwargs(case, fault)
+    sites, kw = None, fault_kwargs(case, fault) if drop is None else {}
     if mode == 'emul':
         if fmt == 'f32':
             qkv, dctx, kw = qkv.float(), dctx.float(), dict(flash_f32=True)
         else:
             sites = O._Sites(O.Rounding(fmt), {})
+    if drop is not None:
+        kw['masks'] = drop_masks(case, drop, fault, qkv.dtype)
     qkv.requires_grad_(True)
     ctx, lse, probs = attention_graph(qkv, case.H, case.sep, sites, **kw)
     dqkv, = torch.autograd.grad(ctx, qkv, dctx)
@@ -279,10 +313,11 @@ def lse_error(got, ref, smax, first=0):
 
 
 @functools.lru_cache(maxsize=48)
-def reference(name, rnd, fmt):
-    """(the f64 reference of the round on the format's inputs, {tensor: e}, {tensor: bound}); 'lse': e and bound of the f32 graph, whatever the format"""
+def reference(name, rnd, fmt, drop=None):
+    """(the f64 reference of the round on the format's inputs, {tensor: e}, {tensor: bound}); 'lse': e and bound of the f32 graph, whatever the format.
+    drop = (p, site seed): reference and emulation under the same dropout masks (lse is that of the unmasked softmax: no mask enters it)"""
     case = CASES[name]
-    ref, emu, sc = run(name, rnd, fmt, 'ref'), run(name, rnd, fmt, 'emul'), scales(name, rnd, fmt)
+    ref, emu, sc = run(name, rnd, fmt, 'ref', drop=drop), run(name, rnd, fmt, 'emul', drop=drop), scales(name, rnd, fmt)
     first = q_first(case)
     e = {t: statistic(emu[t], ref[t], sc[t], first if t == 'ctx' else 0) for t in TENSORS}
     bound = {t: stack_cases.bound(fmt, e[t]) for t in TENSORS}
@@ -399,3 +434,159 @@ def fault_multiples(name, fmt, fault):
         for t in TENSORS:
             out[t] = max(out[t], statistic(bad[t], ref[t], sc[t], first if t == 'ctx' else 0) / bound[t])
     return fault_rounds(name, fault), out
+
+
+# ---- dropout on the probabilities (attn_fwd_kernel / attn_bwd_kv_kernel / attn_bwd_dq_kernel <DROP = true>, the `drop` branches of attn_bwd_plain_*) ----------------
+# The mask is never stored: every pass regenerates keep(pair seed, query, key) from indices, in its own register layout.  The planted keys make one key worth
+# 1/16 .. 1 of a row, so one wrong mask bit on a targeted key moves ctx, dV, and through dS dQ and dK, by a sizeable part of their scale.
+DROP_CASES = ('S100-sep70', 'S333-sep301', 'S300-sep257', 'S520-sep512', 'S300-sep200-D256', 'S200-sep1', 'S130-sep0')      # (no q_begin: the stack never combines it with live dropout)
+# (p, site seed = what dropout_site_seed(call seed, layer, 0) yields); the second seed has its top bit set.  Each seed is the first from 12345 / 0x9E3779B9 upwards
+# that meets drop_coverage_gaps on every case: S130-sep0 has one round and a ragged last slab of two queries, of which one must keep its self key and the other lose
+# it in each of the four (dataset, head) pairs -- 1 seed in 100 at p = 0.2 (12345 and 0x9E3779B9 themselves meet the condition everywhere else)
+DROP_PAIRS = ((0.2, 12523), (0.5, 0x9E3779C8))
+MASK_TILE = 64
+
+
+def residue_tensors(name, drop):
+    """the tensors whose exact zero in the reference the kernels do NOT return exactly: without train rows dQ and dK are zero, and launch_attn_bwd sends such a batch
+    through the self-only kernel only without dropout (attention.hip launch_attn_bwd); under dropout the general query-block pass runs, and its
+    dS = P (dP - delta), delta from the stored output, is ~2^-24 |dP|: held to the bound on the floored scale instead"""
+    return ('dQ', 'dK') if drop is not None and CASES[name].sep == 0 else ()
+
+
+def keep_scale(p):
+    """1 / (1 - p) with p as the kernels see it (float32)"""
+    return 1.0 / (1.0 - torch.tensor(p, dtype=torch.float32).item())
+
+
+@functools.lru_cache(maxsize=None)
+def keep_masks(case, site_seed, p):
+    """[B, H, S, S] bool: keep(query i, key j) of every (dataset, head), the integers of pfn_kernels.h dropout_pair_seed / dropout_keep"""
+    r = range(case.S)
+    return torch.stack([torch.stack([O.dropout_keep_mask(O.dropout_pair_seed(site_seed, b * case.H + h), r, r, p) for h in range(case.H)]) for b in range(case.B)])
+
+
+DropFault = namedtuple('DropFault', 'cls label kind arg')
+MASK_CLASSES = ('mask of key j + 1', 'key index modulo 256', 'query index modulo 256', 'mask of head h + 1', 'mask of dataset b + 1', 'self key unmasked')
+BACKWARD_CLASSES = ('keep transposed in the backward', 'dV from the unmasked P', 'dP without keep', 'dP without 1 / (1 - p)')
+FORWARD_CLASSES = ('ctx without 1 / (1 - p)',)
+
+
+def faulted_keep(case, keep, fault):
+    S, out = case.S, keep.clone()
+    if fault.kind == 'shift':      # the mask of key j + 1 for key j, inside one tile of 64 keys, for the queries of one slab
+        (lo, hi), t0 = fault.arg
+        j = torch.arange(t0, min(t0 + MASK_TILE, S - 1))
+        out[:, :, lo:hi, j] = keep[:, :, lo:hi, j + 1]
+    elif fault.kind == 'keymod':
+        out[..., 256:] = keep[..., torch.arange(256, S) % 256]
+    elif fault.kind == 'querymod':
+        out[:, :, 256:] = keep[:, :, torch.arange(256, S) % 256]
+    elif fault.kind == 'roll':
+        out = keep.roll(-1, fault.arg)
+    elif fault.kind == 'self':
+        i = torch.arange(case.sep, S)
+        out[:, :, i, i] = True
+    elif fault.kind == 'transpose':
+        out = keep.transpose(-1, -2)
+    elif fault.kind == 'unmasked':
+        out[:] = True
+    return out
+
+
+@functools.lru_cache(maxsize=6)
+def _plain_masks(case, drop, dtype):
+    m = keep_masks(case, drop[1], drop[0]).to(dtype) * keep_scale(drop[0])
+    return Masks(m, m, m)
+
+
+def drop_masks(case, drop, fault=None, dtype=torch.float64):
+    """Masks of a (p, site seed) pair; fault (a DropFault): a mask fault goes into all three uses, a backward-only one into dV and / or dP, the forward-only one into ctx"""
+    plain = _plain_masks(case, drop, dtype)
+    if fault is None:
+        return plain
+    p, seed = drop
+    keep, scale = keep_masks(case, seed, p), keep_scale(p)
+    uses = {'transpose': ('dv', 'dp'), 'unmasked': (fault.arg,), 'unscaled': (fault.arg,)}.get(fault.kind, Masks._fields)
+    bad = (keep if fault.kind == 'unscaled' else faulted_keep(case, keep, fault)).to(dtype) * (1.0 if fault.kind == 'unscaled' else scale)
+    return Masks(*[bad if f in uses else getattr(plain, f) for f in Masks._fields])
+
+
+def drop_faults(name):
+    """(the same in every format: the mask knows no format).  Left out where the arithmetic cannot show them: an index taken modulo 256 needs a visible key or a
+    query >= 256; without train rows only keep(i, i) is ever used, which a transposed mask leaves alone, and a row with one visible key has dS = 0 whatever dP is"""
+    case = CASES[name]
+    S, sep = case.S, case.sep
+    full = S // SLAB - 1                                    # the last full slab
+    slab = lambda s: (SLAB * s, SLAB * s + SLAB)
+    t_last = ((sep - 1) if sep else SLAB * full) // MASK_TILE * MASK_TILE      # the tile of the last train key (without train rows: of the slab's self keys)
+    out = [DropFault(MASK_CLASSES[0], f'mask of key j + 1 for keys 0..{MASK_TILE - 1}, queries 0..{SLAB - 1}', 'shift', (slab(0), 0)),
+           DropFault(MASK_CLASSES[0], f'mask of key j + 1 for keys {t_last}..{t_last + MASK_TILE - 1}, queries {slab(full)[0]}..{slab(full)[1] - 1}', 'shift', (slab(full), t_last))]
+    if S > 256:
+        out.append(DropFault(MASK_CLASSES[1], 'key index modulo 256', 'keymod', None))
+        out.append(DropFault(MASK_CLASSES[2], 'query index modulo 256', 'querymod', None))
+    if case.H > 1:
+        out.append(DropFault(MASK_CLASSES[3], 'mask of head h + 1', 'roll', 1))
+    if case.B > 1:
+        out.append(DropFault(MASK_CLASSES[4], 'mask of dataset b + 1', 'roll', 0))
+    out.append(DropFault(MASK_CLASSES[5], f'self key of test rows {sep}..{S - 1} unmasked', 'self', None))
+    if sep > 0:
+        out.append(DropFault(BACKWARD_CLASSES[0], 'keep transposed in dV and dP', 'transpose', None))
+    out.append(DropFault(BACKWARD_CLASSES[1], 'dV from the unmasked P', 'unmasked', 'dv'))
+    if sep > 0:
+        out.append(DropFault(BACKWARD_CLASSES[2], 'dP without keep', 'unmasked', 'dp'))
+        out.append(DropFault(BACKWARD_CLASSES[3], 'dP without 1 / (1 - p)', 'unscaled', 'dp'))
+    out.append(DropFault(FORWARD_CLASSES[0], 'ctx without 1 / (1 - p)', 'unscaled', 'fwd'))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def drop_fault_rounds(name, drop):
+    """{fault label: per kind of round, the one in which the fault moves a masked probability P keep / (1 - p) most}: one pass over the rounds for all the faults of
+    a case (the suite runs every round, so a fault shows on a tensor if one round shows it there)"""
+    case = CASES[name]
+    plain = drop_masks(case, drop)
+    diffs = {}
+    for f in drop_faults(name):
+        bad = drop_masks(case, drop, f)
+        diffs[f.label] = torch.stack([(getattr(bad, u) - getattr(plain, u)).abs() for u in Masks._fields]).amax(0)
+    best = {label: {} for label in diffs}
+    for rnd in rounds(case):
+        p = probabilities(name, rnd)
+        for label, d in diffs.items():
+            moved = (p * d).max().item()
+            if moved > best[label].get(rnd[0], (None, 1e-3))[1]:
+                best[label][rnd[0]] = (rnd, moved)
+    return {label: [rnd for rnd, _ in b.values()] for label, b in best.items()}
+
+
+def drop_fault_multiples(name, fmt, drop, fault):
+    """{tensor: the statistic of the faulted f64 reference against the right one / the bound the GPU test asserts}, the largest over drop_fault_rounds, and those rounds"""
+    rnds = drop_fault_rounds(name, drop)[fault.label]
+    out = dict.fromkeys(TENSORS, 0.0)
+    for rnd in rnds:
+        ref, _, bound = reference(name, rnd, fmt, drop)
+        bad, sc = run(name, rnd, fmt, 'ref', fault, drop), scales(name, rnd, fmt)
+        for t in TENSORS:
+            out[t] = max(out[t], statistic(bad[t], ref[t], sc[t]) / bound[t])
+    return rnds, out
+
+
+def drop_coverage_gaps(name, drop):
+    """What the masks of a (p, site seed) pair leave untested on a case, in words (empty: nothing).  A targeted key is one with p >= 1/16 in the unmasked softmax.
+    In every round, every (dataset, head) and every full 32-query slab some query must keep a targeted key and some query must lose one; the ragged last slab
+    must do both over the rounds of the case taken together."""
+    case = CASES[name]
+    keep = keep_masks(case, drop[1], drop[0])
+    full = case.S // SLAB
+    gaps, tail = [], torch.zeros(2, case.B, case.H, dtype=torch.bool)
+    for rnd in rounds(case):
+        big = probabilities(name, rnd) >= 1 / 16
+        both = torch.stack([(big & keep).any(-1), (big & ~keep).any(-1)])      # [2, B, H, S]: the query keeps / loses a targeted key
+        slabs = both[..., :full * SLAB].reshape(2, case.B, case.H, full, SLAB).any(-1)
+        for w, b, h, s in (~slabs).nonzero().tolist():
+            gaps.append(f'round {rnd[0]} {rnd[1]}, dataset {b}, head {h}, slab {s}: no query {("keeps", "loses")[w]} a targeted key')
+        tail |= both[..., full * SLAB:].any(-1)
+    if case.S % SLAB:
+        gaps += [f'dataset {b}, head {h}, the ragged last slab: no query {("keeps", "loses")[w]} a targeted key in any round' for w, b, h in (~tail).nonzero().tolist()]
+    return gaps

@@ -181,6 +181,9 @@ SIGNATURES = {
     'pfn_op_gather_rows': (_I, [_P, _P, _I, _I, _L, _I, _P]),
     'pfn_op_scatter_rows': (_I, [_P, _P, _I, _I, _L, _I, _I, _P]),
     'pfn_op_attention_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    # (test only, ABI 10, additive) the pair above with dropout on the probabilities: (..., prec[, parts], p_drop, site seed, stream)
+    'pfn_op_attention_fwd_dropout': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _c.c_uint32, _P]),
+    'pfn_op_attention_bwd_dropout': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _c.c_uint32, _P]),
     'pfn_op_layernorm_fwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P]),
     'pfn_op_layernorm_bwd': (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),
     'pfn_op_cast': (_I, [_P, _P, _L, _I, _P]),

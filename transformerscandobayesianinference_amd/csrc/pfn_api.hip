@@ -1446,6 +1446,25 @@ int pfn_op_attention_bwd(const void* qkv, const void* ctx, const float* lse, con
   PFN_TRY(launch_attn_bwd(at, prec, (hipStream_t)stream));
   return PFN_OK;
 }
+int pfn_op_attention_fwd_dropout(const void* qkv, void* ctx, float* lse, int B, int S, int E, int H, int sep, int prec, float p_drop, uint32_t drop_seed,
+                                 void* stream) {
+  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(PFN_ERR_ARGUMENT, "attention dropout: p_drop outside [0, 1)");
+  AttnArgs at; memset(&at, 0, sizeof(at));
+  at.qkv = qkv; at.ctx = ctx; at.lse = lse; at.B = B; at.S = S; at.E = E; at.H = H; at.sep = sep;
+  at.p_drop = p_drop; at.drop_seed = drop_seed;
+  PFN_TRY(launch_attn_fwd(at, prec, (hipStream_t)stream));
+  return PFN_OK;
+}
+int pfn_op_attention_bwd_dropout(const void* qkv, const void* ctx, const float* lse, const void* dctx, void* dqkv, float* delta_ws, void* ds_ws,
+                                 int B, int S, int E, int H, int sep, int prec, int parts, float p_drop, uint32_t drop_seed, void* stream) {
+  if (!(p_drop >= 0.f && p_drop < 1.f)) return fail(PFN_ERR_ARGUMENT, "attention dropout: p_drop outside [0, 1)");
+  AttnArgs at; memset(&at, 0, sizeof(at));
+  at.qkv = qkv; at.ctx = const_cast<void*>(ctx); at.lse = const_cast<float*>(lse); at.B = B; at.S = S; at.E = E; at.H = H; at.sep = sep;
+  at.dctx = dctx; at.dqkv = dqkv; at.delta = delta_ws; at.ds = ds_ws; at.parts = parts;
+  at.p_drop = p_drop; at.drop_seed = drop_seed;
+  PFN_TRY(launch_attn_bwd(at, prec, (hipStream_t)stream));
+  return PFN_OK;
+}
 int pfn_op_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y_f32, void* y_t, float* mean, float* rstd,
                          int64_t rows, int E, float eps, int prec, void* stream) {
   PFN_TRY(launch_layernorm_fwd(x, gamma, beta, y_f32, y_t, mean, rstd, rows, E, eps, prec, (hipStream_t)stream));

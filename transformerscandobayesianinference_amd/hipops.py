@@ -76,11 +76,19 @@ def gemm_ln(A, B, bias, gamma, beta, eps, resid=None, prev=None, out=None, sums1
     return y[:M], x_t, mean, rstd
 
 
-def attention_fwd(qkv, H, sep, prec, q_begin=0, out=None):
+def attention_fwd(qkv, H, sep, prec, q_begin=0, out=None, p_drop=0.0, drop_seed=0):
     """q_begin > 0: the queries below it (rounded down to a multiple of 256) are skipped -- their ctx / lse rows keep the NaN fill
-    (or whatever `out` = (ctx, lse) held: timing loops pass buffers so that no fill kernel runs between the launches)."""
+    (or whatever `out` = (ctx, lse) held: timing loops pass buffers so that no fill kernel runs between the launches).
+    p_drop > 0 (tests): dropout on the probabilities with the site seed drop_seed (pfn_op_attention_fwd_dropout; not with q_begin)."""
     B, S, E3 = qkv.shape
     E = E3 // 3
+    if p_drop:
+        if q_begin:
+            raise _hip.HipExtensionError('attention_fwd: no entry point combines q_begin with dropout')
+        ctx = torch.full((B, S, E), float('nan'), dtype=qkv.dtype, device=qkv.device)      # (tests only: a row the kernel skipped shows)
+        lse = torch.full((B, H, S), float('nan'), dtype=torch.float32, device=qkv.device)
+        _hip.check(_hip.lib().pfn_op_attention_fwd_dropout(qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), B, S, E, H, sep, prec, p_drop, drop_seed, sp()), 'attn fwd')
+        return ctx, lse
     if q_begin:
         if out is not None:
             ctx, lse = out
@@ -140,10 +148,10 @@ ATTENTION_BWD_KV_EXECUTED_UNITS = {}
 _bwd_scratch = {}
 
 
-def attention_bwd(qkv, ctx, lse, dctx, H, sep, prec, parts=0, q_begin=0):
+def attention_bwd(qkv, ctx, lse, dctx, H, sep, prec, parts=0, q_begin=0, p_drop=0.0, drop_seed=0):
     """parts = 0: the whole backward (outputs start as NaN so a skipped element shows).  parts != 0 (timing): only the selected
     launches, into cached scratch buffers (the skipped launches' products must exist from an earlier full call with the same
-    shapes for the numbers to mean anything)."""
+    shapes for the numbers to mean anything).  p_drop > 0 (tests): the forward's dropout (pfn_op_attention_bwd_dropout; not with q_begin)."""
     B, S, E3 = qkv.shape
     E = E3 // 3
     key = (tuple(qkv.shape), qkv.dtype, qkv.device, H)
@@ -156,6 +164,12 @@ def attention_bwd(qkv, ctx, lse, dctx, H, sep, prec, parts=0, q_begin=0):
     if not parts:
         dqkv = torch.full_like(qkv, float('nan'))
         ds.fill_(0xff)                                 # NaN patterns: a dS^T element the key-block pass skipped would show in dQ
+    if p_drop:
+        if q_begin:
+            raise _hip.HipExtensionError('attention_bwd: no entry point combines q_begin with dropout')
+        _hip.check(_hip.lib().pfn_op_attention_bwd_dropout(qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(),
+                                                           delta.data_ptr(), ds.data_ptr(), B, S, E, H, sep, prec, parts, p_drop, drop_seed, sp()), 'attn bwd')
+        return dqkv
     if q_begin:
         _hip.check(_hip.lib().pfn_op_attention_bwd_from(qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(),
                                                         delta.data_ptr(), ds.data_ptr(), B, S, E, H, sep, q_begin, prec, parts, sp()), 'attn bwd')
